@@ -9,8 +9,16 @@ under torchrun; without an outer torchrun the script starts it as a child proces
 shards trials by index: weak scaling, no data-path collective; the per-step error counts
 are summed across ranks once at the end (RCCL all_reduce).
 
-After the headline's timed region the same ranks time north_star's own split, BASELINE
-config 4's 915-point SNR x IBO grid dealt over them (``grid`` object; ``--no-grid`` skips it).
+A plain run sets up, warms up, times the steps and prints the line.  ``--full`` adds what
+takes work of its own: after the headline's timed region the same ranks time north_star's
+own split, BASELINE config 4's 915-point SNR x IBO grid dealt over them (``grid`` object;
+``--no-grid`` skips it), the BER is set against the published value (``ber_vs_published``)
+and the host's CPU baseline is measured (``cpu_baseline``; ``--no-cpu-baseline`` skips it).
+
+``--dump-outputs DIR`` writes what the last timed step returned to its caller (the error
+and bit counters of ``Engine.run``) as ``DIR/err.npy`` and ``DIR/bits.npy`` (float64; with
+N > 1 ranks ``err_rank<r>.npy`` / ``bits_rank<r>.npy``).  Seed and trial indices are fixed,
+so the same arguments give the same inputs in every run.
 
 Prints ONE JSON line (rank 0).
 """
@@ -342,14 +350,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=1 << 16, help="trials (OFDM symbols) per GPU per step")
     ap.add_argument("--iters", type=str, default="0", help="receiver iterations, e.g. 0 or 0,1,2,3,4")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the config-4 grid line, the BER "
+                         "against the published value and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--precision", default="f64", choices=["f64", "f32"],
                     help="arithmetic type of the fused kernel (f64 = the reference's float64)")
     ap.add_argument("--workload", default="2", choices=sorted(WORKLOADS),
                     help="2 = BASELINE config 2 (headline); paper; 5su (config-5 array, one user)")
     ap.add_argument("--check-launch", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--no-grid", action="store_true", help="skip the config-4 grid line (the 'grid' object)")
+    ap.add_argument("--no-grid", action="store_true",
+                    help="with --full: skip the config-4 grid line (the 'grid' object)")
     ap.add_argument("--grid-split", choices=["points", "trials"], default="points",
                     help="the grid's multi-GPU split: whole points by cost (default), or every point's trials")
     ap.add_argument("--grid-check", action="store_true", help=argparse.SUPPRESS)
@@ -428,6 +442,12 @@ def main():
         c = torch.tensor(err_tot.astype(np.int64), device=tdev)
         dist.all_reduce(c)
         err_tot = c.cpu().numpy()
+    if args.dump_outputs and args.steps > 0:
+        # e, b: what Engine.run handed back in the last timed step (this rank's trials)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        tag = "" if world == 1 else f"_rank{rank}"
+        np.save(os.path.join(args.dump_outputs, f"err{tag}.npy"), np.asarray(e, dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, f"bits{tag}.npy"), np.asarray(b, dtype=np.float64))
     total_trials = B * args.steps * world
     value = total_trials / dt
     avg_kernel_s = kern_ms / 1e3 / args.steps
@@ -472,11 +492,11 @@ def main():
                         "trials; the fused kernel does not move them (a model figure, not traffic)"},
         "ber": [round(float(x) / (total_trials * wl["S"] * np.log2(wl["M"])), 8) for x in err_tot],
     }
-    if args.workload == "2" and iters == [0]:
+    if args.full and args.workload == "2" and iters == [0]:
         out["ber_vs_published"] = ber_vs_published(out["ber"][0])
-    if not args.no_grid and args.workload == "2" and args.precision == "f64":
+    if args.full and not args.no_grid and args.workload == "2" and args.precision == "f64":
         out["grid"] = time_grid(rank, world, dist, dev, args.precision, tdev, split=args.grid_split)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, args.workload, iters)
     if dist:
         dist.destroy_process_group()

@@ -58,13 +58,15 @@ def test_world_size_mismatch_exits_nonzero():
 def test_bench_gpus_two_on_one_gpu_reports_both_ranks():
     """The full bench step with two gloo ranks sharing GPU 0 (the driver's N > 1 path uses RCCL,
     one GPU per rank): the line reports n_gpus 2 and counts trials of both ranks."""
-    p = _run(["--gpus", "2", "--no-cpu-baseline", "--steps", "2", "--warmup", "1", "--batch", "4096"], timeout=300)
+    p = _run(["--gpus", "2", "--full", "--no-cpu-baseline", "--steps", "2", "--warmup", "1", "--batch", "4096"],
+             timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     d = _json_line(p.stdout)
     assert d["n_gpus"] == 2 and d["config"]["parallelism"] == "trial-sharded x2"
     assert d["value"] > 0 and 0 < d["ber"][0] < 1e-2
     # the grid object: the 915-point config-4 grid dealt over both ranks equals one rank's grid
-    p1 = _run(["--gpus", "1", "--no-cpu-baseline", "--steps", "1", "--warmup", "1", "--batch", "4096"], timeout=300)
+    p1 = _run(["--gpus", "1", "--full", "--no-cpu-baseline", "--steps", "1", "--warmup", "1", "--batch", "4096"],
+              timeout=300)
     assert p1.returncode == 0, p1.stderr[-3000:]
     g1, g2 = _json_line(p1.stdout)["grid"], d["grid"]
     print("grid 1 rank", g1, "grid 2 ranks", g2)
@@ -100,7 +102,7 @@ def test_bench_rccl_process_group_at_world_one():
         port = so.getsockname()[1]
     env = dict(os.environ, MIMO_BENCH_BACKEND="nccl", MASTER_ADDR="127.0.0.1")
     env.pop("WORLD_SIZE", None)
-    args = ["--gpus", "1", "--no-cpu-baseline", "--steps", "2", "--warmup", "1", "--batch", "4096"]
+    args = ["--gpus", "1", "--full", "--no-cpu-baseline", "--steps", "2", "--warmup", "1", "--batch", "4096"]
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
                         "--master-addr", "127.0.0.1", f"--master-port={port}", BENCH] + args,
                        capture_output=True, text=True, env=env, timeout=300, cwd=REPO)
@@ -113,3 +115,31 @@ def test_bench_rccl_process_group_at_world_one():
     assert d["n_gpus"] == 1 and d["grid"]["ranks_seen"] == 1 and len(d["grid"]["per_rank"]) == 1
     assert d["grid"]["counts_digest"] == d0["grid"]["counts_digest"]
     assert d["ber"] == d0["ber"]
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_last_step(tmp_path):
+    """A plain run carries the headline fields only (the grid, the CPU baseline and the
+    published-BER comparison are behind --full), times exactly --steps steps, and
+    --dump-outputs writes the counters Engine.run returned in the last timed step: equal to
+    the same trials (fixed seed, step index x batch) run again in this process."""
+    import numpy as np
+
+    sys.path.insert(0, REPO)
+    import bench
+    steps, warmup, B = 3, 1, 4096
+    out = tmp_path / "dump"
+    p = _run(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--batch", str(B),
+              "--dump-outputs", str(out)], timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = _json_line(p.stdout)
+    assert not {"grid", "cpu_baseline", "ber_vs_published"} & set(d)
+    assert d["steps"] == steps and d["ms_per_step"] > 0 and d["dtype"] == "f64" and d["higher_is_better"]
+    assert abs(d["value"] * d["ms_per_step"] / 1e3 / B - 1) < 1e-2   # value = batch / time of one step
+    assert sorted(os.listdir(out)) == ["bits.npy", "err.npy"]
+    err, bits = np.load(out / "err.npy"), np.load(out / "bits.npy")
+    assert err.dtype == bits.dtype == np.float64 and err.shape == bits.shape == (1,)
+    e, b, _ = bench.make_engine(0).run(2137, (warmup + steps - 1) * B, B, [0], False)
+    print("dumped", err, bits, "again", e, b)
+    assert np.array_equal(err, e.astype(np.float64)) and np.array_equal(bits, b.astype(np.float64))
+    assert 0 < err[0] < bits[0] == B * 1024 * 6

@@ -57,7 +57,7 @@ case $MODE in
     if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
     timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 || exit $?
     cat "$O/smoke.log"
-    timeout -k 10 300 python bench.py > "$O/bench.json" 2> "$O/bench.err" || exit $?
+    timeout -k 10 300 python bench.py --full > "$O/bench.json" 2> "$O/bench.err" || exit $?
     cat "$O/bench.json"
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o run -- python3 bench.py $N --steps 5 > "$O/prof.log" 2>&1 || exit $?
     cp "$O"/prof/*/run_kernel_stats.csv "$O/bench_kernel_stats.csv" 2> /dev/null || cp "$O"/prof/run_kernel_stats.csv "$O/bench_kernel_stats.csv" 2> /dev/null
