@@ -18,8 +18,12 @@
 
 #include "../../include/mimo_engine.h"
 #include "trial_launch.h"
+#include "host_tables.h"
 
 namespace {
+
+using mimo::AlphaFit;
+using mimo::fit_alpha;
 
 thread_local std::string g_err;
 
@@ -51,120 +55,6 @@ __global__ void reduce_counts(const uint32_t* __restrict__ c, const uint32_t* __
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
   if ((threadIdx.x & 63) == 0) atomicAdd(&tot[(size_t)point_of[k] * n_idx + idx], acc);
-}
-
-// Bussgang gain of modulation.py:178-189 as a function of gamma^2.
-double alpha_exact(double g2) {
-  const double g = std::sqrt(g2);
-  return 1.0 - std::exp(-g2) + 0.88622692545275801 * g * std::erfc(g);
-}
-
-// Degree-8 fit of alpha(g0^2 / (1 + x)) on |x| <= 0.25 (x = relative deviation of an
-// antenna's precoding power from its mean S/A, a few % for MRT): Chebyshev interpolation
-// at 64 nodes, converted to monomials in x for a Horner evaluation in fp32.  Max relative
-// error ~1e-7 for IBO in [-10, 30] dB (fp32 rounding level); the kernel falls back to
-// the exact formula outside the interval.
-struct AlphaFit {
-  double apoly[9];   // fp32 Horner monomials in x
-  double xlim;
-  double amono[19];  // fp64 Horner monomials in x (degree 18)
-};
-
-AlphaFit fit_alpha(double g0sq) {
-  AlphaFit p{};
-  constexpr int N = 64, D = 8;
-  constexpr double L = 0.25;
-  double c[D + 1] = {0};
-  for (int j = 0; j < N; ++j) {
-    const double th = M_PI * (j + 0.5) / N, t = std::cos(th);
-    const double f = alpha_exact(g0sq / (1.0 + L * t));
-    for (int k = 0; k <= D; ++k) c[k] += f * std::cos(k * th) * (k == 0 ? 1.0 : 2.0) / N;
-  }
-  // Chebyshev -> monomials in t (T_{k+1} = 2 t T_k - T_{k-1}), then t = x / L
-  double Tm1[D + 1] = {0}, T0[D + 1] = {0}, mono[D + 1] = {0};
-  T0[0] = 1.0;
-  for (int k = 0; k <= D; ++k) {
-    for (int i = 0; i <= D; ++i) mono[i] += c[k] * T0[i];
-    double Tn[D + 1] = {0};
-    for (int i = 0; i <= D; ++i) {
-      if (i > 0) Tn[i] += (k == 0 ? 1.0 : 2.0) * T0[i - 1];  // T_1 = t
-      Tn[i] -= Tm1[i];
-    }
-    for (int i = 0; i <= D; ++i) {
-      Tm1[i] = T0[i];
-      T0[i] = Tn[i];
-    }
-  }
-  double sc = 1.0;
-  for (int i = 0; i <= D; ++i, sc /= L) p.apoly[i] = mono[i] * sc;
-  p.xlim = L;
-  // fp64: Chebyshev interpolant of degree 18 on the same interval at 64 nodes, in long
-  // double, converted to monomials in x (Horner in the kernel: 18 FMAs with the
-  // coefficients in SGPRs, instead of Clenshaw's 36 ops).  The Taylor radius is 4
-  // half-widths (the pole of g0^2 / (1 + x) at x = -1), so the monomials stay O(1) and
-  // the Horner sum is as accurate as Clenshaw: <= 1.6e-16 relative against the long
-  // double formula over 2e6 points for IBO -5 ... 30 dB (the Clenshaw form: <= 2.1e-16).
-  constexpr int D64 = 18;
-  long double ck[D64 + 1];
-  for (int k = 0; k <= D64; ++k) {
-    long double s = 0.0L;
-    for (int j = 0; j < N; ++j) {
-      const long double th = 3.14159265358979323846264338327950288L * (j + 0.5L) / N;
-      const long double t = std::cos(th);
-      const long double g2 = (long double)g0sq / (1.0L + (long double)L * t);
-      const long double g = std::sqrt(g2);
-      const long double f = 1.0L - std::exp(-g2) + 0.886226925452758013649083741671L * g * std::erfc(g);
-      s += f * std::cos(k * th);
-    }
-    ck[k] = s * (k == 0 ? 1.0L : 2.0L) / N;
-  }
-  long double Um1[D64 + 1] = {0}, U0[D64 + 1] = {0}, um[D64 + 1] = {0};
-  U0[0] = 1.0L;
-  for (int k = 0; k <= D64; ++k) {
-    for (int i = 0; i <= D64; ++i) um[i] += ck[k] * U0[i];
-    long double Un[D64 + 1] = {0};
-    for (int i = 0; i <= D64; ++i) {
-      if (i > 0) Un[i] += (k == 0 ? 1.0L : 2.0L) * U0[i - 1];
-      Un[i] -= Um1[i];
-    }
-    for (int i = 0; i <= D64; ++i) {
-      Um1[i] = U0[i];
-      U0[i] = Un[i];
-    }
-  }
-  long double scl = 1.0L;
-  for (int i = 0; i <= D64; ++i, scl /= (long double)L) p.amono[i] = (double)(um[i] * scl);
-  return p;
-}
-
-// fp64 Box-Muller tables (real.h ln_unit / sincos_lut), computed in long double, followed
-// by the Bussgang-gain segment table (alpha_fit.h; stays in HBM, the kernel copies only the
-// first kLut64 entries into LDS).
-constexpr int kLut64Alloc = mimo::kLut64 + (mimo::kAlphaTabDoubles + 1) / 2;
-std::vector<double2> lut64_table() {
-  std::vector<double2> t(kLut64Alloc);
-  {
-    const std::vector<double> at = mimo::alpha_segment_table();
-    double* dst = reinterpret_cast<double*>(t.data() + mimo::kLut64);
-    for (int i = 0; i < mimo::kAlphaTabDoubles; ++i) dst[i] = at[i];
-  }
-  {  // real.h ln_unit: bucket i = m in [0.5 + i 2^-10, 0.5 + (i + 1) 2^-10), c = 1 for the top one
-    for (int i = 0; i < mimo::kLnTab; ++i) {
-      double c = 1.0;
-      if (i != mimo::kLnTab - 1) {
-        const long double ctr = 0.5L + (i + 0.5L) / 1024.0L;
-        int ex;
-        const long double fr = std::frexp(1.0L / ctr, &ex);
-        c = (double)std::ldexp(std::round(std::ldexp(fr, 12)), ex - 12);
-      }
-      t[i] = make_double2(c, (double)(-std::log((long double)c)));
-    }
-  }
-  for (int i = 0; i < mimo::kScTab; ++i) {
-    const long double a = 2.0L * 3.14159265358979323846264338327950288L * i / mimo::kScTab;
-    t[mimo::kLnTab + i] = make_double2((double)std::cos(a), (double)std::sin(a));
-  }
-  return t;
 }
 
 }  // namespace
@@ -395,78 +285,22 @@ int ensure_device(mimo_engine* e) {
   HIP_TRY(hipEventCreate(&e->ev0));
   HIP_TRY(hipEventCreate(&e->ev1));
   const int F = e->cfg.n_fft, S = e->cfg.n_sub_carr, A = e->cfg.n_ant;
-  // team-FFT stage twiddles per team size (team_fft.h plan), computed in double:
-  // stage s, entry [r][jm] = exp(-j 2 pi e / F) with e = jm r F / (NS R)
-  auto twiddles_of = [](int F, int T, auto cvt) {
-    const int P = F / T;
-    using V = decltype(cvt(0.0, 0.0));
-    std::vector<V> tw(std::max(1, mimo::fft_tw_total(F, P)), cvt(0.0, 0.0));
-    for (int st = 1; st < mimo::fft_nst(F, P); ++st) {
-      const int NS = 1 << mimo::fft_bits_before(F, P, st), R = 1 << mimo::fft_bits(F, P, st);
-      V* blk = tw.data() + mimo::fft_tw_off(F, P, st);
-      for (int r = 0; r < R; ++r)
-        for (int jm = 0; jm < NS; ++jm) {
-          const long e_idx = (long)jm * r * (F / (NS * R));
-          const double ang = -2.0 * M_PI * (double)e_idx / (double)F;
-          blk[r * NS + jm] = cvt(std::cos(ang), std::sin(ang));
-        }
-    }
-    return tw;
-  };
-  // cot-tan constants of the twiddled stages (team_fft.h dft8_ct / dft16_ct), appended to a
-  // stage table: (cos a, tan a) per (stage, row, lane); cos is never exactly 0 in double
-  // (cos(pi/2) = 6.1e-17), so tan stays finite
-  // (appended for every instance; the kernels that do not run cot-tan stages never read them)
-  auto append_ct = [](auto& tw, int Fs, int P, auto cvt) {
-    for (int st = 1; st < mimo::fft_nst(Fs, P); ++st) {
-      const int NS = 1 << mimo::fft_bits_before(Fs, P, st), R = 1 << mimo::fft_bits(Fs, P, st);
-      for (int q = 0; q < mimo::ct_rows(R); ++q)
-        for (int jm = 0; jm < NS; ++jm) {
-          const double a = 2.0 * M_PI * mimo::ct_rev(R, NS, jm, q), c = std::cos(a);
-          tw.push_back(cvt(c, std::sin(a) / c));
-        }
-    }
-  };
-  auto twiddles = [&](int T, auto cvt) {
-    auto tw = twiddles_of(F, T, cvt);
-    tw.resize(std::max(1, mimo::fft_tw_total(F, F / T)));
-    if (F / T >= 2) append_ct(tw, F, F / T, cvt);
-    return tw;
-  };
-  auto to_f32 = [](double c, double s) { return make_float2((float)c, (float)s); };
-  auto to_f64 = [](double c, double s) { return make_double2(c, s); };
-  std::vector<float2> tws[2] = {twiddles(mimo::team_size(F), to_f32), twiddles(mimo::alt_team_size(F), to_f32)};
-  std::vector<double2> tw64 = twiddles(mimo::team_size64(F), to_f64);
-  // split FFT (split_fft.h): the F/2-point sub-transform's table, its cot-tan region, then
-  // the radix-2 stage's (cos a, tan a), a = -2 pi n / F, n < F/2.  At n = F/4 the pair is
-  // (6.1e-17, -1.6e16): c t rounds to sin a, and the product form c (u.x - t u.y) keeps full
-  // precision there (tests/test_fft_split.py, near the quarter turn)
+  // the FFT tables (host_tables.h): the team FFT's per team size, the split FFT's in place of
+  // the fp64 team's where the instance runs it, the wave-split FFT's where used
+  const mimo::TwToF32 to_f32;
+  const mimo::TwToF64 to_f64;
+  std::vector<float2> tws[2] = {mimo::team_twiddles(F, mimo::team_size(F), to_f32),
+                                mimo::team_twiddles(F, mimo::alt_team_size(F), to_f32)};
+  std::vector<double2> tw64 = mimo::team_twiddles(F, mimo::team_size64(F), to_f64);
   if (mimo::split_fft_used(F, mimo::team_size64(F), true)) {
-    const int T = mimo::team_size64(F), P = F / T;
-    tw64 = twiddles_of(F / 2, T / 2, to_f64);
-    tw64.resize(mimo::fft_tw_total(F / 2, P));
-    if (mimo::kSplitCt) append_ct(tw64, F / 2, P, to_f64);
-    for (int n = 0; n < F / 2; ++n) {
-      const double a = -2.0 * M_PI * (double)n / (double)F, c = std::cos(a);
-      tw64.push_back(make_double2(c, std::sin(a) / c));
-    }
+    const int T = mimo::team_size64(F);
+    tw64 = mimo::split_twiddles(F, T);
     if ((int)tw64.size() != mimo::split_fft_tw_total(F, T)) return MIMO_ENOKERNEL;  // table and kernel disagree
   }
-  // wave-split FFT (wave_fft.h): the one-wave sub-transform's stages, then exp(-j 2 pi n / F)
-  auto wave_twiddles = [&](int T, auto cvt) {
-    auto tw = twiddles_of(mimo::wave_fft_fw(F, T), 64, cvt);
-    tw.resize(mimo::wave_fft_tw_inter(F, T));
-    for (int n = 0; n < F; ++n) {
-      const double ang = -2.0 * M_PI * (double)n / (double)F;
-      tw.push_back(cvt(std::cos(ang), std::sin(ang)));
-    }
-    append_ct(tw, mimo::wave_fft_fw(F, T), F / T, cvt);  // the sub-transforms' cot-tan region
-    return tw;
-  };
   std::vector<double2> twave64;
   std::vector<float2> twave32;
-  if (mimo::wave_fft_used(F, mimo::team_size64(F), true)) twave64 = wave_twiddles(mimo::team_size64(F), to_f64);
-  if (mimo::wave_fft_used(F, mimo::team_size(F), false)) twave32 = wave_twiddles(mimo::team_size(F), to_f32);
+  if (mimo::wave_fft_used(F, mimo::team_size64(F), true)) twave64 = mimo::wave_twiddles(F, mimo::team_size64(F), to_f64);
+  if (mimo::wave_fft_used(F, mimo::team_size(F), false)) twave32 = mimo::wave_twiddles(F, mimo::team_size(F), to_f32);
   // in-band sub-carrier k -> bin (modulation.py:266-267)
   std::vector<float> f_rel(S);
   std::vector<double> f_rel64(S), f_over_c(S);
@@ -509,7 +343,7 @@ int ensure_device(mimo_engine* e) {
     HIP_TRY(hipMemcpy(e->d_tab32, t32.data(), sizeof(float2) * n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(e->d_tab64, e->chan_inband.data(), sizeof(double2) * n, hipMemcpyHostToDevice));
   }
-  const std::vector<double2> lut = lut64_table();
+  const std::vector<double2> lut = mimo::lut64_table();
   HIP_TRY(hipMalloc(&e->d_lut64, sizeof(double2) * lut.size()));
   HIP_TRY(hipMemcpy(e->d_lut64, lut.data(), sizeof(double2) * lut.size(), hipMemcpyHostToDevice));
   HIP_TRY(hipMalloc(&e->d_tw64, sizeof(double2) * tw64.size()));

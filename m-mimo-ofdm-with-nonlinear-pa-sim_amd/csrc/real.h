@@ -146,7 +146,8 @@ __device__ __forceinline__ void sincos_rev_lut(double r, double& sn, double& cs)
 // e <= 0, so e ln 2 and ln m have the same sign and need no range fold; bucket i of m
 // (the top 9 mantissa bits, width 2^-10) gives c_i ~ 1 / centre_i (12 bits; c = 1 for the
 // top bucket: t = m - 1 exactly as u -> 1), t = m c_i - 1 with |t| < 2^-10, and
-// log1p(t) to t^6 (truncation < 2^-60 relative).
+// log1p(t) to t^6 (truncation < 2^-60 relative).  <= 1.3 ulp (1.24 measured on the device,
+// tests/test_gpu_probe_math.py).
 // ESC: ln(x 2^ESC) -- the scale enters the exponent only (Box-Muller: x = w0 + 0.5, ESC = -32).
 template <int ESC = 0>
 __device__ __forceinline__ double ln_unit(double x) {
@@ -169,16 +170,27 @@ __device__ __forceinline__ double ln_unit(double x) {
   return fma(de, kLn2Hi, cl.y) + fma(de, kLn2Lo, p);
 }
 // sqrt of a positive normal double by the v_rsq_f64 seed (~2^-25) and one Newton step
-// (~2^-49 relative).
+// (<= 2^-47.5 relative: 2^-47.83 measured on the device, tests/test_gpu_probe_math.py).
 __device__ __forceinline__ double sqrt_n1(double x) {
   const double r = __builtin_amdgcn_rsq(x);
   const double g = x * r, h = 0.5 * r;
   return fma(g, fma(-g, h, 0.5), g);
 }
-// 1/sqrt(x), x > 0 finite: seed and one Newton step (~2^-49 relative).
+// 1/sqrt(x), x > 0 finite: seed and one Newton step (<= 2^-47.5 relative, as sqrt_n1).  The soft
+// limiter used it until its gain was measured (rsq_h1 below); kept for the probe's record.
 __device__ __forceinline__ double rsq_n1(double x) {
   const double y = __builtin_amdgcn_rsq(x);
   return fma(y, fma(-0.5 * x * y, y, 0.5), y);
+}
+// 1/sqrt(x), x > 0 finite, to the rounding level: the seed and one third-order step
+// y (1 + e/2 + 3 e^2 / 8), e = 1 - x y^2 (the seed's 2^-24.4 cubed is below 2^-70; what is
+// left is the rounding of x y inside e, weighted 1/2, and the last FMA's: <= 1 ulp).  One
+// operation more than rsq_n1, whose 2^-47.83 put the soft limiter's gain 18 units of 2^-52 off
+// (tests/test_gpu_probe_math.py).  x = 0: inf, then NaN, as rsq_n1.
+__device__ __forceinline__ double rsq_h1(double x) {
+  const double y = __builtin_amdgcn_rsq(x);
+  const double e = fma(-(x * y), y, 1.0);
+  return fma(y * e, fma(e, 0.375, 0.5), y);
 }
 
 __device__ __forceinline__ float sin_rev(float r) { return __builtin_amdgcn_sinf(r); }

@@ -302,6 +302,9 @@ int32_t mimo_qam_llr(int32_t M, const double* in_iq, int64_t n, const double* no
 }
 
 int32_t mimo_fft(int32_t N, int64_t batch, int32_t inverse, const double* in_iq, double* out_iq) {
+  // checked before anything is allocated (the size below multiplies N and batch)
+  if (N <= 0 || !pow2(N) || N < 2 || N > 8192) return sfail(MIMO_EINVAL, "n_fft must be a power of two in [2, 8192]");
+  if (batch < 0) return sfail(MIMO_EINVAL, "batch must be >= 0");
   DBuf din, dout;
   const size_t bytes = (size_t)N * batch * sizeof(double2);
   S_TRY(din.alloc(bytes));

@@ -283,7 +283,7 @@ struct Dft {
 // of a complex multiply (2 mul + 2 fma) and 4 additions.  The inverse uses conj(z): t -> -t.
 // ROT: the twiddle times rho = DIR j (W_4 of the transform's direction) -- operands swapped,
 // still 6 FMAs.  Exact in the limit c -> 0 as long as c != 0 (the host tables hold
-// cos(pi/2) = 6.1e-17, never 0): c t rounds to s, and the dropped b term is c b ~ 1e-16 b.
+// the stored cos of a quarter turn is -2.5e-20, never 0: host_tables.h): c t rounds to s, and the dropped b term is c b ~ 1e-16 b.
 template <int DIR, bool ROT, class C, typename Re = real_of<C>>
 __device__ __forceinline__ void bfly_ct(C a, C b, C ct, C& o0, C& o1) {
   const Re c = ct.x, tt = DIR < 0 ? ct.y : -ct.y;

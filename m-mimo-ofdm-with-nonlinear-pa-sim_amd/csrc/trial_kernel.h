@@ -261,25 +261,39 @@ __device__ __forceinline__ double alpha_of_gamma2(double g2) {
 // PA on one time-domain sample (distortion.py:9-19, 102-113, 202-211).
 // Soft limiter: min(1, sqrt(sat) rsq(pw)) -- the reference's branch |x|^2 > sat, then
 // x sqrt(sat / |x|^2), up to rounding at |x|^2 = sat (fp64: -0.4 % against the branch).
+// fp64 gains stay within 4 units of 2^-52 of the exact formulas (tests/test_gpu_probe_math.py):
+// the soft limiter's rsq by one third-order step (real.h rsq_h1), the general-hardness Rapp
+// gain with both powers on a base in [1, 2] (below).
 template <class C, typename R = real_of<C>>
 __device__ __forceinline__ C pa_apply(int kind, C x, R sat, R sqrt_sat, R inv_sat, R rapp_p, R toi) {
   const R pw = fmar(x.x, x.x, x.y * x.y);
   R sc = R(1);
   if (kind == PA_SOFTLIM) {
     if constexpr (sizeof(R) == 4) sc = minr(1.0f, sqrt_sat * rsq_r(pw));
-    else sc = fmin(R(1), sqrt_sat * rsq_n1(pw));  // rsq(0) = inf -> NaN -> fmin picks 1
+    else sc = fmin(R(1), sqrt_sat * rsq_h1(pw));  // rsq(0) = inf -> NaN -> fmin picks 1
   } else if (kind == PA_RAPP) {
     // 1 / (1 + (pw/sat)^p)^(1/(2p))
     const R u = pw * inv_sat;
-    const R up = u > R(0) ? exp2_r(rapp_p * log2_r(u)) : R(0);
-    sc = exp2_r(-(R(0.5) / rapp_p) * log2_r(R(1) + up));
+    if constexpr (sizeof(R) == 8) {
+      // fp64 (cold path): exp2(-(1 / 2p) log2(1 + exp2(p log2 u))) loses ~0.5 |log2 u| ulp to
+      // the rounding of p log2 u and of 1 / 2p (8.8 and 11.6 units of 2^-52 at p = 5 and 2.5,
+      // u up to 10^6).  Above u = 1 the gain is u^(-1/2) (1 + u^-p)^(-1/2p) instead, so the
+      // rounded exponent -1 / 2p only ever meets a base in [1, 2].
+      const bool big = u > R(1);
+      const R v = u > R(0) ? pow(u, big ? -rapp_p : rapp_p) : R(0);
+      const R g = pow(R(1) + v, -(R(0.5) / rapp_p));
+      sc = big ? g / __builtin_sqrt(u) : g;
+    } else {
+      const R up = u > R(0) ? exp2_r(rapp_p * log2_r(u)) : R(0);
+      sc = exp2_r(-(R(0.5) / rapp_p) * log2_r(R(1) + up));
+    }
   } else if (kind == PA_TOI) {
     sc = R(1) - toi * pw;
   }
   return mkc(x.x * sc, x.y * sc);
 }
 
-// Cold path out of line: the general-hardness Rapp gain (library log2 / exp2).  Inlined,
+// Cold path out of line: the general-hardness Rapp gain (library pow).  Inlined,
 // its f64 constants were hoisted into the loop preheader and spilled to scratch once per
 // trial (~90 KB of writes per trial at config 2, profiles/r03/pmc); out of line they stay
 // in the call.  Measured with the exact-alpha fallback (now alpha_fit.h's segment table,
@@ -709,6 +723,35 @@ struct Channel {
 };
 
 // ---------------------------------------------------------------- the kernel
+// The instance's FFT.  fp64 up to F 2048 on two or more waves: the wave-split FFT (wave_fft.h).
+// fp64 F 8192: two 4096-point sub-transforms and a radix-2 stage through lane-half swaps
+// (split_fft.h: two LDS exchanges per transform instead of three).  Else the team FFT; fp64 up
+// to F 4096 its twiddled stages absorb their twiddles into FMAs (team_fft.h dft8_ct / dft16_ct).
+template <typename R, int F, int T, int NBUF>
+using trial_fft_t = std::conditional_t<
+    wave_fft_used(F, T, sizeof(R) == 8), WaveFft<F, T, R, true, true>,
+    std::conditional_t<split_fft_used(F, T, sizeof(R) == 8), SplitFft<F, T, NBUF, R>,
+                       TeamFft<F, T, NBUF, R, false, false, false, sizeof(R) == 8 && F <= 4096>>>;
+
+// Box-Muller tables (real.h ln_unit / sincos_lut) into LDS, by the whole team; the caller
+// barriers before the first read.  p: the kernel parameters, or anything with their `lut`
+// (a pointer, not a reference: the table pointer is then loaded where the kernel always
+// loaded it, under the loop guard.  The float32 instances' instruction streams are what they
+// were before the loop became a function; the float64 ones keep their instruction mix but
+// differ in register names, instruction order and the form of a few loop guards, since the
+// inlined loop's block lands before the code that follows it).
+template <int T, class PP>
+__device__ __forceinline__ void fill_lut64(const PP* p, int t) {
+  for (int i = t; i < kLut64; i += T) lut64[i] = p->lut[i];
+}
+// The wave-split sub-transform's LDS twiddle copy (stage 1's block and stage 2's rows, or the
+// cot-tan constants; team_fft.h twl_src) from the instance's table; same barrier.  (The
+// thread id read here, not passed in: its range keeps the index arithmetic unsigned.)
+template <class FFT, int T, class C>
+__device__ __forceinline__ void fill_tw1(C* tw1_s, const C* twsrc) {
+  for (int i = threadIdx.x; i < FFT::TWL_N; i += T) tw1_s[i] = twsrc[FFT::twl_src(i)];
+}
+
 // Occupancy tuning per instance (trial_inst.hip): MINW = waves/SIMD the register
 // allocation targets, NBUF = FFT exchange buffers (2: one barrier per exchange, 1: half
 // the LDS), SYMW_LDS = keep the pre-weighted symbols in LDS (thread-private) instead of
@@ -740,10 +783,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
   // fp64 F 8192: two 4096-point sub-transforms and a radix-2 stage through lane-half swaps
   // (split_fft.h: two LDS exchanges per transform instead of three)
   constexpr bool SPLITFFT = split_fft_used(F, T, sizeof(R) == 8);
-  using FFT = std::conditional_t<
-      WAVEFFT, WaveFft<F, T, R, true, true>,
-      std::conditional_t<SPLITFFT, SplitFft<F, T, NBUF, R>,
-                         TeamFft<F, T, NBUF, R, false, false, false, sizeof(R) == 8 && F <= 4096>>>;
+  using FFT = trial_fft_t<R, F, T, NBUF>;
   using SL = Slots<F, T, NSLOT, ALIGNED>;
   // F 4096: the SALU Philox rounds with CSI only -- CSI -2.4 %, perfect CSI +1.1 / +2.0 %
   // (paper / paper CNC 0-8, profiles/r06/k4096/; r03 measured +1.7 % for the perfect-CSI line)
@@ -807,13 +847,8 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
   const uint32_t ch_trial = p0.chan_period ? trial % p0.chan_period : trial;
   const int S = p.n_sc, A = p.n_ant, L = p.qam_l, hb = p.half_bits;
   const R inv_sqrt_f = p.inv_sqrt_f;
-  if constexpr (sizeof(R) == 8) {  // Box-Muller tables (real.h ln_unit / sincos_lut) into LDS
-    for (int i = t; i < kLut64; i += T) lut64[i] = p.lut[i];
-  }
-  if constexpr (LTW1) {  // the sub-transform's stage-1 block and stage-2 rows (team_fft.h twl_src)
-    const C* twsrc = WAVEFFT ? p.tw_wave : p.tw;
-    for (int i = t; i < TW1_N; i += T) tw1_s[i] = twsrc[FFT::twl_src(i)];
-  }
+  if constexpr (sizeof(R) == 8) fill_lut64<T>(&p, t);
+  if constexpr (LTW1) fill_tw1<FFT, T>(tw1_s, WAVEFFT ? p.tw_wave : p.tw);
   if constexpr (sizeof(R) == 8 || LTW1) __syncthreads();
 
   // RX position for LoS / two-path (mp_model.py:190-201; y uses rx_loc_x, a reference quirk)

@@ -199,3 +199,15 @@ def test_stale_library_reports_its_abi(tmp_path, monkeypatch):
     monkeypatch.setattr(_engine, "LIB_PATH", str(so))
     with pytest.raises(_engine.EngineError, match="is ABI 6, this module ABI 8: rebuild it"):
         _engine.lib()
+
+
+@pytest.mark.parametrize("n_fft,batch,msg", [(0, 1, "n_fft"), (-8, 1, "n_fft"), (3, 1, "n_fft"), (16384, 1, "n_fft"),
+                                             (64, -1, "batch")])
+def test_fft_validates_sizes_before_any_allocation(n_fft, batch, msg):
+    """mimo_fft: n_fft <= 0, not a power of two or beyond 8192, and batch < 0 are MIMO_EINVAL,
+    decided before the device buffers (whose size multiplies the two) are allocated: host only."""
+    lib = _engine.lib()
+    buf = np.zeros(4)
+    dp = ctypes.POINTER(ctypes.c_double)
+    assert lib.mimo_fft(n_fft, batch, 0, buf.ctypes.data_as(dp), buf.ctypes.data_as(dp)) == -1  # MIMO_EINVAL
+    assert msg in lib.mimo_last_error().decode()

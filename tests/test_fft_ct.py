@@ -94,7 +94,9 @@ def test_absorbed_twiddle_dft_equals_twiddle_then_dft(R, DIR, ns):
 
 
 def test_cot_tan_constants_stay_finite_at_quarter_turns():
-    """cos of a quarter turn is 6.1e-17 in double, never 0: tan is ~1.6e16, finite, and
+    """(NumPy's double constants, as the tables were first built; the production tables are
+    formed in long double since, csrc/host_tables.h, where the pair is (-2.5e-20, 4e19) and
+    tests/test_probe_tables.py checks it.)  cos of a quarter turn is 6.1e-17 in double, never 0: tan is ~1.6e16, finite, and
     c * tan rounds back to sin (what bfly_ct relies on)."""
     for rev in (-0.25, 0.25, -0.75, -0.5 + 0.25):
         c, t = ct_const(rev)

@@ -155,7 +155,9 @@ def test_round_trip_with_pointwise_step(clip):
 
 
 def test_r2_twiddle_product_form_near_quarter_turn():
-    """The (cos a, tan a) form at a = -pi/2 (n = F/4: cos 6.1e-17, tan -1.6e16) and its
+    """(NumPy's double constants; the production table, formed in long double, holds
+    (-2.5e-20, 4e19) there: csrc/host_tables.h, tests/test_probe_tables.py.)
+    The (cos a, tan a) form at a = -pi/2 (n = F/4: cos 6.1e-17, tan -1.6e16) and its
     neighbours: c (u.x - t u.y) + j c (u.y + t u.x) equals e^{ja} u to a few ulp of |u|, in
     both directions -- c t rounds to sin a, so the large tangent loses nothing."""
     c, t = r2_table()

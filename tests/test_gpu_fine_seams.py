@@ -174,3 +174,34 @@ def test_cnc_receive_corrected_symbols(units):
     # and the bits path still agrees with the reference's fixture
     for i, b in enumerate(rx.receive(n_iters_lst=iters, in_sig_fd=units["cnc_in"])):
         np.testing.assert_array_equal(b, units["cnc_bits"][i])
+
+
+@pytest.mark.parametrize("N", [2, 4, 64, 128, 1024, 4096, 8192])
+@pytest.mark.parametrize("inverse", [False, True])
+@pytest.mark.parametrize("batch", [1, 3])
+def test_stage_fft_against_long_double(N, inverse, batch):
+    """mimo_fft (stages.hip k_fft_rows, the transform behind utilities.to_freq/time_domain and
+    the object API's modem) against the long-double DFT with the ortho scaling, full-band
+    normals and (batch 3) a one-hot last row; N = 4096 and 8192 (64 and 128 KiB of dynamic LDS) included.
+    Bound: 16 x the error of np.fft (norm="ortho") against the same reference at the same
+    input -- the kernel is a plain radix-2 with sincospi twiddles (tests/test_gpu_probe_fft.py
+    has the reasoning for the factor)."""
+    import _engine
+    import probe_util as pu
+    rng = np.random.default_rng(N + 2 * batch + int(inverse))
+    x = (rng.standard_normal((batch, N)) + 1j * rng.standard_normal((batch, N))) * np.sqrt(0.5)
+    if batch > 1:  # one bin alone, at the quarter turn
+        x[-1] = 0
+        x[-1, N // 4 if N >= 4 else 1] = 0.75 - 1.25j
+    ref = pu.ld_fft(x, +1 if inverse else -1) / np.sqrt(pu.LD(N))
+    y_np = np.fft.ifft(x, axis=-1, norm="ortho") if inverse else np.fft.fft(x, axis=-1, norm="ortho")
+    # NumPy's error at this input: its worst row (the one-bin row alone can come out exact)
+    e_np = tuple(np.full(batch, e.max()) for e in pu.errors(y_np, ref))
+    assert e_np[0][0] > 0
+    got = _engine.fft(x, inverse=inverse)
+    assert got.shape == x.shape
+    l2, mx = pu.errors(got, ref)
+    print(f"PROBE_SEAM|mimo_fft|N={N}|inverse={int(inverse)}|batch={batch}|l2={l2.max():.3e}|e_np_l2={e_np[0].max():.3e}"
+          f"|ratio_l2={np.max(l2 / e_np[0]):.2f}|ratio_mx={np.max(mx / e_np[1]):.2f}")
+    assert np.all(l2 <= 16 * e_np[0]), (l2, e_np[0])
+    assert np.all(mx <= 16 * e_np[1]), (mx, e_np[1])
