@@ -9,6 +9,7 @@
  *     mimo_engine_create        <- Link.__init__                       mp_model.py:32-87
  *     mimo_engine_set_point     <- Link.update_distortion / set_snr    mp_model.py:230-251
  *     mimo_engine_run           <- Link.simulate (trial loop)          mp_model.py:89-228
+ *     mimo_engine_measure_points   the same trials with signal / distortion power sums (SDR, EVM)
  *     mimo_engine_run_points    <- the drivers' grid loops over (IBO, Eb/N0), one launch
  *                                  for many points   main_mp_miso_cnc_constant_ber_req_ebn0_vs_ibo.py:100-215
  *   fine seams (float64 stage kernels, caller-owned host arrays)
@@ -135,6 +136,26 @@ int32_t mimo_engine_run_points(mimo_engine* e, int32_t n_points, const mimo_poin
                                const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters,
                                int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
                                uint32_t* per_trial);
+/* Measure mode (float64 engines): the trials, arguments, launch splitting and point rules of
+ * mimo_engine_run_points and the same counts, plus per point a row of
+ * n_meas = MIMO_MEAS_FIXED + n_idx power sums over the S data sub-carriers k of every trial:
+ *   [0] Es  = sum |s_k|^2               s: the transmitted constellation point
+ *   [1] Ez0 = sum |z0_k|^2              z0 = r / g: the AGC'd received value without noise
+ *   [2], [3] Re, Im of C = sum z0_k conj(s_k)
+ *   [4] Ed0 = sum |z0_k - s_k|^2
+ *   [5 + i] Ee_i = sum |v_{i,k} - s_k|^2   v_i: the slicer input of counter index i (counts
+ *                                       layout: the clean run's z_c, an iteration's z - dist)
+ * from which gain C / Es, SDR |C|^2 / (Es Ez0 - |C|^2), slicer SDR Es / Ed0 and per-iteration
+ * SNDR Es / Ee_i follow.  meas_out: [n_points][n_meas] totals (ADDED to; summed in a fixed
+ * order: equal calls return equal bits).  per_trial_meas: optional [sum n_trials][n_meas]
+ * rows in point order, NULL to skip.  A float32 engine or a null meas_out is MIMO_EINVAL,
+ * before any HIP call.  (Added within ABI 8: a library without it is reported by name.) */
+enum { MIMO_MEAS_FIXED = 5 };
+int32_t mimo_measure_width(int32_t n_iters, int32_t incl_clean); /* MIMO_MEAS_FIXED + n_idx; host only */
+int32_t mimo_engine_measure_points(mimo_engine* e, int32_t n_points, const mimo_point* points, const uint64_t* seeds,
+                                   const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters,
+                                   int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
+                                   uint32_t* per_trial, double* meas_out, double* per_trial_meas);
 /* Device time of the trial kernels of the last run, in ms (HIP events on the engine stream). */
 double mimo_engine_last_kernel_ms(const mimo_engine* e);
 /* Which kernel instance the current config selects: "F=2048 T=128 slots=8 aligned ..." */

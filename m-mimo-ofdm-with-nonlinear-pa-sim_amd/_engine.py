@@ -63,6 +63,10 @@ SYMBOLS = {
     "mimo_engine_run_points": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(MimoPoint), _u64p,
                                                 _u64p, _u64p, _i32p, ctypes.c_int32, ctypes.c_int32, _u64p, _u64p,
                                                 _u32p]),
+    "mimo_measure_width": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32]),
+    "mimo_engine_measure_points": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(MimoPoint), _u64p,
+                                                    _u64p, _u64p, _i32p, ctypes.c_int32, ctypes.c_int32, _u64p, _u64p,
+                                                    _u32p, _dp, _dp]),
     "mimo_engine_last_kernel_ms": (ctypes.c_double, [ctypes.c_void_p]),
     "mimo_engine_describe": (ctypes.c_char_p, [ctypes.c_void_p]),
     "mimo_engine_destroy": (None, [ctypes.c_void_p]),
@@ -95,6 +99,7 @@ class EngineError(RuntimeError):
 
 
 ABI_VERSION = 8  # include/mimo_engine.h MIMO_ABI_VERSION
+MEAS_FIXED = 5   # include/mimo_engine.h MIMO_MEAS_FIXED
 
 
 def lib():
@@ -140,6 +145,85 @@ def as_iq(x):
     """complex array -> contiguous float64 (re, im) view."""
     x = np.ascontiguousarray(np.asarray(x, dtype=np.complex128))
     return x.view(np.float64)
+
+
+def _ratio_db(num, den):
+    """10 log10(num / den) elementwise; a zero denominator gives inf (no warning, no NaN)."""
+    num = np.asarray(num, np.float64)
+    den = np.asarray(den, np.float64)
+    out = np.full(np.broadcast(num, den).shape, np.inf)
+    ok = (den > 0) & (num > 0)
+    np.divide(num, den, out=out, where=ok)
+    np.log10(out, out=out, where=ok)
+    np.multiply(out, 10.0, out=out, where=ok)
+    out[np.broadcast_to((num <= 0) & (den > 0), out.shape)] = -np.inf
+    return out if out.ndim else float(out)
+
+
+class SignalStats:
+    """Signal / distortion powers of a measure call (mimo_engine_measure_points): one row
+    ``[Es, Ez0, Re C, Im C, Ed0, Ee_0 ...]`` of sums over trials and data sub-carriers, with the
+    bit-error totals of the same trials.  ``a + b`` pools two measurements (sums add)."""
+
+    def __init__(self, row, err=None, bits=None):
+        self.row = np.array(row, np.float64).reshape(-1)
+        if self.row.size < MEAS_FIXED + 1:
+            raise ValueError(f"a measure row has at least {MEAS_FIXED + 1} entries")
+        n_idx = self.row.size - MEAS_FIXED
+        self.err = np.zeros(n_idx, np.uint64) if err is None else np.array(err, np.uint64).reshape(-1)
+        self.bits = np.zeros(n_idx, np.uint64) if bits is None else np.array(bits, np.uint64).reshape(-1)
+        if self.err.size != n_idx or self.bits.size != n_idx:
+            raise ValueError("err and bits must have one entry per counter index of the row")
+
+    @classmethod
+    def from_totals(cls, es, ez0, c, ed0, ee, err=None, bits=None):
+        c = complex(c)
+        return cls(np.concatenate([[es, ez0, c.real, c.imag, ed0], np.atleast_1d(np.asarray(ee, np.float64))]),
+                   err, bits)
+
+    es = property(lambda self: float(self.row[0]))
+    ez0 = property(lambda self: float(self.row[1]))
+    c = property(lambda self: complex(self.row[2], self.row[3]))
+    ed0 = property(lambda self: float(self.row[4]))
+    ee = property(lambda self: self.row[MEAS_FIXED:].copy())
+
+    @property
+    def gain(self):
+        """beta = C / Es: the least-squares (Bussgang) gain of the noiseless received signal."""
+        return self.c / self.es if self.es > 0 else complex(np.inf)
+
+    @property
+    def sdr_db(self):
+        """|C|^2 / (Es Ez0 - |C|^2): signal power over the power uncorrelated with it."""
+        c2 = abs(self.c) ** 2
+        return _ratio_db(c2, self.es * self.ez0 - c2)
+
+    @property
+    def slicer_sdr_db(self):
+        """Es / Ed0: what the fixed AGC leaves at the slicer, without noise."""
+        return _ratio_db(self.es, self.ed0)
+
+    @property
+    def sndr_db(self):
+        """Es / Ee_i per counter index: noise plus residual distortion at the slicer."""
+        return _ratio_db(self.es, self.row[MEAS_FIXED:])
+
+    @property
+    def ber(self):
+        out = np.zeros(self.err.size)
+        np.divide(self.err.astype(np.float64), self.bits.astype(np.float64), out=out, where=self.bits > 0)
+        return out
+
+    def __add__(self, other):
+        if not isinstance(other, SignalStats):
+            return NotImplemented
+        if other.row.size != self.row.size:
+            raise ValueError("measurements with different counter layouts cannot be pooled")
+        return SignalStats(self.row + other.row, self.err + other.err, self.bits + other.bits)
+
+    def __repr__(self):
+        return (f"SignalStats(sdr_db={self.sdr_db:.3f}, slicer_sdr_db={self.slicer_sdr_db:.3f}, "
+                f"sndr_db={np.array2string(self.sndr_db, precision=3)})")
 
 
 class Engine:
@@ -191,6 +275,7 @@ class Engine:
     def set_point(self, ibo_db, snr_db, avg_symbol_power, pa_kind, **kw):
         pt = self.make_point(ibo_db, snr_db, avg_symbol_power, pa_kind, **kw)
         _check(self._L.mimo_engine_set_point(self._h, ctypes.byref(pt)))
+        self._point = pt  # the one-point measure() runs it
 
     def run_points(self, points, seeds, first_trials, n_trials, iters, incl_clean=False, per_trial=False):
         """Many grid points in as few launches as possible (mimo_engine_run_points).
@@ -229,6 +314,46 @@ class Engine:
                                      _ptr(err, ctypes.c_uint64), _ptr(bits, ctypes.c_uint64),
                                      _ptr(pt, ctypes.c_uint32) if pt is not None else None))
         return err, bits, pt
+
+    def measure_points(self, points, seeds, first_trials, n_trials, iters, incl_clean=False, per_trial=False):
+        """run_points in measure mode (mimo_engine_measure_points; float64 engines): the same
+        trials and counts, and per point the row of signal / distortion power sums.
+        -> (err[P, n_idx], bits[P, n_idx], meas[P, n_meas], per-trial counts [sum n_trials, n_idx]
+        or None, per-trial rows [sum n_trials, n_meas] or None); SignalStats(meas[i], err[i], bits[i])."""
+        P = len(points)
+        arr = (MimoPoint * max(1, P))()
+        for i, pt in enumerate(points):
+            arr[i] = pt if isinstance(pt, MimoPoint) else self.make_point(**pt)
+        it = _c(sorted(set(int(i) for i in iters)), np.int32)
+        n_idx = len(it) + (1 if incl_clean else 0)
+        n_meas = MEAS_FIXED + n_idx
+        sd = _c(np.asarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], dtype=np.uint64).reshape(-1), np.uint64)
+        ft = _c(np.asarray(first_trials, dtype=np.uint64).reshape(-1), np.uint64)
+        nt = _c(np.asarray(n_trials, dtype=np.uint64).reshape(-1), np.uint64)
+        if not (len(sd) == len(ft) == len(nt) == P):
+            raise ValueError("points, seeds, first_trials and n_trials must have the same length")
+        err = np.zeros((P, n_idx), np.uint64)
+        bits = np.zeros((P, n_idx), np.uint64)
+        meas = np.zeros((P, n_meas), np.float64)
+        pt = np.zeros((int(nt.sum()), n_idx), np.uint32) if per_trial else None
+        pm = np.zeros((int(nt.sum()), n_meas), np.float64) if per_trial else None
+        _check(self._L.mimo_engine_measure_points(
+            self._h, P, arr, _ptr(sd, ctypes.c_uint64), _ptr(ft, ctypes.c_uint64), _ptr(nt, ctypes.c_uint64),
+            _ptr(it, ctypes.c_int32), len(it), int(bool(incl_clean)), _ptr(err, ctypes.c_uint64),
+            _ptr(bits, ctypes.c_uint64), _ptr(pt, ctypes.c_uint32) if pt is not None else None,
+            _ptr(meas, ctypes.c_double), _ptr(pm, ctypes.c_double) if pm is not None else None))
+        return err, bits, meas, pt, pm
+
+    def measure(self, seed, first_trial, n_trials, iters, incl_clean=False, per_trial=False, point=None):
+        """One point (the last set_point's, or ``point``: make_point keywords / MimoPoint).
+        -> (err[n_idx], bits[n_idx], meas[n_meas], per-trial counts or None, per-trial rows or None)."""
+        if point is None:
+            point = getattr(self, "_point", None)
+            if point is None:
+                raise EngineError("mimo_engine_set_point was not called")
+        err, bits, meas, pt, pm = self.measure_points([point], [seed], [first_trial], [n_trials], iters, incl_clean,
+                                                      per_trial)
+        return err[0], bits[0], meas[0], pt, pm
 
     @property
     def kernel_ms(self):

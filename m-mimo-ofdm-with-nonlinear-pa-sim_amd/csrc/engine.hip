@@ -57,6 +57,32 @@ __global__ void reduce_counts(const uint32_t* __restrict__ c, const uint32_t* __
   if ((threadIdx.x & 63) == 0) atomicAdd(&tot[(size_t)point_of[k] * n_idx + idx], acc);
 }
 
+// Per-slice sums of the measure instances' per-trial rows (doubles: the order matters, so it is
+// fixed).  Block (k, col) sums column col over trial blocks [first[k], first[k + 1]): each thread
+// its strided partial in trial order, a fixed shuffle tree per wave, the wave sums in wave order;
+// one partial per (slice, column) into part[k][col], no atomics.  The host adds the slice
+// partials of a point in slice order, so equal calls give bit-identical totals.
+constexpr int kReduceMeasThreads = 256;
+__global__ __launch_bounds__(kReduceMeasThreads) void reduce_meas(const double* __restrict__ rows,
+                                                                  const uint32_t* __restrict__ first, int n_meas,
+                                                                  double* __restrict__ part) {
+  __shared__ double wsum[kReduceMeasThreads / 64];
+  const int k = blockIdx.x, col = blockIdx.y;
+  double acc = 0.0;
+  for (uint32_t t = first[k] + threadIdx.x; t < first[k + 1]; t += kReduceMeasThreads)
+    acc += rows[(size_t)t * n_meas + col];
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = wsum[0];
+#pragma unroll
+    for (int w = 1; w < kReduceMeasThreads / 64; ++w) s += wsum[w];
+    part[(size_t)k * n_meas + col] = s;
+  }
+}
+
 }  // namespace
 
 namespace mimo {
@@ -91,6 +117,11 @@ struct mimo_engine {
   size_t counts_cap = 0;
   unsigned long long* d_tot = nullptr;    // [points][n_idx] totals of one run
   size_t tot_cap = 0;
+  // measure calls (mimo_engine_measure_points): per-trial rows of one launch, per-slice partials
+  double* d_meas = nullptr;               // [launch blocks][n_meas]
+  size_t meas_cap = 0;
+  double* d_mpart = nullptr;              // [launch slices][n_meas]
+  size_t mpart_cap = 0;
   // per-launch tables in one device blob, filled by one copy from a pinned host buffer:
   // TrialParams<R>[segments] | uint32 block offsets [segments + 1] |
   // uint32 reduction-slice starts [slices + 1] (<= kSlice trials, one point each) | int32 point of slice [slices]
@@ -175,6 +206,25 @@ hipError_t launch(const mimo::InstanceKey& k, dim3 grid, hipStream_t st, const m
   }
 #endif
 #undef MIMO_LAUNCH_F
+}
+
+// The measure instance of the key (float64 only); rows: [grid.x][n_meas] doubles.
+hipError_t launch_meas(const mimo::InstanceKey& k, dim3 grid, hipStream_t st, const mimo::TrialParams<double>& p,
+                       double* rows, bool* found) {
+  *found = false;
+#ifndef MIMO_ONLY_F  // the single-size diagnostic builds link no measure instances
+  switch (k.F) {
+    case 128: return mimo::launch_trial_F128_f64_meas(k, grid, st, p, found, nullptr, rows);
+    case 256: return mimo::launch_trial_F256_f64_meas(k, grid, st, p, found, nullptr, rows);
+    case 512: return mimo::launch_trial_F512_f64_meas(k, grid, st, p, found, nullptr, rows);
+    case 1024: return mimo::launch_trial_F1024_f64_meas(k, grid, st, p, found, nullptr, rows);
+    case 2048: return mimo::launch_trial_F2048_f64_meas(k, grid, st, p, found, nullptr, rows);
+    case 4096: return mimo::launch_trial_F4096_f64_meas(k, grid, st, p, found, nullptr, rows);
+    case 8192: return mimo::launch_trial_F8192_f64_meas(k, grid, st, p, found, nullptr, rows);
+    default: break;
+  }
+#endif
+  return hipSuccess;
 }
 
 int validate_config(const mimo_config* c) {
@@ -430,9 +480,13 @@ namespace {
 // Runs n_points grid points of one system in as few launches as possible: every point's
 // trials become a contiguous range of blocks of one launch (split across launches only
 // beyond kChunk blocks), and a segmented reduction sums each point's counts.
+// meas_out != null (mimo_engine_measure_points): the measure instance runs instead, and its
+// per-trial rows of n_meas = MIMO_MEAS_FIXED + n_idx sums are reduced per slice on the device
+// (reduce_meas) and per point, in slice order, here.
 int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64_t* seeds,
                const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters, int32_t n_iters,
-               int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out, uint32_t* per_trial) {
+               int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out, uint32_t* per_trial,
+               double* meas_out = nullptr, double* per_trial_meas = nullptr) {
   if (n_points < 0) return fail(MIMO_EINVAL, "n_points must be >= 0");
   if (n_iters < 1 || !iters) return fail(MIMO_EINVAL, "at least one iteration index is required");
   uint32_t rec_mask = 0;
@@ -447,6 +501,7 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
   if (n_points == 0) return MIMO_OK;
   if (!pts || !seeds || !first_trial || !n_trials) return fail(MIMO_EINVAL, "null point arrays");
   const int n_idx = n_iters + (incl_clean ? 1 : 0);
+  const int n_meas = MIMO_MEAS_FIXED + n_idx;
   const mimo_config& c = e->cfg;
   const bool csi = pts[0].csi_eps >= 0;
   for (int i = 0; i < n_points; ++i) {
@@ -514,6 +569,27 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
   }
   size_t max_seg = 0;
   for (auto& l : launches) max_seg = std::max(max_seg, l.size());
+  // measure calls: the slice partials of every launch, in launch and slice order, and their points
+  std::vector<double> mpart;
+  std::vector<int> mpart_point;
+  if (meas_out) {
+    size_t max_blocks = 0, max_sl = 0, tot_sl = 0;
+    for (auto& l : launches) {
+      size_t nb = 0, nsl = 0;
+      for (auto& sg : l) {
+        nb += (size_t)sg.n;
+        nsl += (size_t)((sg.n + kSlice - 1) / kSlice);
+      }
+      max_blocks = std::max(max_blocks, nb);
+      max_sl = std::max(max_sl, nsl);
+      tot_sl += nsl;
+    }
+    if (int rc = ensure_cap(e->d_meas, e->meas_cap, std::max<size_t>(1, max_blocks * n_meas))) return rc;
+    if (int rc = ensure_cap(e->d_mpart, e->mpart_cap, std::max<size_t>(1, max_sl * n_meas))) return rc;
+    mpart.resize(tot_sl * n_meas);
+    mpart_point.reserve(tot_sl);
+  }
+  size_t mpart_done = 0;
   if (int rc = ensure_cap(e->d_counts, e->counts_cap, (size_t)(1ull << 20) * n_idx)) return rc;
   if (int rc = ensure_cap(e->d_tot, e->tot_cap, (size_t)n_points * n_idx)) return rc;
   const size_t max_slices = max_seg + (size_t)(kChunk / kSlice) + 1;
@@ -610,7 +686,13 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
       HIP_TRY(hipMemcpyAsync(e->d_blob, e->h_blob, o_pof + nsl * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
       HIP_TRY(hipEventRecord(e->ev0, e->stream));
       bool found = false;
-      hipError_t le = launch(key, dim3(nb), e->stream, kp, &found);
+      hipError_t le = hipSuccess;
+      if constexpr (F64) {
+        le = meas_out ? launch_meas(key, dim3(nb), e->stream, kp, e->d_meas, &found)
+                      : launch(key, dim3(nb), e->stream, kp, &found);
+      } else {
+        le = launch(key, dim3(nb), e->stream, kp, &found);
+      }
       if (!found) return fail(MIMO_ENOKERNEL, std::string("no kernel instance for ") + buf);
       if (le != hipSuccess) return fail(MIMO_EHIP, std::string("trial kernel launch: ") + hipGetErrorString(le));
       HIP_TRY(hipEventRecord(e->ev1, e->stream));
@@ -621,6 +703,18 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
       if (per_trial)
         HIP_TRY(hipMemcpyAsync(per_trial + rows_done * n_idx, e->d_counts, (size_t)nb * n_idx * sizeof(uint32_t),
                                hipMemcpyDeviceToHost, e->stream));
+      if (meas_out) {
+        hipLaunchKernelGGL(reduce_meas, dim3((unsigned)nsl, n_meas), dim3(kReduceMeasThreads), 0, e->stream, e->d_meas,
+                           reinterpret_cast<const uint32_t*>(e->d_blob + o_slice), n_meas, e->d_mpart);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(mpart.data() + mpart_done * n_meas, e->d_mpart, nsl * n_meas * sizeof(double),
+                               hipMemcpyDeviceToHost, e->stream));
+        for (size_t i = 0; i < nsl; ++i) mpart_point.push_back(point_of[i]);
+        mpart_done += nsl;
+        if (per_trial_meas)
+          HIP_TRY(hipMemcpyAsync(per_trial_meas + rows_done * n_meas, e->d_meas, (size_t)nb * n_meas * sizeof(double),
+                                 hipMemcpyDeviceToHost, e->stream));
+      }
       rows_done += nb;
       // the host tables of the next launch are rewritten: wait for this one's copies
       HIP_TRY(hipEventSynchronize(e->ev1));
@@ -641,6 +735,14 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
       err_out[(size_t)i * n_idx + j] += tot[(size_t)i * n_idx + j];
       bits_out[(size_t)i * n_idx + j] += bits_per_trial * n_trials[i];
     }
+  if (meas_out) {
+    // per point, its slice partials in slice order (a fixed order: equal calls, equal bits),
+    // then one add into the caller's row
+    std::vector<double> ptot((size_t)n_points * n_meas, 0.0);
+    for (size_t k = 0; k < mpart_point.size(); ++k)
+      for (int j = 0; j < n_meas; ++j) ptot[(size_t)mpart_point[k] * n_meas + j] += mpart[k * n_meas + j];
+    for (size_t i = 0; i < ptot.size(); ++i) meas_out[i] += ptot[i];
+  }
   e->last_ms = ms_total;
   return MIMO_OK;
 }
@@ -668,6 +770,23 @@ int32_t mimo_engine_run_points(mimo_engine* e, int32_t n_points, const mimo_poin
   if (!e) return fail(MIMO_EINVAL, "null engine");
   return run_points(e, n_points, points, seeds, first_trial, n_trials, iters, n_iters, incl_clean, err_out, bits_out,
                     per_trial);
+}
+
+int32_t mimo_measure_width(int32_t n_iters, int32_t incl_clean) {
+  if (n_iters < 1 || n_iters > 32) return fail(MIMO_EINVAL, "n_iters must be in [1, 32]");
+  return MIMO_MEAS_FIXED + n_iters + (incl_clean ? 1 : 0);
+}
+
+int32_t mimo_engine_measure_points(mimo_engine* e, int32_t n_points, const mimo_point* points, const uint64_t* seeds,
+                                   const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters,
+                                   int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
+                                   uint32_t* per_trial, double* meas_out, double* per_trial_meas) {
+  if (!e) return fail(MIMO_EINVAL, "null engine");
+  if (e->cfg.precision != MIMO_PREC_F64)
+    return fail(MIMO_EINVAL, "measure needs a float64 engine (no float32 measure instances are built)");
+  if (!meas_out) return fail(MIMO_EINVAL, "null meas_out");
+  return run_points(e, n_points, points, seeds, first_trial, n_trials, iters, n_iters, incl_clean, err_out, bits_out,
+                    per_trial, meas_out, per_trial_meas);
 }
 
 double mimo_engine_last_kernel_ms(const mimo_engine* e) { return e ? e->last_ms : 0.0; }
@@ -704,6 +823,8 @@ void mimo_engine_destroy(mimo_engine* e) {
     (void)hipFree(e->d_tx_pos);
     if (e->d_tot) (void)hipFree(e->d_tot);
     if (e->d_counts) (void)hipFree(e->d_counts);
+    if (e->d_meas) (void)hipFree(e->d_meas);
+    if (e->d_mpart) (void)hipFree(e->d_mpart);
     if (e->d_blob) (void)hipFree(e->d_blob);
     if (e->h_blob) (void)hipHostFree(e->h_blob);
     (void)hipEventDestroy(e->ev0);

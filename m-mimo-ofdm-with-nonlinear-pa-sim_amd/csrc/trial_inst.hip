@@ -1,8 +1,7 @@
 // Instantiates the fused trial kernel for one FFT size and arithmetic type
-// (compiled once per -DINST_F=<size> -DINST_F64=<0|1>).
+// (compiled once per -DINST_F=<size> -DINST_F64=<0|1>), and once more per size with
+// -DINST_F64=1 -DINST_MEAS=1 for the measure instances (trial_kernel.h MIMO_MEAS_INST).
 #include <type_traits>
-
-#include "trial_launch.h"
 
 #ifndef INST_F
 #error "compile with -DINST_F=<fft size>"
@@ -10,6 +9,15 @@
 #ifndef INST_F64
 #define INST_F64 0
 #endif
+#ifndef INST_MEAS
+#define INST_MEAS 0
+#endif
+#if INST_MEAS && !INST_F64
+#error "measure instances are float64 only"
+#endif
+#define MIMO_MEAS_INST INST_MEAS
+
+#include "trial_launch.h"
 
 #define MIMO_CAT2(a, b) a##b
 #define MIMO_CAT(a, b) MIMO_CAT2(a, b)
@@ -51,34 +59,44 @@ constexpr Profile profile_for(int T, bool aligned, int ch) {
 }
 
 // attr != null: no launch, the instance's attributes instead (its static LDS, which the
-// engine checks with the CSI table's dynamic LDS against the device limit before a launch)
+// engine checks with the CSI table's dynamic LDS against the device limit before a launch).
+// meas: the measure instances' per-trial rows [grid.x][kMeasFixed + n_idx] (unused otherwise).
 template <int T, int NSLOT, bool AL, int CH, bool CSI>
-hipError_t go(dim3 grid, hipStream_t st, const TrialParams<Real>& p, hipFuncAttributes* attr) {
+hipError_t go(dim3 grid, hipStream_t st, const TrialParams<Real>& p, hipFuncAttributes* attr, double* meas) {
   constexpr Profile pr = profile_for(T, AL, CH);
+#if INST_MEAS
+  auto* kern = &trial_kernel_meas<Real, kF, T, NSLOT, AL, CH, CSI, pr.minw, pr.nbuf, pr.symw_lds>;
+#else
   auto* kern = &trial_kernel<Real, kF, T, NSLOT, AL, CH, CSI, pr.minw, pr.nbuf, pr.symw_lds>;
+#endif
   if (attr) return hipFuncGetAttributes(attr, reinterpret_cast<const void*>(kern));
   // CSI: the per-antenna power table is dynamic LDS, A reals (trial_kernel pw_csi)
   const size_t dyn = CSI ? sizeof(Real) * (size_t)p.n_ant : 0;
+#if INST_MEAS
+  hipLaunchKernelGGL(kern, grid, dim3(T), dyn, st, p, meas);
+#else
   hipLaunchKernelGGL(kern, grid, dim3(T), dyn, st, p);
+#endif
   return hipGetLastError();
 }
 
 template <int T, int NSLOT, bool AL>
 hipError_t by_channel(const InstanceKey& k, dim3 grid, hipStream_t st, const TrialParams<Real>& p, bool* found,
-                      hipFuncAttributes* a) {
+                      hipFuncAttributes* a, double* m) {
   *found = true;
   switch (k.ch) {
     case CH_RAYLEIGH:
-      return k.csi ? go<T, NSLOT, AL, CH_RAYLEIGH, true>(grid, st, p, a)
-                   : go<T, NSLOT, AL, CH_RAYLEIGH, false>(grid, st, p, a);
+      return k.csi ? go<T, NSLOT, AL, CH_RAYLEIGH, true>(grid, st, p, a, m)
+                   : go<T, NSLOT, AL, CH_RAYLEIGH, false>(grid, st, p, a, m);
     case CH_LOS:
-      return k.csi ? go<T, NSLOT, AL, CH_LOS, true>(grid, st, p, a) : go<T, NSLOT, AL, CH_LOS, false>(grid, st, p, a);
+      return k.csi ? go<T, NSLOT, AL, CH_LOS, true>(grid, st, p, a, m)
+                   : go<T, NSLOT, AL, CH_LOS, false>(grid, st, p, a, m);
     case CH_TWOPATH:
-      return k.csi ? go<T, NSLOT, AL, CH_TWOPATH, true>(grid, st, p, a)
-                   : go<T, NSLOT, AL, CH_TWOPATH, false>(grid, st, p, a);
+      return k.csi ? go<T, NSLOT, AL, CH_TWOPATH, true>(grid, st, p, a, m)
+                   : go<T, NSLOT, AL, CH_TWOPATH, false>(grid, st, p, a, m);
     case CH_TABLE:
-      return k.csi ? go<T, NSLOT, AL, CH_TABLE, true>(grid, st, p, a)
-                   : go<T, NSLOT, AL, CH_TABLE, false>(grid, st, p, a);
+      return k.csi ? go<T, NSLOT, AL, CH_TABLE, true>(grid, st, p, a, m)
+                   : go<T, NSLOT, AL, CH_TABLE, false>(grid, st, p, a, m);
     default:
       *found = false;
       return hipSuccess;
@@ -87,38 +105,47 @@ hipError_t by_channel(const InstanceKey& k, dim3 grid, hipStream_t st, const Tri
 
 template <int T>
 hipError_t by_team(const InstanceKey& k, dim3 grid, hipStream_t st, const TrialParams<Real>& p, bool* found,
-                   hipFuncAttributes* a) {
+                   hipFuncAttributes* a, double* m) {
   constexpr int P = kF / T;
   if (k.aligned) {
     if constexpr (8 < P) {
-      if (k.nslot == 8) return by_channel<T, 8, true>(k, grid, st, p, found, a);
+      if (k.nslot == 8) return by_channel<T, 8, true>(k, grid, st, p, found, a, m);
     }
     if constexpr (4 < P) {
-      if (k.nslot == 4) return by_channel<T, 4, true>(k, grid, st, p, found, a);
+      if (k.nslot == 4) return by_channel<T, 4, true>(k, grid, st, p, found, a, m);
     }
     return hipSuccess;
   }
   if (k.nslot != P) return hipSuccess;
-  return by_channel<T, P, false>(k, grid, st, p, found, a);
+  return by_channel<T, P, false>(k, grid, st, p, found, a, m);
 }
 
 }  // namespace
 
-#if INST_F64
+#if INST_MEAS
+#define MIMO_LAUNCH_NAME MIMO_CAT(MIMO_CAT(launch_trial_F, INST_F), _f64_meas)
+#define MIMO_LAUNCH_MEAS_ARG , double* meas
+#elif INST_F64
 #define MIMO_LAUNCH_NAME MIMO_CAT(MIMO_CAT(launch_trial_F, INST_F), _f64)
 #else
 #define MIMO_LAUNCH_NAME MIMO_CAT(MIMO_CAT(launch_trial_F, INST_F), _f32)
 #endif
+#ifndef MIMO_LAUNCH_MEAS_ARG
+#define MIMO_LAUNCH_MEAS_ARG
+#endif
 hipError_t MIMO_LAUNCH_NAME(const InstanceKey& k, dim3 grid, hipStream_t st, const TrialParams<Real>& p, bool* found,
-                            hipFuncAttributes* attr) {
+                            hipFuncAttributes* attr MIMO_LAUNCH_MEAS_ARG) {
+#if !INST_MEAS
+  double* const meas = nullptr;
+#endif
   *found = false;
   if (k.F != kF || k.f64 != kF64) return hipSuccess;
   if constexpr (kF64) {
-    if (k.T == team_size64(kF)) return by_team<team_size64(kF)>(k, grid, st, p, found, attr);
+    if (k.T == team_size64(kF)) return by_team<team_size64(kF)>(k, grid, st, p, found, attr, meas);
   } else {
-    if (k.T == team_size(kF)) return by_team<team_size(kF)>(k, grid, st, p, found, attr);
+    if (k.T == team_size(kF)) return by_team<team_size(kF)>(k, grid, st, p, found, attr, meas);
     if constexpr (alt_team_size(kF) != team_size(kF)) {
-      if (k.T == alt_team_size(kF)) return by_team<alt_team_size(kF)>(k, grid, st, p, found, attr);
+      if (k.T == alt_team_size(kF)) return by_team<alt_team_size(kF)>(k, grid, st, p, found, attr, meas);
     }
   }
   return hipSuccess;

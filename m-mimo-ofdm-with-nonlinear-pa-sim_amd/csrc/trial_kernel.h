@@ -43,6 +43,17 @@ enum PaKind : int { PA_NONE = 0, PA_SOFTLIM = 1, PA_RAPP = 2, PA_TOI = 3 };
 enum ChanKind : int { CH_RAYLEIGH = 1, CH_LOS = 2, CH_TWOPATH = 3, CH_TABLE = 4 };
 enum RxKind : int { RX_CNC = 1, RX_MCNC = 2 };
 
+// Measure instances (trial_inst.hip with -DINST_MEAS=1, float64 only): the same trial, the same
+// counts, and per trial a row of kMeasFixed + n_idx power sums over the valid in-band slots
+// (include/mimo_engine.h mimo_engine_measure_points: Es, Ez0, Re C, Im C, Ed0, then Ee_i per
+// counter index).  The row pointer is an extra argument of that kernel alone: TrialParams is
+// the stride of the per-point table and its layout is tuned (see csi_seed), and the plain
+// instances compile to the code they had (profiles/r08/measure/isa_diff.txt).
+#ifndef MIMO_MEAS_INST
+#define MIMO_MEAS_INST 0
+#endif
+constexpr int kMeasFixed = 5;  // MIMO_MEAS_FIXED
+
 constexpr int kMaxCsiAnt = 512;  // CSI-error runs: antennas (dynamic LDS per team, A doubles; engine.hip checks)
 constexpr uint32_t kFixedCsiTrial = 0xFFFFFFFFu;  // CSI stream counter of fixed-channel runs (oracle/sim.py draws)
 // The measured alternatives of the choices below (channel pipeline on / off per precision,
@@ -757,8 +768,15 @@ __device__ __forceinline__ void fill_tw1(C* tw1_s, const C* twsrc) {
 // the LDS), SYMW_LDS = keep the pre-weighted symbols in LDS (thread-private) instead of
 // registers.  F = 2048 runs (3, 1, true): 25 KiB LDS and <= 168 VGPRs per 128-thread team.
 template <typename R, int F, int T, int NSLOT, bool ALIGNED, int CH, bool CSI, int MINW, int NBUF, bool SYMW_LDS>
+#if MIMO_MEAS_INST
+__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel_meas(TrialParams<R> p0,
+                                                                                                  double* meas_rows) {
+#else
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel(TrialParams<R> p0) {
+  constexpr double* meas_rows = nullptr;
+#endif
   using C = cx<R>;
+  constexpr bool MEAS = MIMO_MEAS_INST != 0 && sizeof(R) == 8;
   // ---- which point and trial this block runs (uniform binary search over point_start)
   uint32_t pi = 0;
   if (p0.n_points > 1) {
@@ -1360,12 +1378,25 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
     const R tot = team_sum<T>((R)errs, red);
     if (t0) out[idx] = (uint32_t)(tot + R(0.5));
   };
+  // measure instances: column `col` of the trial's row = the team's sum of v (team_sum's fixed order)
+  auto measure = [&](int col, R v) __attribute__((always_inline)) {
+    if constexpr (MEAS) {
+      const R tot = team_sum<T>(v, red);
+      if (t0) meas_rows[(size_t)blockIdx.x * (size_t)(kMeasFixed + p0.n_idx) + col] = (double)tot;
+    }
+  };
+  // |a - b|^2 on a valid slot, 0 off band
+  auto err2 = [&](int s, C a, C b) __attribute__((always_inline)) -> R {
+    const C e = csub(a, b);
+    return ((valid_mask >> s) & 1u) ? fmar(e.x, e.x, e.y * e.y) : R(0);
+  };
 
   if (p.incl_clean) {
     // clean run (mp_model.py:159-175): no PA, AGC / noise from sum_a Hhat P = ||Hhat||
     const R etac = team_sum<T>(etac_p, red) / (R)S;
     const R sig_c = sqrt_ieee(p.es_over_snr * etac);
     uint32_t errs = 0;
+    R ee = R(0);
 #pragma unroll
     for (int s = 0; s < NSLOT; ++s) {
       const C sym = qam_point<R>(lab[s], L, hb);
@@ -1376,7 +1407,9 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
       const C zc = mkc((rc.x + sn * zn[s].x) * ig, (rc.y + sn * zn[s].y) * ig);
       const uint32_t lh = slice(zc, L, hb);
       errs += ((valid_mask >> s) & 1u) ? __popc(lh ^ lab[s]) : 0u;
+      if constexpr (MEAS) ee += err2(s, zc, sym);
     }
+    measure(kMeasFixed, ee);
     record(0, errs);
   }
 
@@ -1387,6 +1420,26 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
     const R ig = ((valid_mask >> s) & 1u) ? R(1) / g[s] : R(0);
     const R sn = sig / frel_of(s);
     z[s] = mkc((r[s].x + sn * zn[s].x) * ig, (r[s].y + sn * zn[s].y) * ig);
+  }
+  if constexpr (MEAS) {
+    // the noiseless AGC'd value z0 = r / g against the transmitted point: Es, Ez0, C = sum z0 conj(s), Ed0
+    R es = R(0), ez0 = R(0), cre = R(0), cim = R(0), ed0 = R(0);
+#pragma unroll
+    for (int s = 0; s < NSLOT; ++s) {
+      const bool v = (valid_mask >> s) & 1u;
+      const C sym = qam_point<R>(lab[s], L, hb);
+      const C z0 = cscale(r[s], v ? R(1) / g[s] : R(0));
+      es += v ? fmar(sym.x, sym.x, sym.y * sym.y) : R(0);
+      ez0 += v ? fmar(z0.x, z0.x, z0.y * z0.y) : R(0);
+      cre += v ? fmar(z0.x, sym.x, z0.y * sym.y) : R(0);
+      cim += v ? fmar(z0.y, sym.x, -(z0.x * sym.y)) : R(0);
+      ed0 += err2(s, z0, sym);
+    }
+    measure(0, es);
+    measure(1, ez0);
+    measure(2, cre);
+    measure(3, cim);
+    measure(4, ed0);
   }
 
   // ---- CNC / MCNC receiver.  One loop per receiver kind (a uniform branch outside the
@@ -1399,12 +1452,17 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
   // slice z - dist, count and record iteration `it`; false once the last one is recorded
   auto detect = [&](int it, uint32_t (&lh)[NSLOT]) __attribute__((always_inline)) -> bool {
     uint32_t errs = 0;
+    R ee = R(0);
 #pragma unroll
     for (int s = 0; s < NSLOT; ++s) {
       lh[s] = slice(csub(z[s], dist[s]), L, hb);
       errs += ((valid_mask >> s) & 1u) ? __popc(lh[s] ^ lab[s]) : 0u;
+      if constexpr (MEAS) ee += err2(s, csub(z[s], dist[s]), qam_point<R>(lab[s], L, hb));
     }
-    if ((p.rec_mask >> it) & 1u) record(idx++, errs);
+    if ((p.rec_mask >> it) & 1u) {
+      measure(kMeasFixed + idx, ee);
+      record(idx++, errs);
+    }
     return it < p.max_iter;
   };
   if (p.receiver == RX_CNC) {

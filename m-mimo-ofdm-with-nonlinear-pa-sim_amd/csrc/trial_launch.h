@@ -38,7 +38,11 @@ struct InstanceKey {
                                       hipFuncAttributes* attr = nullptr);                                 \
   hipError_t launch_trial_F##FV##_f64(const InstanceKey& k, dim3 grid, hipStream_t st,                    \
                                       const TrialParams<double>& p, bool* found,                          \
-                                      hipFuncAttributes* attr = nullptr);
+                                      hipFuncAttributes* attr = nullptr);                                 \
+  /* the measure instance (float64 only): meas = per-trial rows [grid.x][kMeasFixed + n_idx] */           \
+  hipError_t launch_trial_F##FV##_f64_meas(const InstanceKey& k, dim3 grid, hipStream_t st,               \
+                                           const TrialParams<double>& p, bool* found,                     \
+                                           hipFuncAttributes* attr, double* meas);
 MIMO_DECLARE_LAUNCH(128)
 MIMO_DECLARE_LAUNCH(256)
 MIMO_DECLARE_LAUNCH(512)

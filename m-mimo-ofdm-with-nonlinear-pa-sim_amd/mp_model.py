@@ -538,6 +538,40 @@ class Link:
         if stats is not None:
             stats.update(trials=trial.copy(), trials_run=ran, rounds=rounds)
 
+    # ------------------------------------------------------------------ measure mode
+    def measure(self, incl_clean_run: bool, reroll_chan: bool, cnc_n_iter_lst, seed_arr, n_trials: int):
+        """Signal / distortion powers of the current grid point over trials [0, n_trials) of
+        ``simulate``'s trial sequence (the same seed_arr, the same channel, bit and noise draws):
+        a ``_engine.SignalStats`` -- gain, in-band SDR at the user, SDR at the slicer, and
+        the signal-to-error ratio per counter ([clean] + one per sorted, unique iteration) --
+        with the bit-error totals of those trials.  A fixed number of trials, no stopping rule."""
+        return self.measure_points(incl_clean_run, reroll_chan, cnc_n_iter_lst, [seed_arr], [self.point_params()],
+                                   n_trials)[0]
+
+    def measure_points(self, incl_clean_run: bool, reroll_chan: bool, cnc_n_iter_lst, seed_arrs, point_params,
+                       n_trials) -> list:
+        """``measure`` for many grid points of this system in one engine call
+        (mimo_engine_measure_points); ``point_params`` as for ``simulate_points``, ``n_trials``
+        one number or one per point.  -> a list of ``_engine.SignalStats``.  Single GPU."""
+        P = len(point_params)
+        if len(seed_arrs) != P:
+            raise ValueError("one seed_arr per point")
+        for pp in point_params:
+            if pp["snr_db"] is None:
+                raise ValueError("set_snr() must be called before measure()")
+        n = np.broadcast_to(np.asarray(n_trials, dtype=np.int64), (P,))
+        if np.any(n < 0):
+            raise ValueError("n_trials must be >= 0")
+        dev = self.device if self.device is not None else _default_device()
+        acquire_device_slot(dev)  # private totals: nobody else closes them, never wait
+        with SlotHeartbeat(dev):
+            eng = self.engine(reroll_chan)
+            uniq = sorted(set(int(i) for i in np.asarray(cnc_n_iter_lst, dtype=np.int64).reshape(-1)))
+            err, bits, meas, _, _ = eng.measure_points([_engine.Engine.make_point(**pp) for pp in point_params],
+                                                       [_seed64(s) for s in seed_arrs], np.zeros(P, np.int64), n,
+                                                       uniq, incl_clean_run)
+        return [_engine.SignalStats(meas[i], err[i], bits[i]) for i in range(P)]
+
     def update_distortion(self, ibo_val_db: float) -> None:
         """(mp_model.py:230-241)"""
         self.my_array.update_distortion(ibo_db=ibo_val_db, avg_sample_pow=self.my_mod.avg_sample_power)

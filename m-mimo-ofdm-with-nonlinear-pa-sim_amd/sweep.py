@@ -233,6 +233,26 @@ def run_grid(link, ibo_arr, ebn0_arr, iters, incl_clean=True, seed=2137, rank=0,
     return counts[..., 0], counts[..., 1]
 
 
+def measure_vs_ibo(link, ibo_arr, iters, n_trials, seed=2137, incl_clean=False, reroll_chan=True):
+    """Signal / distortion powers at the user for every IBO of ``ibo_arr`` at the link's current
+    SNR: ``n_trials`` trials per point, all points in one ``Link.measure_points`` call (one GPU;
+    point i is seeded by ``point_seed(seed, i)``).  -> a list of ``_engine.SignalStats``."""
+    params, seeds = [], []
+    for i, ibo in enumerate(np.asarray(ibo_arr, dtype=np.float64)):
+        link.update_distortion(ibo_val_db=float(ibo))
+        params.append(dict(link.point_params()))
+        seeds.append(point_seed(seed, i))
+    return link.measure_points(incl_clean, reroll_chan, iters, seeds, params, n_trials)
+
+
+def sdr_vs_ibo_rows(ibo_arr, stats):
+    """CSV rows of the SDR sweep: IBO axis, in-band SDR at the user [dB], SDR at the slicer
+    [dB], then the signal-to-error ratio [dB] of each recorded iteration."""
+    sndr = np.asarray([st.sndr_db for st in stats], dtype=np.float64)
+    return ([np.asarray(ibo_arr), np.asarray([st.sdr_db for st in stats]),
+             np.asarray([st.slicer_sdr_db for st in stats])] + [sndr[:, j] for j in range(sndr.shape[1])])
+
+
 def ber_from_counts(err, bits):
     """BER with NaN where nothing was sent (main_mp_miso_cnc_ber_vs_ebn0.py:134-139)."""
     err = np.asarray(err, dtype=np.float64)
@@ -307,7 +327,9 @@ def _build_link(args, device):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--grid", choices=["ber_vs_ebn0", "fixed_ber"], default="fixed_ber")
+    ap.add_argument("--grid", choices=["ber_vs_ebn0", "fixed_ber", "sdr_vs_ibo"], default="fixed_ber",
+                    help="sdr_vs_ibo: measured in-band SDR and per-iteration signal-to-error ratio per IBO "
+                         "(--n-trials trials per point at the first --ebn0 value; one GPU)")
     ap.add_argument("--n-ant", type=int, default=64)
     ap.add_argument("--n-sc", type=int, default=2048)
     ap.add_argument("--n-fft", type=int, default=4096)
@@ -325,6 +347,7 @@ def main():
     ap.add_argument("--bits-sent-max", type=int, default=int(5e6))
     ap.add_argument("--n-err-min", type=int, default=int(1e5))
     ap.add_argument("--seed", type=int, default=2137)
+    ap.add_argument("--n-trials", type=int, default=4096, help="sdr_vs_ibo: trials per IBO point")
     ap.add_argument("--out", type=str, default="figs/csv_results")
     ap.add_argument("--split", choices=["points", "trials", "auto"], default="auto",
                     help="ranks deal whole points by cost (one all-reduce at the end), or share every point's "
@@ -346,6 +369,20 @@ def main():
     iters = np.asarray([int(x) for x in args.iters.split(",")])
     incl_clean = args.grid == "ber_vs_ebn0"
     link = _build_link(args, local)
+    if args.grid == "sdr_vs_ibo":
+        if world > 1:
+            raise SystemExit("--grid sdr_vs_ibo runs on one GPU")
+        m = link.my_mod
+        link.set_snr(float(ebn0_to_snr(ebn0_arr[0], m.n_sub_carr, m.n_sub_carr, m.constel_size)))
+        t0 = time.perf_counter()
+        stats = measure_vs_ibo(link, ibo_arr, iters, args.n_trials, args.seed)
+        name = "sdr_vs_ibo_%s_%s_nant%d_ebn0_%d_ibo_min%d_max%d_step%1.2f_ntrials%d_niter%s" % (
+            args.receiver, args.channel, args.n_ant, ebn0_arr[0], min(ibo_arr), max(ibo_arr),
+            ibo_arr[1] - ibo_arr[0] if len(ibo_arr) > 1 else 0.0, args.n_trials, "_".join(str(v) for v in iters))
+        save_to_csv(sdr_vs_ibo_rows(ibo_arr, stats), name, directory=args.out)
+        print(f"sdr sweep done: {len(ibo_arr)} IBO points x {args.n_trials} trials in "
+              f"{time.perf_counter() - t0:.1f} s -> {args.out}")
+        return
     t0 = time.perf_counter()
     err, bits = run_grid(link, ibo_arr, ebn0_arr, iters, incl_clean, args.seed, rank, world, dist, local,
                          split=args.split)
