@@ -10,6 +10,8 @@
  *     mimo_engine_set_point     <- Link.update_distortion / set_snr    mp_model.py:230-251
  *     mimo_engine_run           <- Link.simulate (trial loop)          mp_model.py:89-228
  *     mimo_engine_measure_points   the same trials with signal / distortion power sums (SDR, EVM)
+ *     mimo_engine_spectrum_points  the same trials with the array's radiated PSD per FFT bin
+ *                                  (out-of-band emission, Bussgang gain, efficiency)
  *     mimo_engine_run_points    <- the drivers' grid loops over (IBO, Eb/N0), one launch
  *                                  for many points   main_mp_miso_cnc_constant_ber_req_ebn0_vs_ibo.py:100-215
  *   fine seams (float64 stage kernels, caller-owned host arrays)
@@ -156,6 +158,31 @@ int32_t mimo_engine_measure_points(mimo_engine* e, int32_t n_points, const mimo_
                                    const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters,
                                    int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
                                    uint32_t* per_trial, double* meas_out, double* per_trial_meas);
+/* Spectrum mode (float64 engines): the trials, arguments and point rules of mimo_engine_run_points
+ * and the same counts, plus per point a row of n_spec = n_fft + MIMO_SPEC_FIXED sums over what the
+ * array radiates in the main transmission of every trial, with Y_a = FFT(PA(IFFT(X_a))) of antenna
+ * a (ortho transform pair) and X_a = s conj(Hhat_a) / ||Hhat|| its precoded input (the estimate
+ * under CSI error):
+ *   [k], k < n_fft     psd[k] = sum_a |Y_a[k]|^2, FFT bin k in numpy.fft order (bin 0 = DC), so
+ *                      sum_k psd[k] = sum_a sum_n |y_a[n]|^2, the radiated power
+ *   [n_fft]            Ex = sum_a sum_{k in band} |X_a[k]|^2   (= sum_k |s_k|^2 under MRT)
+ *   [n_fft + 1], [+ 2] Re, Im of C = sum_a sum_{k in band} Y_a[k] conj(X_a[k])
+ * from which the out-of-band share, the array's Bussgang gain C / Ex and its efficiency
+ * sum psd / Ex follow.  MCNC re-transmissions and the CNC receiver's chain do not contribute.
+ * spec_out: [n_points][n_spec] totals (ADDED to; summed in a fixed order: equal calls return equal
+ * bits).  per_trial_spec: optional [sum n_trials][n_spec] rows in point order, NULL to skip; they
+ * do not depend on how the call is split into launches.  The per-trial rows of one launch live in
+ * a device buffer of at most MIMO_SPEC_BUFFER_BYTES (256 MiB, a design figure), so a spectrum
+ * launch holds floor(2^28 / (8 n_spec)) trials -- 4,094 at n_fft 8192, 129,553 at 256 -- or
+ * fewer (MIMO_MAX_LAUNCH_TRIALS).  A float32 engine or a null spec_out is MIMO_EINVAL, before any
+ * HIP call.  (Added within ABI 8: a library without it is reported by name.) */
+enum { MIMO_SPEC_FIXED = 3 };
+#define MIMO_SPEC_BUFFER_BYTES (256u << 20)
+int32_t mimo_spectrum_width(int32_t n_fft); /* n_fft + MIMO_SPEC_FIXED; host only, EINVAL for a bad n_fft */
+int32_t mimo_engine_spectrum_points(mimo_engine* e, int32_t n_points, const mimo_point* points, const uint64_t* seeds,
+                                    const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters,
+                                    int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
+                                    uint32_t* per_trial, double* spec_out, double* per_trial_spec);
 /* Device time of the trial kernels of the last run, in ms (HIP events on the engine stream). */
 double mimo_engine_last_kernel_ms(const mimo_engine* e);
 /* Which kernel instance the current config selects: "F=2048 T=128 slots=8 aligned ..." */

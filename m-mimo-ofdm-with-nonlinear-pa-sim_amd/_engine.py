@@ -67,6 +67,10 @@ SYMBOLS = {
     "mimo_engine_measure_points": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(MimoPoint), _u64p,
                                                     _u64p, _u64p, _i32p, ctypes.c_int32, ctypes.c_int32, _u64p, _u64p,
                                                     _u32p, _dp, _dp]),
+    "mimo_spectrum_width": (ctypes.c_int32, [ctypes.c_int32]),
+    "mimo_engine_spectrum_points": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(MimoPoint), _u64p,
+                                                     _u64p, _u64p, _i32p, ctypes.c_int32, ctypes.c_int32, _u64p, _u64p,
+                                                     _u32p, _dp, _dp]),
     "mimo_engine_last_kernel_ms": (ctypes.c_double, [ctypes.c_void_p]),
     "mimo_engine_describe": (ctypes.c_char_p, [ctypes.c_void_p]),
     "mimo_engine_destroy": (None, [ctypes.c_void_p]),
@@ -100,6 +104,7 @@ class EngineError(RuntimeError):
 
 ABI_VERSION = 8  # include/mimo_engine.h MIMO_ABI_VERSION
 MEAS_FIXED = 5   # include/mimo_engine.h MIMO_MEAS_FIXED
+SPEC_FIXED = 3   # include/mimo_engine.h MIMO_SPEC_FIXED
 
 
 def lib():
@@ -226,6 +231,95 @@ class SignalStats:
                 f"sndr_db={np.array2string(self.sndr_db, precision=3)})")
 
 
+def inband_bins(n_fft, n_sub_carr):
+    """Data sub-carrier k -> FFT bin (modulation.py:266-267, 293): the negative half first, DC skipped."""
+    half = n_sub_carr // 2
+    return np.concatenate((np.arange(n_fft - half, n_fft), np.arange(1, half + 1)))
+
+
+class SpectrumStats:
+    """Radiated spectrum of a spectrum call (mimo_engine_spectrum_points): one row
+    ``[psd[0] ... psd[F-1], Ex, Re C, Im C]`` of sums over trials and antennas -- the power the
+    array radiates per FFT bin (numpy.fft order), its precoded input power and the correlation of
+    output and input over the ``n_sub_carr`` data sub-carriers.  ``a + b`` pools two measurements."""
+
+    def __init__(self, row, n_sub_carr, n_trials=None):
+        self.row = np.array(row, np.float64).reshape(-1)
+        self.n_fft = self.row.size - SPEC_FIXED
+        self.n_sub_carr = int(n_sub_carr)
+        if self.n_fft < 4 or not 0 < self.n_sub_carr <= self.n_fft - 2 or self.n_sub_carr % 2:
+            raise ValueError("a spectrum row has n_fft + 3 entries, and n_sub_carr is even and at most n_fft - 2")
+        self.n_trials = None if n_trials is None else int(n_trials)
+
+    psd = property(lambda self: self.row[:self.n_fft].copy())
+    ex = property(lambda self: float(self.row[self.n_fft]))
+    c = property(lambda self: complex(self.row[self.n_fft + 1], self.row[self.n_fft + 2]))
+
+    @property
+    def freq_index(self):
+        """Signed bin index of ``psd_centered``'s entries: -F/2 ... F/2 - 1."""
+        return np.arange(-(self.n_fft // 2), self.n_fft - self.n_fft // 2)
+
+    @property
+    def psd_centered(self):
+        """``psd`` fft-shifted: most negative frequency first, DC in the middle (see ``freq_index``)."""
+        return np.fft.fftshift(self.row[:self.n_fft])
+
+    @property
+    def total(self):
+        return float(self.row[:self.n_fft].sum())
+
+    @property
+    def inband(self):
+        """Power in the data sub-carriers' bins (the DC bin is out of band)."""
+        return float(self.row[inband_bins(self.n_fft, self.n_sub_carr)].sum())
+
+    @property
+    def oob(self):
+        mask = np.ones(self.n_fft, bool)
+        mask[inband_bins(self.n_fft, self.n_sub_carr)] = False
+        return float(self.row[:self.n_fft][mask].sum())
+
+    @property
+    def oob_ratio_db(self):
+        """10 log10(oob / total); -inf without out-of-band power."""
+        return _ratio_db(self.oob, self.total)
+
+    @property
+    def gain(self):
+        """C / Ex: the array's measured Bussgang gain."""
+        return self.c / self.ex if self.ex > 0 else complex(np.inf)
+
+    @property
+    def efficiency(self):
+        """total / Ex: radiated power over precoded input power."""
+        return self.total / self.ex if self.ex > 0 else np.inf
+
+    @property
+    def radiated_sdr_db(self):
+        """|C|^2 / Ex over inband - |C|^2 / Ex: in-band power correlated with the input over the rest."""
+        sig = abs(self.c) ** 2 / self.ex if self.ex > 0 else np.inf
+        return _ratio_db(sig, self.inband - sig)
+
+    @property
+    def psd_rel_db(self):
+        """``psd`` over the mean in-band ``psd``, in dB."""
+        return _ratio_db(self.row[:self.n_fft], self.inband / self.n_sub_carr)
+
+    def __add__(self, other):
+        if not isinstance(other, SpectrumStats):
+            return NotImplemented
+        if other.row.size != self.row.size or other.n_sub_carr != self.n_sub_carr:
+            raise ValueError("spectra of different systems cannot be pooled")
+        n = None if self.n_trials is None or other.n_trials is None else self.n_trials + other.n_trials
+        return SpectrumStats(self.row + other.row, self.n_sub_carr, n)
+
+    def __repr__(self):
+        return (f"SpectrumStats(n_fft={self.n_fft}, oob_ratio_db={self.oob_ratio_db:.3f}, "
+                f"radiated_sdr_db={self.radiated_sdr_db:.3f}, gain={abs(self.gain):.4f}, "
+                f"efficiency={self.efficiency:.4f})")
+
+
 class Engine:
     """One configured system (the deep-copied objects of a ``Link``) on one GPU."""
 
@@ -259,6 +353,7 @@ class Engine:
             raise ValueError(L.mimo_last_error().decode())
         self._h, self._L = h, L   # the library this handle belongs to
         self.n_sub_carr, self.constel_size = n_sub_carr, constel_size
+        self.n_fft = n_fft
 
     @staticmethod
     def make_point(ibo_db, snr_db, avg_symbol_power, pa_kind, sat_pow=0.0, p_hardness=0.0, toi_coeff=0.0,
@@ -354,6 +449,46 @@ class Engine:
         err, bits, meas, pt, pm = self.measure_points([point], [seed], [first_trial], [n_trials], iters, incl_clean,
                                                       per_trial)
         return err[0], bits[0], meas[0], pt, pm
+
+    def spectrum_points(self, points, seeds, first_trials, n_trials, iters, incl_clean=False, per_trial=False):
+        """run_points in spectrum mode (mimo_engine_spectrum_points; float64 engines): the same
+        trials and counts, and per point the row of the array's radiated PSD per FFT bin, Ex and C.
+        -> (err[P, n_idx], bits[P, n_idx], spec[P, n_spec], per-trial counts [sum n_trials, n_idx]
+        or None, per-trial rows [sum n_trials, n_spec] or None); SpectrumStats(spec[i], n_sub_carr)."""
+        P = len(points)
+        arr = (MimoPoint * max(1, P))()
+        for i, pt in enumerate(points):
+            arr[i] = pt if isinstance(pt, MimoPoint) else self.make_point(**pt)
+        it = _c(sorted(set(int(i) for i in iters)), np.int32)
+        n_idx = len(it) + (1 if incl_clean else 0)
+        n_spec = self.n_fft + SPEC_FIXED
+        sd = _c(np.asarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], dtype=np.uint64).reshape(-1), np.uint64)
+        ft = _c(np.asarray(first_trials, dtype=np.uint64).reshape(-1), np.uint64)
+        nt = _c(np.asarray(n_trials, dtype=np.uint64).reshape(-1), np.uint64)
+        if not (len(sd) == len(ft) == len(nt) == P):
+            raise ValueError("points, seeds, first_trials and n_trials must have the same length")
+        err = np.zeros((P, n_idx), np.uint64)
+        bits = np.zeros((P, n_idx), np.uint64)
+        spec = np.zeros((P, n_spec), np.float64)
+        pt = np.zeros((int(nt.sum()), n_idx), np.uint32) if per_trial else None
+        ps = np.zeros((int(nt.sum()), n_spec), np.float64) if per_trial else None
+        _check(self._L.mimo_engine_spectrum_points(
+            self._h, P, arr, _ptr(sd, ctypes.c_uint64), _ptr(ft, ctypes.c_uint64), _ptr(nt, ctypes.c_uint64),
+            _ptr(it, ctypes.c_int32), len(it), int(bool(incl_clean)), _ptr(err, ctypes.c_uint64),
+            _ptr(bits, ctypes.c_uint64), _ptr(pt, ctypes.c_uint32) if pt is not None else None,
+            _ptr(spec, ctypes.c_double), _ptr(ps, ctypes.c_double) if ps is not None else None))
+        return err, bits, spec, pt, ps
+
+    def spectrum(self, seed, first_trial, n_trials, iters, incl_clean=False, per_trial=False, point=None):
+        """One point (the last set_point's, or ``point``: make_point keywords / MimoPoint).
+        -> (err[n_idx], bits[n_idx], spec[n_spec], per-trial counts or None, per-trial rows or None)."""
+        if point is None:
+            point = getattr(self, "_point", None)
+            if point is None:
+                raise EngineError("mimo_engine_set_point was not called")
+        err, bits, spec, pt, ps = self.spectrum_points([point], [seed], [first_trial], [n_trials], iters, incl_clean,
+                                                       per_trial)
+        return err[0], bits[0], spec[0], pt, ps
 
     @property
     def kernel_ms(self):

@@ -83,6 +83,22 @@ __global__ __launch_bounds__(kReduceMeasThreads) void reduce_meas(const double* 
   }
 }
 
+// Per-slice sums of the spectrum instances' per-trial rows (n_spec = F + MIMO_SPEC_FIXED columns,
+// thousands of them, and at most kSlice rows per slice): block (k, tile) gives each thread one
+// column, which it sums over trial blocks [first[k], first[k + 1]) in trial order -- the loads of
+// a row coalesce across the threads' columns; one partial per (slice, column), no atomics.  The
+// host adds the slice partials of a point in launch and slice order, as for reduce_meas.
+constexpr int kReduceSpecThreads = 256;
+__global__ __launch_bounds__(kReduceSpecThreads) void reduce_spec(const double* __restrict__ rows,
+                                                                  const uint32_t* __restrict__ first, int n_spec,
+                                                                  double* __restrict__ part) {
+  const int k = blockIdx.x, col = blockIdx.y * kReduceSpecThreads + threadIdx.x;
+  if (col >= n_spec) return;
+  double acc = 0.0;
+  for (uint32_t t = first[k]; t < first[k + 1]; ++t) acc += rows[(size_t)t * n_spec + col];
+  part[(size_t)k * n_spec + col] = acc;
+}
+
 }  // namespace
 
 namespace mimo {
@@ -122,6 +138,12 @@ struct mimo_engine {
   size_t meas_cap = 0;
   double* d_mpart = nullptr;              // [launch slices][n_meas]
   size_t mpart_cap = 0;
+  // spectrum calls (mimo_engine_spectrum_points): the same pair, rows of n_fft + MIMO_SPEC_FIXED;
+  // d_spec holds at most MIMO_SPEC_BUFFER_BYTES (it bounds the trials of a spectrum launch)
+  double* d_spec = nullptr;               // [launch blocks][n_spec]
+  size_t spec_cap = 0;
+  double* d_spart = nullptr;              // [launch slices][n_spec]
+  size_t spart_cap = 0;
   // per-launch tables in one device blob, filled by one copy from a pinned host buffer:
   // TrialParams<R>[segments] | uint32 block offsets [segments + 1] |
   // uint32 reduction-slice starts [slices + 1] (<= kSlice trials, one point each) | int32 point of slice [slices]
@@ -221,6 +243,25 @@ hipError_t launch_meas(const mimo::InstanceKey& k, dim3 grid, hipStream_t st, co
     case 2048: return mimo::launch_trial_F2048_f64_meas(k, grid, st, p, found, nullptr, rows);
     case 4096: return mimo::launch_trial_F4096_f64_meas(k, grid, st, p, found, nullptr, rows);
     case 8192: return mimo::launch_trial_F8192_f64_meas(k, grid, st, p, found, nullptr, rows);
+    default: break;
+  }
+#endif
+  return hipSuccess;
+}
+
+// The spectrum instance of the key (float64 only); rows: [grid.x][F + MIMO_SPEC_FIXED] doubles.
+hipError_t launch_spec(const mimo::InstanceKey& k, dim3 grid, hipStream_t st, const mimo::TrialParams<double>& p,
+                       double* rows, bool* found) {
+  *found = false;
+#ifndef MIMO_ONLY_F  // the single-size diagnostic builds link no spectrum instances
+  switch (k.F) {
+    case 128: return mimo::launch_trial_F128_f64_spec(k, grid, st, p, found, nullptr, rows);
+    case 256: return mimo::launch_trial_F256_f64_spec(k, grid, st, p, found, nullptr, rows);
+    case 512: return mimo::launch_trial_F512_f64_spec(k, grid, st, p, found, nullptr, rows);
+    case 1024: return mimo::launch_trial_F1024_f64_spec(k, grid, st, p, found, nullptr, rows);
+    case 2048: return mimo::launch_trial_F2048_f64_spec(k, grid, st, p, found, nullptr, rows);
+    case 4096: return mimo::launch_trial_F4096_f64_spec(k, grid, st, p, found, nullptr, rows);
+    case 8192: return mimo::launch_trial_F8192_f64_spec(k, grid, st, p, found, nullptr, rows);
     default: break;
   }
 #endif
@@ -483,10 +524,13 @@ namespace {
 // meas_out != null (mimo_engine_measure_points): the measure instance runs instead, and its
 // per-trial rows of n_meas = MIMO_MEAS_FIXED + n_idx sums are reduced per slice on the device
 // (reduce_meas) and per point, in slice order, here.
+// spec (mimo_engine_spectrum_points): meas_out / per_trial_meas are the spectrum rows instead, of
+// n_fft + MIMO_SPEC_FIXED sums; the spectrum instance runs, reduce_spec forms the slice partials,
+// and a launch holds no more trials than its rows fit MIMO_SPEC_BUFFER_BYTES.
 int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64_t* seeds,
                const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters, int32_t n_iters,
                int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out, uint32_t* per_trial,
-               double* meas_out = nullptr, double* per_trial_meas = nullptr) {
+               double* meas_out = nullptr, double* per_trial_meas = nullptr, bool spec = false) {
   if (n_points < 0) return fail(MIMO_EINVAL, "n_points must be >= 0");
   if (n_iters < 1 || !iters) return fail(MIMO_EINVAL, "at least one iteration index is required");
   uint32_t rec_mask = 0;
@@ -501,8 +545,8 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
   if (n_points == 0) return MIMO_OK;
   if (!pts || !seeds || !first_trial || !n_trials) return fail(MIMO_EINVAL, "null point arrays");
   const int n_idx = n_iters + (incl_clean ? 1 : 0);
-  const int n_meas = MIMO_MEAS_FIXED + n_idx;
   const mimo_config& c = e->cfg;
+  const int n_meas = spec ? c.n_fft + MIMO_SPEC_FIXED : MIMO_MEAS_FIXED + n_idx;  // row width of either mode
   const bool csi = pts[0].csi_eps >= 0;
   for (int i = 0; i < n_points; ++i) {
     if (int rc = validate_point(e, &pts[i])) return rc;
@@ -548,6 +592,11 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
     const uint64_t v = std::strtoull(env, nullptr, 10);
     if (v >= 1 && v < kChunk) kChunk = v;
   }
+  if (spec) kChunk = std::min<uint64_t>(kChunk, MIMO_SPEC_BUFFER_BYTES / (sizeof(double) * (size_t)n_meas));
+  double*& d_rows = spec ? e->d_spec : e->d_meas;  // per-trial rows and slice partials of the mode
+  size_t& rows_cap = spec ? e->spec_cap : e->meas_cap;
+  double*& d_part = spec ? e->d_spart : e->d_mpart;
+  size_t& part_cap = spec ? e->spart_cap : e->mpart_cap;
   struct Seg {
     int point;
     uint64_t first, n;
@@ -584,8 +633,8 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
       max_sl = std::max(max_sl, nsl);
       tot_sl += nsl;
     }
-    if (int rc = ensure_cap(e->d_meas, e->meas_cap, std::max<size_t>(1, max_blocks * n_meas))) return rc;
-    if (int rc = ensure_cap(e->d_mpart, e->mpart_cap, std::max<size_t>(1, max_sl * n_meas))) return rc;
+    if (int rc = ensure_cap(d_rows, rows_cap, std::max<size_t>(1, max_blocks * n_meas))) return rc;
+    if (int rc = ensure_cap(d_part, part_cap, std::max<size_t>(1, max_sl * n_meas))) return rc;
     mpart.resize(tot_sl * n_meas);
     mpart_point.reserve(tot_sl);
   }
@@ -688,8 +737,9 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
       bool found = false;
       hipError_t le = hipSuccess;
       if constexpr (F64) {
-        le = meas_out ? launch_meas(key, dim3(nb), e->stream, kp, e->d_meas, &found)
-                      : launch(key, dim3(nb), e->stream, kp, &found);
+        le = spec       ? launch_spec(key, dim3(nb), e->stream, kp, d_rows, &found)
+             : meas_out ? launch_meas(key, dim3(nb), e->stream, kp, d_rows, &found)
+                        : launch(key, dim3(nb), e->stream, kp, &found);
       } else {
         le = launch(key, dim3(nb), e->stream, kp, &found);
       }
@@ -704,15 +754,21 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
         HIP_TRY(hipMemcpyAsync(per_trial + rows_done * n_idx, e->d_counts, (size_t)nb * n_idx * sizeof(uint32_t),
                                hipMemcpyDeviceToHost, e->stream));
       if (meas_out) {
-        hipLaunchKernelGGL(reduce_meas, dim3((unsigned)nsl, n_meas), dim3(kReduceMeasThreads), 0, e->stream, e->d_meas,
-                           reinterpret_cast<const uint32_t*>(e->d_blob + o_slice), n_meas, e->d_mpart);
+        if (spec)
+          hipLaunchKernelGGL(reduce_spec,
+                             dim3((unsigned)nsl, (unsigned)((n_meas + kReduceSpecThreads - 1) / kReduceSpecThreads)),
+                             dim3(kReduceSpecThreads), 0, e->stream, d_rows,
+                             reinterpret_cast<const uint32_t*>(e->d_blob + o_slice), n_meas, d_part);
+        else
+          hipLaunchKernelGGL(reduce_meas, dim3((unsigned)nsl, n_meas), dim3(kReduceMeasThreads), 0, e->stream, d_rows,
+                             reinterpret_cast<const uint32_t*>(e->d_blob + o_slice), n_meas, d_part);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(mpart.data() + mpart_done * n_meas, e->d_mpart, nsl * n_meas * sizeof(double),
+        HIP_TRY(hipMemcpyAsync(mpart.data() + mpart_done * n_meas, d_part, nsl * n_meas * sizeof(double),
                                hipMemcpyDeviceToHost, e->stream));
         for (size_t i = 0; i < nsl; ++i) mpart_point.push_back(point_of[i]);
         mpart_done += nsl;
         if (per_trial_meas)
-          HIP_TRY(hipMemcpyAsync(per_trial_meas + rows_done * n_meas, e->d_meas, (size_t)nb * n_meas * sizeof(double),
+          HIP_TRY(hipMemcpyAsync(per_trial_meas + rows_done * n_meas, d_rows, (size_t)nb * n_meas * sizeof(double),
                                  hipMemcpyDeviceToHost, e->stream));
       }
       rows_done += nb;
@@ -789,6 +845,24 @@ int32_t mimo_engine_measure_points(mimo_engine* e, int32_t n_points, const mimo_
                     per_trial, meas_out, per_trial_meas);
 }
 
+int32_t mimo_spectrum_width(int32_t n_fft) {
+  if (!is_pow2(n_fft) || n_fft < 128 || n_fft > 8192)
+    return fail(MIMO_EINVAL, "n_fft must be a power of two in [128, 8192]");
+  return n_fft + MIMO_SPEC_FIXED;
+}
+
+int32_t mimo_engine_spectrum_points(mimo_engine* e, int32_t n_points, const mimo_point* points, const uint64_t* seeds,
+                                    const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters,
+                                    int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
+                                    uint32_t* per_trial, double* spec_out, double* per_trial_spec) {
+  if (!e) return fail(MIMO_EINVAL, "null engine");
+  if (e->cfg.precision != MIMO_PREC_F64)
+    return fail(MIMO_EINVAL, "spectrum needs a float64 engine (no float32 spectrum instances are built)");
+  if (!spec_out) return fail(MIMO_EINVAL, "null spec_out");
+  return run_points(e, n_points, points, seeds, first_trial, n_trials, iters, n_iters, incl_clean, err_out, bits_out,
+                    per_trial, spec_out, per_trial_spec, true);
+}
+
 double mimo_engine_last_kernel_ms(const mimo_engine* e) { return e ? e->last_ms : 0.0; }
 
 const char* mimo_engine_describe(const mimo_engine* e) {
@@ -825,6 +899,8 @@ void mimo_engine_destroy(mimo_engine* e) {
     if (e->d_counts) (void)hipFree(e->d_counts);
     if (e->d_meas) (void)hipFree(e->d_meas);
     if (e->d_mpart) (void)hipFree(e->d_mpart);
+    if (e->d_spec) (void)hipFree(e->d_spec);
+    if (e->d_spart) (void)hipFree(e->d_spart);
     if (e->d_blob) (void)hipFree(e->d_blob);
     if (e->h_blob) (void)hipHostFree(e->h_blob);
     (void)hipEventDestroy(e->ev0);

@@ -1,6 +1,7 @@
 // Instantiates the fused trial kernel for one FFT size and arithmetic type
 // (compiled once per -DINST_F=<size> -DINST_F64=<0|1>), and once more per size with
-// -DINST_F64=1 -DINST_MEAS=1 for the measure instances (trial_kernel.h MIMO_MEAS_INST).
+// -DINST_F64=1 -DINST_MEAS=1 for the measure instances (trial_kernel.h MIMO_MEAS_INST) and with
+// -DINST_F64=1 -DINST_SPEC=1 for the spectrum instances (MIMO_SPEC_INST).
 #include <type_traits>
 
 #ifndef INST_F
@@ -16,6 +17,13 @@
 #error "measure instances are float64 only"
 #endif
 #define MIMO_MEAS_INST INST_MEAS
+#ifndef INST_SPEC
+#define INST_SPEC 0
+#endif
+#if INST_SPEC && (!INST_F64 || INST_MEAS)
+#error "spectrum instances are float64 only, and objects of their own"
+#endif
+#define MIMO_SPEC_INST INST_SPEC
 
 #include "trial_launch.h"
 
@@ -60,19 +68,22 @@ constexpr Profile profile_for(int T, bool aligned, int ch) {
 
 // attr != null: no launch, the instance's attributes instead (its static LDS, which the
 // engine checks with the CSI table's dynamic LDS against the device limit before a launch).
-// meas: the measure instances' per-trial rows [grid.x][kMeasFixed + n_idx] (unused otherwise).
+// meas: the measure instances' per-trial rows [grid.x][kMeasFixed + n_idx], the spectrum
+// instances' [grid.x][kF + kSpecFixed] (unused otherwise).
 template <int T, int NSLOT, bool AL, int CH, bool CSI>
 hipError_t go(dim3 grid, hipStream_t st, const TrialParams<Real>& p, hipFuncAttributes* attr, double* meas) {
   constexpr Profile pr = profile_for(T, AL, CH);
 #if INST_MEAS
   auto* kern = &trial_kernel_meas<Real, kF, T, NSLOT, AL, CH, CSI, pr.minw, pr.nbuf, pr.symw_lds>;
+#elif INST_SPEC
+  auto* kern = &trial_kernel_spec<Real, kF, T, NSLOT, AL, CH, CSI, pr.minw, pr.nbuf, pr.symw_lds>;
 #else
   auto* kern = &trial_kernel<Real, kF, T, NSLOT, AL, CH, CSI, pr.minw, pr.nbuf, pr.symw_lds>;
 #endif
   if (attr) return hipFuncGetAttributes(attr, reinterpret_cast<const void*>(kern));
   // CSI: the per-antenna power table is dynamic LDS, A reals (trial_kernel pw_csi)
   const size_t dyn = CSI ? sizeof(Real) * (size_t)p.n_ant : 0;
-#if INST_MEAS
+#if INST_MEAS || INST_SPEC
   hipLaunchKernelGGL(kern, grid, dim3(T), dyn, st, p, meas);
 #else
   hipLaunchKernelGGL(kern, grid, dim3(T), dyn, st, p);
@@ -125,6 +136,9 @@ hipError_t by_team(const InstanceKey& k, dim3 grid, hipStream_t st, const TrialP
 #if INST_MEAS
 #define MIMO_LAUNCH_NAME MIMO_CAT(MIMO_CAT(launch_trial_F, INST_F), _f64_meas)
 #define MIMO_LAUNCH_MEAS_ARG , double* meas
+#elif INST_SPEC
+#define MIMO_LAUNCH_NAME MIMO_CAT(MIMO_CAT(launch_trial_F, INST_F), _f64_spec)
+#define MIMO_LAUNCH_MEAS_ARG , double* meas
 #elif INST_F64
 #define MIMO_LAUNCH_NAME MIMO_CAT(MIMO_CAT(launch_trial_F, INST_F), _f64)
 #else
@@ -135,7 +149,7 @@ hipError_t by_team(const InstanceKey& k, dim3 grid, hipStream_t st, const TrialP
 #endif
 hipError_t MIMO_LAUNCH_NAME(const InstanceKey& k, dim3 grid, hipStream_t st, const TrialParams<Real>& p, bool* found,
                             hipFuncAttributes* attr MIMO_LAUNCH_MEAS_ARG) {
-#if !INST_MEAS
+#if !INST_MEAS && !INST_SPEC
   double* const meas = nullptr;
 #endif
   *found = false;

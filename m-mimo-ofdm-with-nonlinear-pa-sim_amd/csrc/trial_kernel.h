@@ -54,6 +54,24 @@ enum RxKind : int { RX_CNC = 1, RX_MCNC = 2 };
 #endif
 constexpr int kMeasFixed = 5;  // MIMO_MEAS_FIXED
 
+// Spectrum instances (trial_inst.hip with -DINST_SPEC=1, float64 only): the same trial, the same
+// counts, and per trial a row of F + kSpecFixed doubles from the main array pass alone
+// (include/mimo_engine.h mimo_engine_spectrum_points): psd[k] = sum_a |Y_a[k]|^2 for every FFT
+// bin k (numpy.fft order, ortho transform pair), then Ex = sum_a sum_band |X_a|^2 and Re / Im of
+// C = sum_a sum_band Y_a conj(X_a).  After the forward transform register m of frequency thread
+// tf holds bin tf + T m in every FFT kind (plain and wave-split teams: tf = t; the F 8192 split
+// FFT: tf = 2 vt + g, so bin 2 (vt + 256 m) + g -- csrc/probe.hip writes its outputs by the same
+// statement).  psd accumulator: a read-modify-write of the thread's own P cells of the trial's
+// row once per antenna (antenna 0 stores), in antenna order, no atomics and no synchronisation;
+// the rows of the teams in flight stay L2-resident.  (One form for all sizes: from F 256 up the
+// instances sit at their register cap with scratch already -- 168 VGPRs up to F 2048, 256 from
+// F 4096 -- so P more f64 registers would spill to the same memory.)  As for the measure
+// instances the row pointer is an extra argument of that kernel alone.
+#ifndef MIMO_SPEC_INST
+#define MIMO_SPEC_INST 0
+#endif
+constexpr int kSpecFixed = 3;  // MIMO_SPEC_FIXED
+
 constexpr int kMaxCsiAnt = 512;  // CSI-error runs: antennas (dynamic LDS per team, A doubles; engine.hip checks)
 constexpr uint32_t kFixedCsiTrial = 0xFFFFFFFFu;  // CSI stream counter of fixed-channel runs (oracle/sim.py draws)
 // The measured alternatives of the choices below (channel pipeline on / off per precision,
@@ -771,12 +789,19 @@ template <typename R, int F, int T, int NSLOT, bool ALIGNED, int CH, bool CSI, i
 #if MIMO_MEAS_INST
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel_meas(TrialParams<R> p0,
                                                                                                   double* meas_rows) {
+  constexpr double* spec_rows = nullptr;
+#elif MIMO_SPEC_INST
+__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel_spec(TrialParams<R> p0,
+                                                                                                  double* spec_rows) {
+  constexpr double* meas_rows = nullptr;
 #else
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel(TrialParams<R> p0) {
   constexpr double* meas_rows = nullptr;
+  constexpr double* spec_rows = nullptr;
 #endif
   using C = cx<R>;
   constexpr bool MEAS = MIMO_MEAS_INST != 0 && sizeof(R) == 8;
+  constexpr bool SPEC = MIMO_SPEC_INST != 0 && sizeof(R) == 8;
   // ---- which point and trial this block runs (uniform binary search over point_start)
   uint32_t pi = 0;
   if (p0.n_points > 1) {
@@ -1133,6 +1158,8 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
   // (CHN::normals_w): one multiply per draw instead of three, |h w|^2 from the radius
   constexpr bool WSC_RAY = MIMO_WSC_RAY != 0 && WSC && CH == CH_RAYLEIGH && ALIGNED;  // (fp64: no pipelined draws)
   R wsc[WSC ? NSLOT : 1];
+  // spectrum instances: the thread's in-band sums over the main pass (|x|^2, Re / Im of y conj(x))
+  R sp_ex = R(0), sp_cre = R(0), sp_cim = R(0);
   auto array_pass = [&](bool main_pass, C (&acc)[NSLOT]) __attribute__((always_inline)) {
 #pragma unroll
     for (int s = 0; s < NSLOT; ++s) acc[s] = czero<R>();
@@ -1244,6 +1271,9 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
           e2[s] = fmar(e.x, e.x, e.y * e.y);
           vk = fmar(e2[s], inv_nrm[s] * inv_nrm[s], vk);  // inv_nrm = 0 off band
         }
+        if constexpr (SPEC) {
+          if (main_pass) sp_ex = fmar(x[s].x, x[s].x, fmar(x[s].y, x[s].y, sp_ex));
+        }
       }
       if (main_pass) {
         vk = wave_sum_lane63(vk);
@@ -1312,6 +1342,48 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
       }
       // keep the vk_part / alpha_s hand-offs ordered when the ablations drop the barriers
       if (MIMO_ABL(p, ABL_FFT) || (ALPHA1 && MIMO_ABL(p, ABL_XCHG))) __syncthreads();
+      if constexpr (SPEC) {
+        if (main_pass) {
+          // psd: |d|^2 / F (ortho) into the thread's cells, bin tl + T m; 1 / F is a power of two
+          double* cell = spec_rows + (size_t)blockIdx.x * (size_t)(F + kSpecFixed) + tl;
+          R pw[P];
+#pragma unroll
+          for (int m = 0; m < P; ++m) pw[m] = fmar(d[m].x, d[m].x, d[m].y * d[m].y) * R(1.0 / F);
+          if (a == 0) {
+#pragma unroll
+            for (int m = 0; m < P; ++m) cell[T * m] = (double)pw[m];
+          } else {
+            double old[P];
+#pragma unroll
+            for (int m = 0; m < P; ++m) old[m] = cell[T * m];
+#pragma unroll
+            for (int m = 0; m < P; ++m) cell[T * m] = old[m] + (double)pw[m];
+          }
+          // C: the precoder input x rebuilt from the (estimated) channel as the slot loop above
+          // formed it (not held across the transforms); x = 0 off band
+#pragma unroll
+          for (int s = 0; s < NSLOT; ++s) {
+            const C e = hest(s);
+            C xs;
+            if constexpr (PRE_EW) {
+              C ew;
+              if constexpr (WSC) {
+                ew = e;
+              } else {
+                R in = inv_nrm[s];
+                asm volatile("" : "+v"(in));
+                ew = cscale(e, in * inv_sqrt_f);
+              }
+              xs = cmulc(slab_point(s), ew);
+            } else {
+              xs = cmulc(symw(s), e);
+            }
+            const C y = SL::gather(d, s, t0);
+            sp_cre = fmar(y.x, xs.x, fmar(y.y, xs.y, sp_cre));
+            sp_cim = fmar(y.y, xs.x, fmar(-y.x, xs.y, sp_cim));
+          }
+        }
+      }
       R alpha_a = R(0);
       if (main_pass) alpha_a = ALPHA1 ? alpha_s[vkb] : alpha_of_vk();
 #pragma unroll
@@ -1349,6 +1421,16 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
     for (int s = 0; s < NSLOT; ++s) wsc[s] = inv_nrm[s] * inv_sqrt_f;
   }
   array_pass(true, r);
+  if constexpr (SPEC) {
+    // Ex = F sum |x|^2 (x carries 1 / sqrt(F)); Y conj(X) = (d / sqrt(F)) conj(x sqrt(F)) = d conj(x)
+    const R ex = team_sum<T>(sp_ex, red), cre = team_sum<T>(sp_cre, red), cim = team_sum<T>(sp_cim, red);
+    if (t0) {
+      double* fixed = spec_rows + (size_t)blockIdx.x * (size_t)(F + kSpecFixed) + F;
+      fixed[0] = (double)(ex * (R)F);
+      fixed[1] = (double)cre;
+      fixed[2] = (double)cim;
+    }
+  }
   if constexpr (WSC) {
 #pragma unroll
     for (int s = 0; s < NSLOT; ++s) inv_nrm[s] = wsc[s] / inv_sqrt_f;

@@ -42,7 +42,11 @@ struct InstanceKey {
   /* the measure instance (float64 only): meas = per-trial rows [grid.x][kMeasFixed + n_idx] */           \
   hipError_t launch_trial_F##FV##_f64_meas(const InstanceKey& k, dim3 grid, hipStream_t st,               \
                                            const TrialParams<double>& p, bool* found,                     \
-                                           hipFuncAttributes* attr, double* meas);
+                                           hipFuncAttributes* attr, double* meas);                        \
+  /* the spectrum instance (float64 only): spec = per-trial rows [grid.x][F + kSpecFixed] */              \
+  hipError_t launch_trial_F##FV##_f64_spec(const InstanceKey& k, dim3 grid, hipStream_t st,               \
+                                           const TrialParams<double>& p, bool* found,                     \
+                                           hipFuncAttributes* attr, double* spec);
 MIMO_DECLARE_LAUNCH(128)
 MIMO_DECLARE_LAUNCH(256)
 MIMO_DECLARE_LAUNCH(512)

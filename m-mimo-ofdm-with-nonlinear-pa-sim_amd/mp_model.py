@@ -572,6 +572,35 @@ class Link:
                                                        uniq, incl_clean_run)
         return [_engine.SignalStats(meas[i], err[i], bits[i]) for i in range(P)]
 
+    # ------------------------------------------------------------------ spectrum mode
+    def spectrum(self, reroll_chan: bool, seed_arr, n_trials: int):
+        """Radiated spectrum of the current grid point over trials [0, n_trials) of ``simulate``'s
+        trial sequence (the same seed_arr, the same channel and bit draws): a
+        ``_engine.SpectrumStats`` -- the power the array radiates per FFT bin, its out-of-band
+        share, the array's Bussgang gain and efficiency.  A fixed number of trials, no stopping rule."""
+        return self.spectrum_points(reroll_chan, [seed_arr], [self.point_params()], n_trials)[0]
+
+    def spectrum_points(self, reroll_chan: bool, seed_arrs, point_params, n_trials) -> list:
+        """``spectrum`` for many grid points of this system in one engine call
+        (mimo_engine_spectrum_points); ``point_params`` as for ``simulate_points``, ``n_trials``
+        one number or one per point.  The spectrum is taken before the channel and the noise, so
+        a point whose SNR was never set runs at 0 dB.  -> a list of ``_engine.SpectrumStats``.
+        Single GPU."""
+        P = len(point_params)
+        if len(seed_arrs) != P:
+            raise ValueError("one seed_arr per point")
+        n = np.broadcast_to(np.asarray(n_trials, dtype=np.int64), (P,))
+        if np.any(n < 0):
+            raise ValueError("n_trials must be >= 0")
+        pts = [_engine.Engine.make_point(**dict(pp, snr_db=0.0 if pp["snr_db"] is None else pp["snr_db"]))
+               for pp in point_params]
+        dev = self.device if self.device is not None else _default_device()
+        acquire_device_slot(dev)  # private totals: nobody else closes them, never wait
+        with SlotHeartbeat(dev):
+            eng = self.engine(reroll_chan)
+            _, _, spec, _, _ = eng.spectrum_points(pts, [_seed64(s) for s in seed_arrs], np.zeros(P, np.int64), n, [0])
+        return [_engine.SpectrumStats(spec[i], self.my_mod.n_sub_carr, int(n[i])) for i in range(P)]
+
     def update_distortion(self, ibo_val_db: float) -> None:
         """(mp_model.py:230-241)"""
         self.my_array.update_distortion(ibo_db=ibo_val_db, avg_sample_pow=self.my_mod.avg_sample_power)

@@ -253,6 +253,33 @@ def sdr_vs_ibo_rows(ibo_arr, stats):
              np.asarray([st.slicer_sdr_db for st in stats])] + [sndr[:, j] for j in range(sndr.shape[1])])
 
 
+def spectrum_vs_ibo(link, ibo_arr, n_trials, seed=2137, reroll_chan=True):
+    """Radiated spectrum of the array for every IBO of ``ibo_arr``: ``n_trials`` trials per point,
+    all points in one ``Link.spectrum_points`` call (one GPU; point i is seeded by
+    ``point_seed(seed, i)``).  -> a list of ``_engine.SpectrumStats``."""
+    params, seeds = [], []
+    for i, ibo in enumerate(np.asarray(ibo_arr, dtype=np.float64)):
+        link.update_distortion(ibo_val_db=float(ibo))
+        params.append(dict(link.point_params()))
+        seeds.append(point_seed(seed, i))
+    return link.spectrum_points(reroll_chan, seeds, params, n_trials)
+
+
+def oob_vs_ibo_rows(ibo_arr, stats):
+    """CSV rows of the spectrum sweep's summary, one per IBO: IBO, out-of-band share of the
+    radiated power [dB], in-band radiated SDR [dB], |Bussgang gain| of the array, efficiency
+    (radiated over input power)."""
+    return [np.asarray([ibo, st.oob_ratio_db, st.radiated_sdr_db, abs(st.gain), st.efficiency], dtype=np.float64)
+            for ibo, st in zip(np.asarray(ibo_arr, dtype=np.float64), stats)]
+
+
+def psd_vs_ibo_rows(stats):
+    """CSV rows of the spectrum sweep's PSD, one per centred bin (most negative frequency first):
+    the signed bin index, then the PSD over the mean in-band PSD [dB], one column per IBO."""
+    rel = np.stack([np.fft.fftshift(st.psd_rel_db) for st in stats], axis=1)
+    return list(np.concatenate([stats[0].freq_index[:, None].astype(np.float64), rel], axis=1))
+
+
 def ber_from_counts(err, bits):
     """BER with NaN where nothing was sent (main_mp_miso_cnc_ber_vs_ebn0.py:134-139)."""
     err = np.asarray(err, dtype=np.float64)
@@ -327,9 +354,11 @@ def _build_link(args, device):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--grid", choices=["ber_vs_ebn0", "fixed_ber", "sdr_vs_ibo"], default="fixed_ber",
+    ap.add_argument("--grid", choices=["ber_vs_ebn0", "fixed_ber", "sdr_vs_ibo", "psd_vs_ibo"], default="fixed_ber",
                     help="sdr_vs_ibo: measured in-band SDR and per-iteration signal-to-error ratio per IBO "
-                         "(--n-trials trials per point at the first --ebn0 value; one GPU)")
+                         "(--n-trials trials per point at the first --ebn0 value; one GPU).  psd_vs_ibo: the "
+                         "array's radiated PSD per FFT bin, out-of-band share, Bussgang gain and efficiency per "
+                         "IBO (--n-trials trials per point; one GPU)")
     ap.add_argument("--n-ant", type=int, default=64)
     ap.add_argument("--n-sc", type=int, default=2048)
     ap.add_argument("--n-fft", type=int, default=4096)
@@ -347,7 +376,7 @@ def main():
     ap.add_argument("--bits-sent-max", type=int, default=int(5e6))
     ap.add_argument("--n-err-min", type=int, default=int(1e5))
     ap.add_argument("--seed", type=int, default=2137)
-    ap.add_argument("--n-trials", type=int, default=4096, help="sdr_vs_ibo: trials per IBO point")
+    ap.add_argument("--n-trials", type=int, default=4096, help="sdr_vs_ibo, psd_vs_ibo: trials per IBO point")
     ap.add_argument("--out", type=str, default="figs/csv_results")
     ap.add_argument("--split", choices=["points", "trials", "auto"], default="auto",
                     help="ranks deal whole points by cost (one all-reduce at the end), or share every point's "
@@ -381,6 +410,19 @@ def main():
             ibo_arr[1] - ibo_arr[0] if len(ibo_arr) > 1 else 0.0, args.n_trials, "_".join(str(v) for v in iters))
         save_to_csv(sdr_vs_ibo_rows(ibo_arr, stats), name, directory=args.out)
         print(f"sdr sweep done: {len(ibo_arr)} IBO points x {args.n_trials} trials in "
+              f"{time.perf_counter() - t0:.1f} s -> {args.out}")
+        return
+    if args.grid == "psd_vs_ibo":
+        if world > 1:
+            raise SystemExit("--grid psd_vs_ibo runs on one GPU")
+        t0 = time.perf_counter()
+        stats = spectrum_vs_ibo(link, ibo_arr, args.n_trials, args.seed)
+        name = "vs_ibo_%s_nant%d_nfft%d_nsc%d_ibo_min%d_max%d_step%1.2f_ntrials%d" % (
+            args.channel, args.n_ant, args.n_fft, args.n_sc, min(ibo_arr), max(ibo_arr),
+            ibo_arr[1] - ibo_arr[0] if len(ibo_arr) > 1 else 0.0, args.n_trials)
+        save_to_csv(oob_vs_ibo_rows(ibo_arr, stats), "oob_" + name, directory=args.out)
+        save_to_csv(psd_vs_ibo_rows(stats), "psd_" + name, directory=args.out)
+        print(f"psd sweep done: {len(ibo_arr)} IBO points x {args.n_trials} trials in "
               f"{time.perf_counter() - t0:.1f} s -> {args.out}")
         return
     t0 = time.perf_counter()
