@@ -189,7 +189,26 @@ double mimo_engine_last_kernel_ms(const mimo_engine* e);
 const char* mimo_engine_describe(const mimo_engine* e);
 void mimo_engine_destroy(mimo_engine* e);
 
-/* Fine seams (float64) ------------------------------------------------------------ */
+/* Fine seams (float64) ------------------------------------------------------------
+ * Caller-owned host arrays; complex data as (re, im) pairs.  Every seam checks its sizes
+ * host-side, before any allocation or HIP call: a value outside the ranges below is
+ * MIMO_EINVAL with a message in mimo_last_error(), and a size of 0 (n, batch, n_cols) is
+ * MIMO_OK with nothing read or written (mimo_count_bit_errors stores 0).
+ *   constel_size  a square power of two in [4, 4096]: 4, 16, 64, 256, 1024, 4096
+ *   n, batch      >= 0
+ *   n_fft         a power of two in [2, 8192]
+ *   n_sub_carr    even, in [2, n_fft - 2]
+ *   cp_len        in [0, n_fft]
+ *   n_ant         >= 1;  n_cols, n >= 0 (mimo_mrt_precode, mimo_combine: [n_ant][n] row-major)
+ *   kind, pa_kind MIMO_PA_NONE ... MIMO_PA_TOI
+ *   alpha         finite and non-zero (mimo_cnc_receive, mimo_cnc_receive_ex)
+ *   iters         n_iters >= 1 values, ascending, unique, >= 0
+ * mimo_qam_map: labels in [0, constel_size).  mimo_qam_llr: noise_var holds n values; out is
+ * [n][log2 constel_size], MSB first, +inf where the zero-bit sum underflows to 0.
+ * mimo_ofdm_tx: sym_iq [batch][n_sub_carr] -> td_iq [batch][n_fft + cp_len]; mimo_ofdm_rx the
+ * reverse.  mimo_awgn: out = in + sqrt(-ln u1) exp(j 2 pi u2) noise_std / sqrt(2) with
+ * (w0, w1, ., .) = Philox4x32-10 of counter (i_lo, counter_lo, 6, counter_hi ^ i_hi) under the
+ * key seed for element i, u1 = (w0 + 0.5) 2^-32, u2 = w1 2^-32. */
 int32_t mimo_qam_map(int32_t constel_size, const int32_t* labels, int64_t n, double* out_iq);
 int32_t mimo_qam_slice(int32_t constel_size, const double* in_iq, int64_t n, int32_t* labels_out);
 int32_t mimo_qam_llr(int32_t constel_size, const double* in_iq, int64_t n, const double* noise_var, double* llr_out);

@@ -559,6 +559,8 @@ def ofdm_tx(symbols, n_fft, n_sub_carr, cp_len):
 
 def ofdm_rx(td, n_fft, n_sub_carr, cp_len):
     t = np.asarray(td, np.complex128)
+    if t.ndim < 1 or t.shape[-1] != n_fft + cp_len:
+        raise ValueError("the last axis of td must have n_fft + cp_len samples")
     batch = t.size // (n_fft + cp_len)
     out = np.empty(batch * n_sub_carr, np.complex128)
     _check(lib().mimo_ofdm_rx(n_fft, n_sub_carr, cp_len, batch, _ptr(as_iq(t), ctypes.c_double),
@@ -588,6 +590,8 @@ def calc_alpha(ibo_db):
 
 def mrt_precode(h_sc):
     h = np.asarray(h_sc, np.complex128)
+    if h.ndim != 2:
+        raise ValueError("h_sc must be a 2-D [n_ant, n_cols] matrix")
     A, K = h.shape
     out = np.empty(A * K, np.complex128)
     _check(lib().mimo_mrt_precode(A, K, _ptr(as_iq(h), ctypes.c_double), _ptr(out.view(np.float64), ctypes.c_double)))
@@ -597,6 +601,8 @@ def mrt_precode(h_sc):
 def combine(h, y):
     h = np.asarray(h, np.complex128)
     y = np.asarray(y, np.complex128)
+    if h.ndim != 2 or h.shape != y.shape:
+        raise ValueError("h and y must be 2-D [n_ant, n] matrices of the same shape")
     A, K = h.shape
     out = np.empty(K, np.complex128)
     _check(lib().mimo_combine(A, K, _ptr(as_iq(h), ctypes.c_double), _ptr(as_iq(y), ctypes.c_double),
@@ -615,6 +621,8 @@ def awgn(x, noise_std, seed, counter):
 def count_bit_errors(a, b):
     a = _c(a, np.int64).reshape(-1)
     b = _c(b, np.int64).reshape(-1)
+    if a.size != b.size:
+        raise ValueError("a and b must have the same number of elements")
     out = np.zeros(1, np.int64)
     _check(lib().mimo_count_bit_errors(_ptr(a, ctypes.c_int64), _ptr(b, ctypes.c_int64), a.size,
                                        _ptr(out, ctypes.c_int64)))

@@ -29,6 +29,20 @@ int qam_l(int M) {
   return (L * L == M && pow2(M) && M >= 4 && M <= 4096) ? L : 0;
 }
 
+// Argument checks of the seams: host only, before any allocation or HIP call.
+const char* const kBadQam = "Constellation size must be a power of some number, only square QAM supported.";
+const char* const kBadFft = "n_fft must be a power of two in [2, 8192]";
+bool bad_fft(long F) { return !pow2(F) || F < 2 || F > 8192; }
+bool bad_sub_carr(long F, long S) { return S < 2 || S > F - 2 || S % 2; }
+// 0 = fine; else the message of what mimo_ofdm_tx / mimo_ofdm_rx reject
+const char* bad_ofdm(long F, long S, long cp, int64_t batch) {
+  if (bad_fft(F)) return kBadFft;
+  if (bad_sub_carr(F, S)) return "n_sub_carr must be even and in [2, n_fft - 2]";
+  if (cp < 0 || cp > F) return "cp_len must be in [0, n_fft]";
+  if (batch < 0) return "batch must be >= 0";
+  return nullptr;
+}
+
 // RAII device buffer
 struct DBuf {
   void* p = nullptr;
@@ -228,7 +242,7 @@ __global__ void k_sub(int64_t n, const double2* a, const double2* b, double2* ou
 dim3 grid_for(int64_t n) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 4096))); }
 
 int fft_device(int N, int64_t batch, int inverse, const double2* din, double2* dout) {
-  if (!pow2(N) || N < 2 || N > 8192) return sfail(MIMO_EINVAL, "n_fft must be a power of two in [2, 8192]");
+  if (bad_fft(N)) return sfail(MIMO_EINVAL, kBadFft);
   int logN = 0;
   while ((1 << logN) < N) ++logN;
   const size_t lds = sizeof(double2) * N;
@@ -254,7 +268,9 @@ extern "C" {
 
 int32_t mimo_qam_map(int32_t M, const int32_t* labels, int64_t n, double* out_iq) {
   const int L = qam_l(M);
-  if (!L) return sfail(MIMO_EINVAL, "Constellation size must be a power of some number, only square QAM supported.");
+  if (!L) return sfail(MIMO_EINVAL, kBadQam);
+  if (n < 0) return sfail(MIMO_EINVAL, "n must be >= 0");
+  if (n == 0) return MIMO_OK;
   int hb = 0;
   while ((1 << hb) < L) ++hb;
   DBuf dl, dout;
@@ -269,7 +285,9 @@ int32_t mimo_qam_map(int32_t M, const int32_t* labels, int64_t n, double* out_iq
 
 int32_t mimo_qam_slice(int32_t M, const double* in_iq, int64_t n, int32_t* labels_out) {
   const int L = qam_l(M);
-  if (!L) return sfail(MIMO_EINVAL, "Constellation size must be a power of some number, only square QAM supported.");
+  if (!L) return sfail(MIMO_EINVAL, kBadQam);
+  if (n < 0) return sfail(MIMO_EINVAL, "n must be >= 0");
+  if (n == 0) return MIMO_OK;
   int hb = 0;
   while ((1 << hb) < L) ++hb;
   DBuf din, dl;
@@ -284,7 +302,9 @@ int32_t mimo_qam_slice(int32_t M, const double* in_iq, int64_t n, int32_t* label
 
 int32_t mimo_qam_llr(int32_t M, const double* in_iq, int64_t n, const double* noise_var, double* llr_out) {
   const int L = qam_l(M);
-  if (!L) return sfail(MIMO_EINVAL, "Constellation size must be a power of some number, only square QAM supported.");
+  if (!L) return sfail(MIMO_EINVAL, kBadQam);
+  if (n < 0) return sfail(MIMO_EINVAL, "n must be >= 0");
+  if (n == 0) return MIMO_OK;
   int hb = 0;
   while ((1 << hb) < L) ++hb;
   const int nb = 2 * hb;
@@ -303,8 +323,9 @@ int32_t mimo_qam_llr(int32_t M, const double* in_iq, int64_t n, const double* no
 
 int32_t mimo_fft(int32_t N, int64_t batch, int32_t inverse, const double* in_iq, double* out_iq) {
   // checked before anything is allocated (the size below multiplies N and batch)
-  if (N <= 0 || !pow2(N) || N < 2 || N > 8192) return sfail(MIMO_EINVAL, "n_fft must be a power of two in [2, 8192]");
+  if (bad_fft(N)) return sfail(MIMO_EINVAL, kBadFft);
   if (batch < 0) return sfail(MIMO_EINVAL, "batch must be >= 0");
+  if (batch == 0) return MIMO_OK;
   DBuf din, dout;
   const size_t bytes = (size_t)N * batch * sizeof(double2);
   S_TRY(din.alloc(bytes));
@@ -316,8 +337,8 @@ int32_t mimo_fft(int32_t N, int64_t batch, int32_t inverse, const double* in_iq,
 }
 
 int32_t mimo_ofdm_tx(int32_t F, int32_t S, int32_t cp, int64_t batch, const double* sym_iq, double* td_iq) {
-  if (S < 2 || S > F - 2 || S % 2) return sfail(MIMO_EINVAL, "mod_symbols length must match n_sub_carr value");
-  if (cp < 0 || cp > F) return sfail(MIMO_EINVAL, "bad cp_len");
+  if (const char* m = bad_ofdm(F, S, cp, batch)) return sfail(MIMO_EINVAL, m);
+  if (batch == 0) return MIMO_OK;
   DBuf ds, dfd, dtd, dout;
   S_TRY(ds.alloc(batch * S * sizeof(double2)));
   S_TRY(dfd.alloc(batch * F * sizeof(double2)));
@@ -334,7 +355,8 @@ int32_t mimo_ofdm_tx(int32_t F, int32_t S, int32_t cp, int64_t batch, const doub
 }
 
 int32_t mimo_ofdm_rx(int32_t F, int32_t S, int32_t cp, int64_t batch, const double* td_iq, double* sym_iq) {
-  if (S < 2 || S > F - 2 || S % 2) return sfail(MIMO_EINVAL, "bad n_sub_carr");
+  if (const char* m = bad_ofdm(F, S, cp, batch)) return sfail(MIMO_EINVAL, m);
+  if (batch == 0) return MIMO_OK;
   DBuf din, dtd, dfd, ds;
   S_TRY(din.alloc(batch * (F + cp) * sizeof(double2)));
   S_TRY(dtd.alloc(batch * F * sizeof(double2)));
@@ -351,6 +373,8 @@ int32_t mimo_ofdm_rx(int32_t F, int32_t S, int32_t cp, int64_t batch, const doub
 
 int32_t mimo_pa(int32_t kind, double sat, double p, double toi, const double* in_iq, int64_t n, double* out_iq) {
   if (kind < MIMO_PA_NONE || kind > MIMO_PA_TOI) return sfail(MIMO_EINVAL, "unknown PA kind");
+  if (n < 0) return sfail(MIMO_EINVAL, "n must be >= 0");
+  if (n == 0) return MIMO_OK;
   DBuf din, dout;
   S_TRY(din.alloc(n * sizeof(double2)));
   S_TRY(dout.alloc(n * sizeof(double2)));
@@ -389,6 +413,9 @@ int32_t mimo_calc_alpha(const double* ibo_db, int64_t n, double* out) {
 }
 
 int32_t mimo_mrt_precode(int32_t A, int32_t K, const double* h_iq, double* p_iq) {
+  if (A < 1) return sfail(MIMO_EINVAL, "n_ant must be >= 1");
+  if (K < 0) return sfail(MIMO_EINVAL, "n_cols must be >= 0");
+  if (K == 0) return MIMO_OK;
   DBuf dh, dp;
   const size_t bytes = (size_t)A * K * sizeof(double2);
   S_TRY(dh.alloc(bytes));
@@ -401,6 +428,9 @@ int32_t mimo_mrt_precode(int32_t A, int32_t K, const double* h_iq, double* p_iq)
 }
 
 int32_t mimo_combine(int32_t A, int64_t K, const double* h_iq, const double* y_iq, double* out_iq) {
+  if (A < 1) return sfail(MIMO_EINVAL, "n_ant must be >= 1");
+  if (K < 0) return sfail(MIMO_EINVAL, "n must be >= 0");
+  if (K == 0) return MIMO_OK;
   DBuf dh, dy, dout;
   const size_t bytes = (size_t)A * K * sizeof(double2);
   S_TRY(dh.alloc(bytes));
@@ -415,6 +445,8 @@ int32_t mimo_combine(int32_t A, int64_t K, const double* h_iq, const double* y_i
 }
 
 int32_t mimo_awgn(uint64_t seed, uint64_t counter, int64_t n, double noise_std, const double* in_iq, double* out_iq) {
+  if (n < 0) return sfail(MIMO_EINVAL, "n must be >= 0");
+  if (n == 0) return MIMO_OK;
   DBuf din, dout;
   S_TRY(din.alloc(n * sizeof(double2)));
   S_TRY(dout.alloc(n * sizeof(double2)));
@@ -427,6 +459,11 @@ int32_t mimo_awgn(uint64_t seed, uint64_t counter, int64_t n, double noise_std, 
 }
 
 int32_t mimo_count_bit_errors(const int64_t* a, const int64_t* b, int64_t n, int64_t* out) {
+  if (n < 0) return sfail(MIMO_EINVAL, "n must be >= 0");
+  if (n == 0) {
+    *out = 0;
+    return MIMO_OK;
+  }
   DBuf da, db, dc;
   S_TRY(da.alloc(n * sizeof(int64_t)));
   S_TRY(db.alloc(n * sizeof(int64_t)));
@@ -451,7 +488,11 @@ int32_t mimo_cnc_receive_ex(int32_t M, int32_t F, int32_t S, int32_t pa_kind, do
                             double alpha, const int32_t* iters, int32_t n_iters, const double* in_sc_iq,
                             int32_t* labels_out, double* corrected_iq_out) {
   const int L = qam_l(M);
-  if (!L) return sfail(MIMO_EINVAL, "Constellation size must be a power of some number, only square QAM supported.");
+  if (!L) return sfail(MIMO_EINVAL, kBadQam);
+  if (bad_fft(F)) return sfail(MIMO_EINVAL, kBadFft);
+  if (bad_sub_carr(F, S)) return sfail(MIMO_EINVAL, "n_sub_carr must be even and in [2, n_fft - 2]");
+  if (pa_kind < MIMO_PA_NONE || pa_kind > MIMO_PA_TOI) return sfail(MIMO_EINVAL, "unknown PA kind");
+  if (alpha == 0 || !std::isfinite(alpha)) return sfail(MIMO_EINVAL, "alpha must be finite and non-zero");
   if (n_iters < 1) return sfail(MIMO_EINVAL, "empty iteration list");
   int hb = 0;
   while ((1 << hb) < L) ++hb;

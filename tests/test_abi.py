@@ -211,3 +211,159 @@ def test_fft_validates_sizes_before_any_allocation(n_fft, batch, msg):
     dp = ctypes.POINTER(ctypes.c_double)
     assert lib.mimo_fft(n_fft, batch, 0, buf.ctypes.data_as(dp), buf.ctypes.data_as(dp)) == -1  # MIMO_EINVAL
     assert msg in lib.mimo_last_error().decode()
+
+
+_dp = ctypes.POINTER(ctypes.c_double)
+_i32p = ctypes.POINTER(ctypes.c_int32)
+_i64p = ctypes.POINTER(ctypes.c_int64)
+
+
+def _seam_call(name, *args):
+    """Call a fine seam with dummy 8-element buffers for every pointer argument: the calls
+    below are all decided before the library looks at (or allocates for) any of them."""
+    lib = _engine.lib()
+    keep = []
+
+    def buf(ptr_type, dtype):
+        a = np.zeros(8, dtype)
+        keep.append(a)
+        return a.ctypes.data_as(ptr_type)
+
+    d, i32, i64 = (lambda: buf(_dp, np.float64)), (lambda: buf(_i32p, np.int32)), (lambda: buf(_i64p, np.int64))
+    if name == "mimo_qam_map":
+        M, n = args
+        return lib.mimo_qam_map(M, i32(), n, d())
+    if name == "mimo_qam_slice":
+        M, n = args
+        return lib.mimo_qam_slice(M, d(), n, i32())
+    if name == "mimo_qam_llr":
+        M, n = args
+        return lib.mimo_qam_llr(M, d(), n, d(), d())
+    if name == "mimo_fft":
+        F, batch = args
+        return lib.mimo_fft(F, batch, 0, d(), d())
+    if name in ("mimo_ofdm_tx", "mimo_ofdm_rx"):
+        F, S, cp, batch = args
+        return getattr(lib, name)(F, S, cp, batch, d(), d())
+    if name == "mimo_pa":
+        kind, n = args
+        return lib.mimo_pa(kind, 1.0, 2.0, 0.1, d(), n, d())
+    if name == "mimo_mrt_precode":
+        A, K = args
+        return lib.mimo_mrt_precode(A, K, d(), d())
+    if name == "mimo_combine":
+        A, K = args
+        return lib.mimo_combine(A, K, d(), d(), d())
+    if name == "mimo_awgn":
+        (n,) = args
+        return lib.mimo_awgn(1, 0, n, 1.0, d(), d())
+    if name == "mimo_count_bit_errors":
+        (n,) = args
+        out = np.full(1, -7, np.int64)
+        rc = lib.mimo_count_bit_errors(i64(), i64(), n, out.ctypes.data_as(_i64p))
+        return rc if rc or n else (rc, int(out[0]))
+    if name in ("mimo_cnc_receive", "mimo_cnc_receive_ex"):
+        M, F, S, kind, alpha = args
+        it = np.zeros(1, np.int32)
+        tail = (i32(), d()) if name.endswith("_ex") else (i32(),)
+        return getattr(lib, name)(M, F, S, kind, 1.0, 2.0, 0.1, alpha, it.ctypes.data_as(_i32p), 1, d(), *tail)
+    raise KeyError(name)
+
+
+_OFDM_REJECTS = [((128, 64, 4, -1), "batch must be >= 0"),
+                 ((0, 64, 4, 1), "n_fft must be a power of two"),
+                 ((-128, 64, 4, 1), "n_fft must be a power of two"),
+                 ((96, 64, 4, 1), "n_fft must be a power of two"),
+                 ((1, 2, 0, 1), "n_fft must be a power of two"),
+                 ((16384, 64, 4, 1), "n_fft must be a power of two"),
+                 ((128, 63, 4, 1), "n_sub_carr must be even"),
+                 ((128, 0, 4, 1), "n_sub_carr must be even"),
+                 ((128, -2, 4, 1), "n_sub_carr must be even"),
+                 ((128, 128, 4, 1), "n_sub_carr must be even"),
+                 ((2, 2, 0, 1), "n_sub_carr must be even"),
+                 ((128, 64, -1, 1), "cp_len must be in [0, n_fft]"),
+                 ((128, 64, 129, 1), "cp_len must be in [0, n_fft]")]
+_CNC_REJECTS = [((16, 0, 64, 1, 0.9), "n_fft must be a power of two"),
+                ((16, 100, 64, 1, 0.9), "n_fft must be a power of two"),
+                ((16, 16384, 64, 1, 0.9), "n_fft must be a power of two"),
+                ((16, 128, 63, 1, 0.9), "n_sub_carr must be even"),
+                ((16, 128, 0, 1, 0.9), "n_sub_carr must be even"),
+                ((16, 128, -4, 1, 0.9), "n_sub_carr must be even"),
+                ((16, 128, 128, 1, 0.9), "n_sub_carr must be even"),
+                ((16, 128, 64, -1, 0.9), "unknown PA kind"),
+                ((16, 128, 64, 4, 0.9), "unknown PA kind"),
+                ((16, 128, 64, 1, 0.0), "alpha must be finite and non-zero"),
+                ((16, 128, 64, 1, float("nan")), "alpha must be finite and non-zero"),
+                ((16, 128, 64, 1, float("inf")), "alpha must be finite and non-zero"),
+                ((8, 128, 64, 1, 0.9), "only square QAM supported")]
+
+
+@pytest.mark.parametrize("name,args,msg", [
+    ("mimo_qam_map", (16, -1), "n must be >= 0"),
+    ("mimo_qam_slice", (16, -1), "n must be >= 0"),
+    ("mimo_qam_llr", (16, -1), "n must be >= 0"),
+    ("mimo_qam_map", (8192, 4), "only square QAM supported"),
+    ("mimo_pa", (1, -1), "n must be >= 0"),
+    ("mimo_pa", (4, 4), "unknown PA kind"),
+    ("mimo_awgn", (-1,), "n must be >= 0"),
+    ("mimo_count_bit_errors", (-1,), "n must be >= 0"),
+    ("mimo_count_bit_errors", (-(1 << 62),), "n must be >= 0"),
+    ("mimo_mrt_precode", (0, 4), "n_ant must be >= 1"),
+    ("mimo_mrt_precode", (-3, 4), "n_ant must be >= 1"),
+    ("mimo_mrt_precode", (4, -1), "n_cols must be >= 0"),
+    ("mimo_combine", (0, 4), "n_ant must be >= 1"),
+    ("mimo_combine", (4, -1), "n must be >= 0"),
+] + [(f, a, m) for f in ("mimo_ofdm_tx", "mimo_ofdm_rx") for a, m in _OFDM_REJECTS]
+  + [(f, a, m) for f in ("mimo_cnc_receive", "mimo_cnc_receive_ex") for a, m in _CNC_REJECTS])
+def test_fine_seams_reject_bad_sizes_before_any_hip_call(name, args, msg):
+    """Every fine seam refuses a negative size, an n_fft / n_sub_carr / cp_len outside the
+    ranges of include/mimo_engine.h, a row count below 1, an unknown PA kind and a zero or
+    non-finite alpha with MIMO_EINVAL and a message -- on a machine without a GPU, so no
+    allocation and no HIP call comes first (mimo_ofdm_rx used to read in front of its buffer
+    for cp_len < 0; a negative n became a huge allocation)."""
+    lib = _engine.lib()
+    assert _seam_call(name, *args) == -1  # MIMO_EINVAL
+    assert msg in lib.mimo_last_error().decode()
+
+
+@pytest.mark.parametrize("name,args", [
+    ("mimo_qam_map", (16, 0)), ("mimo_qam_slice", (4096, 0)), ("mimo_qam_llr", (64, 0)), ("mimo_fft", (64, 0)),
+    ("mimo_ofdm_tx", (128, 64, 4, 0)), ("mimo_ofdm_rx", (128, 64, 0, 0)), ("mimo_ofdm_rx", (8192, 8190, 8192, 0)),
+    ("mimo_pa", (2, 0)), ("mimo_mrt_precode", (4, 0)), ("mimo_combine", (4, 0)), ("mimo_awgn", (0,)),
+])
+def test_fine_seams_accept_a_size_of_zero_without_a_gpu(name, args):
+    """A size of 0 is MIMO_OK with no HIP call (this machine has no GPU to answer one)."""
+    assert _seam_call(name, *args) == 0
+
+
+def test_count_bit_errors_of_nothing_is_zero_without_a_gpu():
+    assert _seam_call("mimo_count_bit_errors", 0) == (0, 0)
+
+
+def test_seam_wrappers_reject_mismatched_shapes():
+    """_engine's wrappers size the library's reads from one argument: a second array of
+    another shape, a last axis that is not n_fft + cp_len, or a matrix that is not 2-D is a
+    ValueError before the library is called (no GPU needed to see it)."""
+    z = np.zeros((4, 8), complex)
+    with pytest.raises(ValueError, match="same shape"):
+        _engine.combine(z, np.zeros((4, 9), complex))
+    with pytest.raises(ValueError, match="same shape"):
+        _engine.combine(z, np.zeros((3, 8), complex))
+    with pytest.raises(ValueError, match="2-D"):
+        _engine.combine(np.zeros(8, complex), np.zeros(8, complex))
+    with pytest.raises(ValueError, match="2-D"):
+        _engine.combine(np.zeros((2, 2, 2), complex), np.zeros((2, 2, 2), complex))
+    with pytest.raises(ValueError, match="2-D"):
+        _engine.mrt_precode(np.zeros(8, complex))
+    with pytest.raises(ValueError, match="2-D"):
+        _engine.mrt_precode(np.zeros((2, 2, 2), complex))
+    with pytest.raises(ValueError, match="same number of elements"):
+        _engine.count_bit_errors(np.zeros(8, int), np.zeros(9, int))
+    with pytest.raises(ValueError, match="n_fft \\+ cp_len"):
+        _engine.ofdm_rx(np.zeros((2, 131), complex), 128, 64, 4)
+    with pytest.raises(ValueError, match="n_fft \\+ cp_len"):
+        _engine.ofdm_rx(np.zeros(264, complex), 128, 64, 4)  # two symbols flattened
+    with pytest.raises(ValueError, match="n_fft \\+ cp_len"):
+        _engine.ofdm_rx(np.complex128(1.0), 128, 64, 4)
+    with pytest.raises(ValueError, match="n_sub_carr"):
+        _engine.ofdm_tx(np.zeros((2, 63), complex), 128, 64, 4)
