@@ -12,6 +12,8 @@
  *     mimo_engine_measure_points   the same trials with signal / distortion power sums (SDR, EVM)
  *     mimo_engine_spectrum_points  the same trials with the array's radiated PSD per FFT bin
  *                                  (out-of-band emission, Bussgang gain, efficiency)
+ *     mimo_engine_beam_points      the same trials with the signal, distortion and out-of-band power
+ *                                  the array radiates towards a list of probe positions (beampattern)
  *     mimo_engine_run_points    <- the drivers' grid loops over (IBO, Eb/N0), one launch
  *                                  for many points   main_mp_miso_cnc_constant_ber_req_ebn0_vs_ibo.py:100-215
  *   fine seams (float64 stage kernels, caller-owned host arrays)
@@ -183,8 +185,44 @@ int32_t mimo_engine_spectrum_points(mimo_engine* e, int32_t n_points, const mimo
                                     const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters,
                                     int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
                                     uint32_t* per_trial, double* spec_out, double* per_trial_spec);
+/* Beam mode (float64 engines): the trials, arguments and point rules of mimo_engine_run_points and
+ * the same counts, plus per point and per probe position q (n_probes 3-D points [m], the same for
+ * every point of the call) MIMO_BEAM_FIXED sums over what the array radiates towards q in the main
+ * transmission of every trial.  With G_q[a,k] = exp(+j 2 pi d_qa f_k / c) c / (4 pi d_qa f_k) the
+ * line-of-sight channel from antenna a to the probe at FFT bin k (d_qa their distance, f_k =
+ * carrier_freqs[k], gain 0 dB), Y_a and X_a as in the spectrum mode, R_q[k] = sum_a G_q[a,k] Y_a[k]
+ * the field at the probe and U_q[k] = sum_a G_q[a,k] X_a[k] its linear part's source:
+ *   [0] Py_in  = sum_{k in band} |R_q[k]|^2
+ *   [1] Py_oob = sum_{k not in band} |R_q[k]|^2      (DC and Nyquist included)
+ *   [2] Px     = sum_{k in band} |U_q[k]|^2
+ *   [3], [4] Re, Im of C = sum_{k in band} R_q[k] conj(U_q[k])
+ * from which the Bussgang gain C / Px towards q, the signal |C|^2 / Px, the uncorrelated in-band
+ * distortion Py_in - |C|^2 / Px and the out-of-band pattern follow.  MCNC re-transmissions and the
+ * CNC receiver's chain do not contribute.  beam_out: [n_points][n_probes][MIMO_BEAM_FIXED] totals
+ * (ADDED to; summed in a fixed order: equal calls return equal bits).  per_trial_beam: optional
+ * [sum n_trials][n_probes][MIMO_BEAM_FIXED] rows in point order, NULL to skip; they do not depend
+ * on how the call is split into launches.  The chains of one launch live in a device buffer of
+ * 32 n_ant n_fft bytes per trial and at most MIMO_BEAM_BUFFER_BYTES (1 GiB, a design figure) in
+ * all, so a beam launch holds floor(2^30 / (32 n_ant n_fft)) trials -- 256 at n_ant 64, n_fft
+ * 2048 -- or fewer: the per-trial rows of a launch (40 n_probes bytes per trial) fill at most
+ * MIMO_BEAM_ROWS_BYTES (256 MiB; 1,638 trials at 4,096 probes), and MIMO_MAX_LAUNCH_TRIALS lowers
+ * the count further.  MIMO_EINVAL, before any HIP call: a float32 engine,
+ * null probes or beam_out, n_probes outside [1, MIMO_BEAM_MAX_PROBES], a probe coordinate that is
+ * not finite, a probe at an antenna's position, a system of which one trial does not fit the
+ * buffer.  (Added within ABI 8: a library without it is reported by name.) */
+enum { MIMO_BEAM_FIXED = 5, MIMO_BEAM_MAX_PROBES = 4096 };
+#define MIMO_BEAM_BUFFER_BYTES (1ull << 30)
+#define MIMO_BEAM_ROWS_BYTES (256u << 20)
+int32_t mimo_beam_width(int32_t n_probes); /* n_probes MIMO_BEAM_FIXED; host only, EINVAL for a bad n_probes */
+int32_t mimo_engine_beam_points(mimo_engine* e, int32_t n_points, const mimo_point* points, const uint64_t* seeds,
+                                const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters,
+                                int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
+                                uint32_t* per_trial, const double* probes, int32_t n_probes, double* beam_out,
+                                double* per_trial_beam);
 /* Device time of the trial kernels of the last run, in ms (HIP events on the engine stream). */
 double mimo_engine_last_kernel_ms(const mimo_engine* e);
+/* ... and of the beamforming kernels of the last beam call (0 after any other call). */
+double mimo_engine_last_beam_ms(const mimo_engine* e);
 /* Which kernel instance the current config selects: "F=2048 T=128 slots=8 aligned ..." */
 const char* mimo_engine_describe(const mimo_engine* e);
 void mimo_engine_destroy(mimo_engine* e);

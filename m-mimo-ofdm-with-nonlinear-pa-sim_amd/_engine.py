@@ -71,7 +71,12 @@ SYMBOLS = {
     "mimo_engine_spectrum_points": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(MimoPoint), _u64p,
                                                      _u64p, _u64p, _i32p, ctypes.c_int32, ctypes.c_int32, _u64p, _u64p,
                                                      _u32p, _dp, _dp]),
+    "mimo_beam_width": (ctypes.c_int32, [ctypes.c_int32]),
+    "mimo_engine_beam_points": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(MimoPoint), _u64p,
+                                                 _u64p, _u64p, _i32p, ctypes.c_int32, ctypes.c_int32, _u64p, _u64p,
+                                                 _u32p, _dp, ctypes.c_int32, _dp, _dp]),
     "mimo_engine_last_kernel_ms": (ctypes.c_double, [ctypes.c_void_p]),
+    "mimo_engine_last_beam_ms": (ctypes.c_double, [ctypes.c_void_p]),
     "mimo_engine_describe": (ctypes.c_char_p, [ctypes.c_void_p]),
     "mimo_engine_destroy": (None, [ctypes.c_void_p]),
     "mimo_qam_map": (ctypes.c_int32, [ctypes.c_int32, _i32p, ctypes.c_int64, _dp]),
@@ -105,6 +110,7 @@ class EngineError(RuntimeError):
 ABI_VERSION = 8  # include/mimo_engine.h MIMO_ABI_VERSION
 MEAS_FIXED = 5   # include/mimo_engine.h MIMO_MEAS_FIXED
 SPEC_FIXED = 3   # include/mimo_engine.h MIMO_SPEC_FIXED
+BEAM_FIXED = 5   # include/mimo_engine.h MIMO_BEAM_FIXED
 
 
 def lib():
@@ -320,6 +326,80 @@ class SpectrumStats:
                 f"efficiency={self.efficiency:.4f})")
 
 
+class BeamStats:
+    """Beampattern of a beam call (mimo_engine_beam_points): per probe position the row
+    ``[Py_in, Py_oob, Px, Re C, Im C]`` of sums over trials and FFT bins -- the in-band and the
+    out-of-band power the array radiates towards the probe through a line-of-sight channel, the
+    power its precoded input would deliver there, and their in-band correlation.  Every figure
+    below is an array with one entry per probe.  ``a + b`` pools two measurements."""
+
+    def __init__(self, rows, n_trials=None):
+        self.rows = np.array(rows, np.float64)
+        if self.rows.ndim != 2 or self.rows.shape[0] < 1 or self.rows.shape[1] != BEAM_FIXED:
+            raise ValueError(f"beam rows are [n_probes, {BEAM_FIXED}]")
+        self.n_trials = None if n_trials is None else int(n_trials)
+
+    n_probes = property(lambda self: self.rows.shape[0])
+    power_inband = property(lambda self: self.rows[:, 0].copy())
+    power_oob = property(lambda self: self.rows[:, 1].copy())
+    input_power = property(lambda self: self.rows[:, 2].copy())
+    c = property(lambda self: self.rows[:, 3] + 1j * self.rows[:, 4])
+
+    @property
+    def gain(self):
+        """C / Px: the array's Bussgang gain towards each probe (inf where no input power arrives)."""
+        out = np.full(self.n_probes, complex(np.inf))
+        np.divide(self.c, self.rows[:, 2], out=out, where=self.rows[:, 2] > 0)
+        return out
+
+    @property
+    def signal(self):
+        """|C|^2 / Px: the in-band power correlated with the precoded input."""
+        out = np.full(self.n_probes, np.inf)
+        np.divide(self.rows[:, 3] ** 2 + self.rows[:, 4] ** 2, self.rows[:, 2], out=out, where=self.rows[:, 2] > 0)
+        return out
+
+    @property
+    def distortion(self):
+        """Py_in - |C|^2 / Px: the in-band power uncorrelated with the input."""
+        return self.rows[:, 0] - self.signal
+
+    @property
+    def sdr_db(self):
+        """signal over distortion, in dB; inf where rounding leaves no distortion."""
+        return _ratio_db(self.signal, self.distortion)
+
+    _PATTERNS = ("signal", "distortion", "power_oob", "power_inband", "input_power")
+
+    def _pattern(self, which):
+        if which not in self._PATTERNS:
+            raise ValueError("which must be signal, distortion, power_oob, power_inband or input_power")
+        return getattr(self, which)
+
+    def directivity(self, which="signal"):
+        """max / mean over the probes of ``signal``, ``distortion``, ``power_oob``, ``power_inband`` or
+        ``input_power``."""
+        v = self._pattern(which)
+        return float(v.max() / v.mean())
+
+    def pattern_db(self, which="signal", ref=None):
+        """The pattern ``which`` (as for ``directivity``) over ``ref`` in dB, per probe; ``ref``
+        defaults to the mean ``signal`` over the probes.  -inf where nothing is radiated."""
+        return _ratio_db(self._pattern(which), float(np.mean(self.signal)) if ref is None else ref)
+
+    def __add__(self, other):
+        if not isinstance(other, BeamStats):
+            return NotImplemented
+        if other.rows.shape != self.rows.shape:
+            raise ValueError("beampatterns over different probe lists cannot be pooled")
+        n = None if self.n_trials is None or other.n_trials is None else self.n_trials + other.n_trials
+        return BeamStats(self.rows + other.rows, n)
+
+    def __repr__(self):
+        return (f"BeamStats(n_probes={self.n_probes}, signal directivity={self.directivity('signal'):.3f}, "
+                f"distortion directivity={self.directivity('distortion'):.3f})")
+
+
 class Engine:
     """One configured system (the deep-copied objects of a ``Link``) on one GPU."""
 
@@ -490,9 +570,59 @@ class Engine:
                                                        per_trial)
         return err[0], bits[0], spec[0], pt, ps
 
+    def beam_points(self, points, seeds, first_trials, n_trials, iters, probes, incl_clean=False, per_trial=False):
+        """run_points in beam mode (mimo_engine_beam_points; float64 engines): the same trials and
+        counts, and per point and probe position (``probes``: [n_probes, 3] in metres, the same for
+        every point) the row ``[Py_in, Py_oob, Px, Re C, Im C]``.
+        -> (err[P, n_idx], bits[P, n_idx], beam[P, n_probes, 5], per-trial counts [sum n_trials, n_idx]
+        or None, per-trial rows [sum n_trials, n_probes, 5] or None); BeamStats(beam[i])."""
+        P = len(points)
+        arr = (MimoPoint * max(1, P))()
+        for i, pt in enumerate(points):
+            arr[i] = pt if isinstance(pt, MimoPoint) else self.make_point(**pt)
+        it = _c(sorted(set(int(i) for i in iters)), np.int32)
+        n_idx = len(it) + (1 if incl_clean else 0)
+        pr = _c(probes, np.float64)
+        if pr.ndim != 2 or pr.shape[1] != 3:
+            raise ValueError("probes must be [n_probes, 3]")
+        nq = pr.shape[0]
+        sd = _c(np.asarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], dtype=np.uint64).reshape(-1), np.uint64)
+        ft = _c(np.asarray(first_trials, dtype=np.uint64).reshape(-1), np.uint64)
+        nt = _c(np.asarray(n_trials, dtype=np.uint64).reshape(-1), np.uint64)
+        if not (len(sd) == len(ft) == len(nt) == P):
+            raise ValueError("points, seeds, first_trials and n_trials must have the same length")
+        err = np.zeros((P, n_idx), np.uint64)
+        bits = np.zeros((P, n_idx), np.uint64)
+        beam = np.zeros((P, nq, BEAM_FIXED), np.float64)
+        pt = np.zeros((int(nt.sum()), n_idx), np.uint32) if per_trial else None
+        pb = np.zeros((int(nt.sum()), nq, BEAM_FIXED), np.float64) if per_trial else None
+        _check(self._L.mimo_engine_beam_points(
+            self._h, P, arr, _ptr(sd, ctypes.c_uint64), _ptr(ft, ctypes.c_uint64), _ptr(nt, ctypes.c_uint64),
+            _ptr(it, ctypes.c_int32), len(it), int(bool(incl_clean)), _ptr(err, ctypes.c_uint64),
+            _ptr(bits, ctypes.c_uint64), _ptr(pt, ctypes.c_uint32) if pt is not None else None,
+            _ptr(pr, ctypes.c_double), nq, _ptr(beam, ctypes.c_double),
+            _ptr(pb, ctypes.c_double) if pb is not None else None))
+        return err, bits, beam, pt, pb
+
+    def beam(self, seed, first_trial, n_trials, iters, probes, incl_clean=False, per_trial=False, point=None):
+        """One point (the last set_point's, or ``point``: make_point keywords / MimoPoint).
+        -> (err[n_idx], bits[n_idx], beam[n_probes, 5], per-trial counts or None, per-trial rows or None)."""
+        if point is None:
+            point = getattr(self, "_point", None)
+            if point is None:
+                raise EngineError("mimo_engine_set_point was not called")
+        err, bits, beam, pt, pb = self.beam_points([point], [seed], [first_trial], [n_trials], iters, probes,
+                                                   incl_clean, per_trial)
+        return err[0], bits[0], beam[0], pt, pb
+
     @property
     def kernel_ms(self):
         return self._L.mimo_engine_last_kernel_ms(self._h)
+
+    @property
+    def beam_kernel_ms(self):
+        """Device time of the beamforming kernels of the last beam call."""
+        return self._L.mimo_engine_last_beam_ms(self._h)
 
     def describe(self):
         return self._L.mimo_engine_describe(self._h).decode()

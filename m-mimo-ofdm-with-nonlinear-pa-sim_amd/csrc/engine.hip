@@ -19,6 +19,9 @@
 #include "../../include/mimo_engine.h"
 #include "trial_launch.h"
 #include "host_tables.h"
+#ifndef MIMO_ONLY_F  // the single-size diagnostic builds link neither beam instances nor beam.o
+#include "beam.h"
+#endif
 
 namespace {
 
@@ -144,6 +147,19 @@ struct mimo_engine {
   size_t spec_cap = 0;
   double* d_spart = nullptr;              // [launch slices][n_spec]
   size_t spart_cap = 0;
+  // beam calls (mimo_engine_beam_points): the beam instances' cells of one launch (at most the
+  // beam buffer's bytes: it bounds the trials of a beam launch), the probe geometry, and the
+  // same pair of per-trial rows and slice partials, rows of n_probes MIMO_BEAM_FIXED
+  double* d_bcell = nullptr;              // [2][launch blocks][A][F] complex128
+  size_t bcell_cap = 0;
+  double* d_bgeo = nullptr;               // dist [n_probes][A] | 1 / dist [n_probes][A] | f / c [F]
+  size_t bgeo_cap = 0;
+  double* d_beam = nullptr;               // [launch blocks][n_probes][MIMO_BEAM_FIXED]
+  size_t beam_cap = 0;
+  double* d_bpart = nullptr;              // [launch slices][n_probes][MIMO_BEAM_FIXED]
+  size_t bpart_cap = 0;
+  hipEvent_t ev2 = nullptr;               // after the beamforming kernel of a launch
+  double last_beam_ms = 0.0;
   // per-launch tables in one device blob, filled by one copy from a pinned host buffer:
   // TrialParams<R>[segments] | uint32 block offsets [segments + 1] |
   // uint32 reduction-slice starts [slices + 1] (<= kSlice trials, one point each) | int32 point of slice [slices]
@@ -268,6 +284,33 @@ hipError_t launch_spec(const mimo::InstanceKey& k, dim3 grid, hipStream_t st, co
   return hipSuccess;
 }
 
+// The beam instance of the key (float64 only); cells: [2][grid.x][A][F] complex128.
+hipError_t launch_beam_inst(const mimo::InstanceKey& k, dim3 grid, hipStream_t st, const mimo::TrialParams<double>& p,
+                            double* cells, bool* found) {
+  *found = false;
+#ifndef MIMO_ONLY_F  // the single-size diagnostic builds link no beam instances
+  switch (k.F) {
+    case 128: return mimo::launch_trial_F128_f64_beam(k, grid, st, p, found, nullptr, cells);
+    case 256: return mimo::launch_trial_F256_f64_beam(k, grid, st, p, found, nullptr, cells);
+    case 512: return mimo::launch_trial_F512_f64_beam(k, grid, st, p, found, nullptr, cells);
+    case 1024: return mimo::launch_trial_F1024_f64_beam(k, grid, st, p, found, nullptr, cells);
+    case 2048: return mimo::launch_trial_F2048_f64_beam(k, grid, st, p, found, nullptr, cells);
+    case 4096: return mimo::launch_trial_F4096_f64_beam(k, grid, st, p, found, nullptr, cells);
+    case 8192: return mimo::launch_trial_F8192_f64_beam(k, grid, st, p, found, nullptr, cells);
+    default: break;
+  }
+#endif
+  return hipSuccess;
+}
+
+// A beam call's probes, checked and turned into the beamforming kernel's tables by the caller
+// (mimo_engine_beam_points): geo = dist [n_probes][A] | 1 / dist [n_probes][A] | f / c [F].
+struct BeamCall {
+  int n_probes;
+  std::vector<double> geo;
+  uint64_t max_trials;  // of one launch: the cells of so many trials fit the beam buffer, their rows the rows buffer
+};
+
 int validate_config(const mimo_config* c) {
   if (!c) return fail(MIMO_EINVAL, "null config");
   if (!is_pow2(c->n_fft) || c->n_fft < 128 || c->n_fft > 8192)
@@ -375,6 +418,7 @@ int ensure_device(mimo_engine* e) {
   HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
   HIP_TRY(hipEventCreate(&e->ev0));
   HIP_TRY(hipEventCreate(&e->ev1));
+  HIP_TRY(hipEventCreate(&e->ev2));
   const int F = e->cfg.n_fft, S = e->cfg.n_sub_carr, A = e->cfg.n_ant;
   // the FFT tables (host_tables.h): the team FFT's per team size, the split FFT's in place of
   // the fp64 team's where the instance runs it, the wave-split FFT's where used
@@ -527,10 +571,14 @@ namespace {
 // spec (mimo_engine_spectrum_points): meas_out / per_trial_meas are the spectrum rows instead, of
 // n_fft + MIMO_SPEC_FIXED sums; the spectrum instance runs, reduce_spec forms the slice partials,
 // and a launch holds no more trials than its rows fit MIMO_SPEC_BUFFER_BYTES.
+// beam (mimo_engine_beam_points): the rows are n_probes MIMO_BEAM_FIXED sums; the beam instance
+// runs and fills the launch's cells, the beamforming kernel (beam.hip) forms the per-trial rows
+// from them, reduce_spec the slice partials; a launch holds beam->max_trials trials at most.
 int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64_t* seeds,
                const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters, int32_t n_iters,
                int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out, uint32_t* per_trial,
-               double* meas_out = nullptr, double* per_trial_meas = nullptr, bool spec = false) {
+               double* meas_out = nullptr, double* per_trial_meas = nullptr, bool spec = false,
+               const BeamCall* beam = nullptr) {
   if (n_points < 0) return fail(MIMO_EINVAL, "n_points must be >= 0");
   if (n_iters < 1 || !iters) return fail(MIMO_EINVAL, "at least one iteration index is required");
   uint32_t rec_mask = 0;
@@ -546,7 +594,9 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
   if (!pts || !seeds || !first_trial || !n_trials) return fail(MIMO_EINVAL, "null point arrays");
   const int n_idx = n_iters + (incl_clean ? 1 : 0);
   const mimo_config& c = e->cfg;
-  const int n_meas = spec ? c.n_fft + MIMO_SPEC_FIXED : MIMO_MEAS_FIXED + n_idx;  // row width of either mode
+  const int n_meas = beam   ? beam->n_probes * MIMO_BEAM_FIXED  // row width of the mode
+                     : spec ? c.n_fft + MIMO_SPEC_FIXED
+                            : MIMO_MEAS_FIXED + n_idx;
   const bool csi = pts[0].csi_eps >= 0;
   for (int i = 0; i < n_points; ++i) {
     if (int rc = validate_point(e, &pts[i])) return rc;
@@ -593,10 +643,11 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
     if (v >= 1 && v < kChunk) kChunk = v;
   }
   if (spec) kChunk = std::min<uint64_t>(kChunk, MIMO_SPEC_BUFFER_BYTES / (sizeof(double) * (size_t)n_meas));
-  double*& d_rows = spec ? e->d_spec : e->d_meas;  // per-trial rows and slice partials of the mode
-  size_t& rows_cap = spec ? e->spec_cap : e->meas_cap;
-  double*& d_part = spec ? e->d_spart : e->d_mpart;
-  size_t& part_cap = spec ? e->spart_cap : e->mpart_cap;
+  if (beam) kChunk = std::min<uint64_t>(kChunk, beam->max_trials);
+  double*& d_rows = beam ? e->d_beam : spec ? e->d_spec : e->d_meas;  // per-trial rows and slice partials of the mode
+  size_t& rows_cap = beam ? e->beam_cap : spec ? e->spec_cap : e->meas_cap;
+  double*& d_part = beam ? e->d_bpart : spec ? e->d_spart : e->d_mpart;
+  size_t& part_cap = beam ? e->bpart_cap : spec ? e->spart_cap : e->mpart_cap;
   struct Seg {
     int point;
     uint64_t first, n;
@@ -637,13 +688,20 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
     if (int rc = ensure_cap(d_part, part_cap, std::max<size_t>(1, max_sl * n_meas))) return rc;
     mpart.resize(tot_sl * n_meas);
     mpart_point.reserve(tot_sl);
+    if (beam) {
+      const size_t cells = 2 * max_blocks * (size_t)c.n_ant * (size_t)c.n_fft * 2;  // doubles
+      if (int rc = ensure_cap(e->d_bcell, e->bcell_cap, std::max<size_t>(2, cells))) return rc;
+      if (int rc = ensure_cap(e->d_bgeo, e->bgeo_cap, beam->geo.size())) return rc;
+      HIP_TRY(hipMemcpyAsync(e->d_bgeo, beam->geo.data(), sizeof(double) * beam->geo.size(), hipMemcpyHostToDevice,
+                             e->stream));
+    }
   }
   size_t mpart_done = 0;
   if (int rc = ensure_cap(e->d_counts, e->counts_cap, (size_t)(1ull << 20) * n_idx)) return rc;
   if (int rc = ensure_cap(e->d_tot, e->tot_cap, (size_t)n_points * n_idx)) return rc;
   const size_t max_slices = max_seg + (size_t)(kChunk / kSlice) + 1;
   HIP_TRY(hipMemsetAsync(e->d_tot, 0, sizeof(unsigned long long) * n_points * n_idx, e->stream));
-  double ms_total = 0.0;
+  double ms_total = 0.0, beam_ms_total = 0.0;
   uint64_t rows_done = 0;
 
   auto run_as = [&](auto zero) -> int {
@@ -737,7 +795,8 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
       bool found = false;
       hipError_t le = hipSuccess;
       if constexpr (F64) {
-        le = spec       ? launch_spec(key, dim3(nb), e->stream, kp, d_rows, &found)
+        le = beam       ? launch_beam_inst(key, dim3(nb), e->stream, kp, e->d_bcell, &found)
+             : spec     ? launch_spec(key, dim3(nb), e->stream, kp, d_rows, &found)
              : meas_out ? launch_meas(key, dim3(nb), e->stream, kp, d_rows, &found)
                         : launch(key, dim3(nb), e->stream, kp, &found);
       } else {
@@ -746,6 +805,16 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
       if (!found) return fail(MIMO_ENOKERNEL, std::string("no kernel instance for ") + buf);
       if (le != hipSuccess) return fail(MIMO_EHIP, std::string("trial kernel launch: ") + hipGetErrorString(le));
       HIP_TRY(hipEventRecord(e->ev1, e->stream));
+#ifndef MIMO_ONLY_F  // (the single-size diagnostic builds found no beam instance above)
+      if (beam) {
+        const size_t na = (size_t)beam->n_probes * (size_t)c.n_ant;
+        const hipError_t be = mimo::launch_beam(e->stream, e->d_bcell, e->d_bgeo, e->d_bgeo + na, e->d_bgeo + 2 * na,
+                                                (int)nb, c.n_ant, c.n_fft, c.n_sub_carr, beam->n_probes, d_rows);
+        if (be != hipSuccess)
+          return fail(MIMO_EHIP, std::string("beamforming kernel launch: ") + hipGetErrorString(be));
+        HIP_TRY(hipEventRecord(e->ev2, e->stream));
+      }
+#endif
       hipLaunchKernelGGL(reduce_counts, dim3((unsigned)nsl, n_idx), dim3(256), 0, e->stream, e->d_counts,
                          reinterpret_cast<const uint32_t*>(e->d_blob + o_slice),
                          reinterpret_cast<const int32_t*>(e->d_blob + o_pof), n_idx, e->d_tot);
@@ -754,7 +823,7 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
         HIP_TRY(hipMemcpyAsync(per_trial + rows_done * n_idx, e->d_counts, (size_t)nb * n_idx * sizeof(uint32_t),
                                hipMemcpyDeviceToHost, e->stream));
       if (meas_out) {
-        if (spec)
+        if (spec || beam)
           hipLaunchKernelGGL(reduce_spec,
                              dim3((unsigned)nsl, (unsigned)((n_meas + kReduceSpecThreads - 1) / kReduceSpecThreads)),
                              dim3(kReduceSpecThreads), 0, e->stream, d_rows,
@@ -777,6 +846,11 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
       float ms = 0.f;
       HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
       ms_total += ms;
+      if (beam) {
+        HIP_TRY(hipEventSynchronize(e->ev2));
+        HIP_TRY(hipEventElapsedTime(&ms, e->ev1, e->ev2));
+        beam_ms_total += ms;
+      }
     }
     return MIMO_OK;
   };
@@ -800,6 +874,7 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
     for (size_t i = 0; i < ptot.size(); ++i) meas_out[i] += ptot[i];
   }
   e->last_ms = ms_total;
+  e->last_beam_ms = beam_ms_total;
   return MIMO_OK;
 }
 
@@ -863,7 +938,66 @@ int32_t mimo_engine_spectrum_points(mimo_engine* e, int32_t n_points, const mimo
                     per_trial, spec_out, per_trial_spec, true);
 }
 
+int32_t mimo_beam_width(int32_t n_probes) {
+  if (n_probes < 1 || n_probes > MIMO_BEAM_MAX_PROBES)
+    return fail(MIMO_EINVAL, "n_probes must be in [1, " + std::to_string(MIMO_BEAM_MAX_PROBES) + "]");
+  return n_probes * MIMO_BEAM_FIXED;
+}
+
+int32_t mimo_engine_beam_points(mimo_engine* e, int32_t n_points, const mimo_point* points, const uint64_t* seeds,
+                                const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters,
+                                int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
+                                uint32_t* per_trial, const double* probes, int32_t n_probes, double* beam_out,
+                                double* per_trial_beam) {
+  if (!e) return fail(MIMO_EINVAL, "null engine");
+  if (e->cfg.precision != MIMO_PREC_F64)
+    return fail(MIMO_EINVAL, "beam needs a float64 engine (no float32 beam instances are built)");
+  if (!probes) return fail(MIMO_EINVAL, "null probes");
+  if (!beam_out) return fail(MIMO_EINVAL, "null beam_out");
+  if (mimo_beam_width(n_probes) < 0) return MIMO_EINVAL;
+  const int A = e->cfg.n_ant, F = e->cfg.n_fft;
+  BeamCall bc;
+  bc.n_probes = n_probes;
+  // the launch's cells: Y and X of every antenna and bin, complex128
+  const uint64_t per_trial_bytes = 2ull * (uint64_t)A * (uint64_t)F * 16ull;
+  uint64_t buffer = MIMO_BEAM_BUFFER_BYTES;
+  if (const char* env = std::getenv("MIMO_BEAM_BUFFER_BYTES")) {  // lowers it, for tests of the splitting
+    const uint64_t v = std::strtoull(env, nullptr, 10);
+    if (v >= 1 && v < buffer) buffer = v;
+  }
+  bc.max_trials = buffer / per_trial_bytes;
+  if (bc.max_trials < 1)
+    return fail(MIMO_EINVAL, "one trial's beam cells (" + std::to_string(per_trial_bytes) + " B at n_ant " +
+                                 std::to_string(A) + ", n_fft " + std::to_string(F) +
+                                 ") do not fit the beam buffer of " + std::to_string(buffer) + " B");
+  // ... and its per-trial rows, as for the spectrum mode (one trial's 40 n_probes bytes always fit)
+  bc.max_trials = std::min<uint64_t>(
+      bc.max_trials, MIMO_BEAM_ROWS_BYTES / (sizeof(double) * (uint64_t)MIMO_BEAM_FIXED * (uint64_t)n_probes));
+  const size_t na = (size_t)n_probes * (size_t)A;
+  bc.geo.resize(2 * na + (size_t)F);
+  for (int q = 0; q < n_probes; ++q) {
+    for (int i = 0; i < 3; ++i)
+      if (!std::isfinite(probes[3 * q + i])) return fail(MIMO_EINVAL, "probe " + std::to_string(q) + " is not finite");
+    for (int a = 0; a < A; ++a) {
+      const double dx = e->tx_pos[3 * a] - probes[3 * q], dy = e->tx_pos[3 * a + 1] - probes[3 * q + 1],
+                   dz = e->tx_pos[3 * a + 2] - probes[3 * q + 2];
+      // the squares rounded one by one and summed in this order, as oracle.refmath.los_channel does
+      const double xx = dx * dx, yy = dy * dy, zz = dz * dz;
+      const double d = std::sqrt((xx + yy) + zz);
+      if (!(d > 0) || !std::isfinite(d))
+        return fail(MIMO_EINVAL, "probe " + std::to_string(q) + " coincides with antenna " + std::to_string(a) +
+                                     " (or is too far): no LoS channel");
+      bc.geo[(size_t)q * A + a] = d;
+      bc.geo[na + (size_t)q * A + a] = 1.0 / d;
+    }
+  }
+  for (int k = 0; k < F; ++k) bc.geo[2 * na + k] = e->freqs[k] / kSpeedOfLight;
+  return run_points(e, n_points, points, seeds, first_trial, n_trials, iters, n_iters, incl_clean, err_out, bits_out,
+                    per_trial, beam_out, per_trial_beam, false, &bc);
+}
+
 double mimo_engine_last_kernel_ms(const mimo_engine* e) { return e ? e->last_ms : 0.0; }
+double mimo_engine_last_beam_ms(const mimo_engine* e) { return e ? e->last_beam_ms : 0.0; }
 
 const char* mimo_engine_describe(const mimo_engine* e) {
   if (!e) return "";
@@ -901,10 +1035,15 @@ void mimo_engine_destroy(mimo_engine* e) {
     if (e->d_mpart) (void)hipFree(e->d_mpart);
     if (e->d_spec) (void)hipFree(e->d_spec);
     if (e->d_spart) (void)hipFree(e->d_spart);
+    if (e->d_bcell) (void)hipFree(e->d_bcell);
+    if (e->d_bgeo) (void)hipFree(e->d_bgeo);
+    if (e->d_beam) (void)hipFree(e->d_beam);
+    if (e->d_bpart) (void)hipFree(e->d_bpart);
     if (e->d_blob) (void)hipFree(e->d_blob);
     if (e->h_blob) (void)hipHostFree(e->h_blob);
     (void)hipEventDestroy(e->ev0);
     (void)hipEventDestroy(e->ev1);
+    (void)hipEventDestroy(e->ev2);
     (void)hipStreamDestroy(e->stream);
   }
   delete e;

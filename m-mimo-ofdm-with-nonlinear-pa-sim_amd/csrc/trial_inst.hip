@@ -1,7 +1,8 @@
 // Instantiates the fused trial kernel for one FFT size and arithmetic type
 // (compiled once per -DINST_F=<size> -DINST_F64=<0|1>), and once more per size with
 // -DINST_F64=1 -DINST_MEAS=1 for the measure instances (trial_kernel.h MIMO_MEAS_INST) and with
-// -DINST_F64=1 -DINST_SPEC=1 for the spectrum instances (MIMO_SPEC_INST).
+// -DINST_F64=1 -DINST_SPEC=1 for the spectrum instances (MIMO_SPEC_INST) and with
+// -DINST_F64=1 -DINST_BEAM=1 for the beam instances (MIMO_BEAM_INST).
 #include <type_traits>
 
 #ifndef INST_F
@@ -24,6 +25,13 @@
 #error "spectrum instances are float64 only, and objects of their own"
 #endif
 #define MIMO_SPEC_INST INST_SPEC
+#ifndef INST_BEAM
+#define INST_BEAM 0
+#endif
+#if INST_BEAM && (!INST_F64 || INST_MEAS || INST_SPEC)
+#error "beam instances are float64 only, and objects of their own"
+#endif
+#define MIMO_BEAM_INST INST_BEAM
 
 #include "trial_launch.h"
 
@@ -69,7 +77,8 @@ constexpr Profile profile_for(int T, bool aligned, int ch) {
 // attr != null: no launch, the instance's attributes instead (its static LDS, which the
 // engine checks with the CSI table's dynamic LDS against the device limit before a launch).
 // meas: the measure instances' per-trial rows [grid.x][kMeasFixed + n_idx], the spectrum
-// instances' [grid.x][kF + kSpecFixed] (unused otherwise).
+// instances' [grid.x][kF + kSpecFixed], the beam instances' cells [2][grid.x][A][kF] complex128
+// (unused otherwise).
 template <int T, int NSLOT, bool AL, int CH, bool CSI>
 hipError_t go(dim3 grid, hipStream_t st, const TrialParams<Real>& p, hipFuncAttributes* attr, double* meas) {
   constexpr Profile pr = profile_for(T, AL, CH);
@@ -77,13 +86,15 @@ hipError_t go(dim3 grid, hipStream_t st, const TrialParams<Real>& p, hipFuncAttr
   auto* kern = &trial_kernel_meas<Real, kF, T, NSLOT, AL, CH, CSI, pr.minw, pr.nbuf, pr.symw_lds>;
 #elif INST_SPEC
   auto* kern = &trial_kernel_spec<Real, kF, T, NSLOT, AL, CH, CSI, pr.minw, pr.nbuf, pr.symw_lds>;
+#elif INST_BEAM
+  auto* kern = &trial_kernel_beam<Real, kF, T, NSLOT, AL, CH, CSI, pr.minw, pr.nbuf, pr.symw_lds>;
 #else
   auto* kern = &trial_kernel<Real, kF, T, NSLOT, AL, CH, CSI, pr.minw, pr.nbuf, pr.symw_lds>;
 #endif
   if (attr) return hipFuncGetAttributes(attr, reinterpret_cast<const void*>(kern));
   // CSI: the per-antenna power table is dynamic LDS, A reals (trial_kernel pw_csi)
   const size_t dyn = CSI ? sizeof(Real) * (size_t)p.n_ant : 0;
-#if INST_MEAS || INST_SPEC
+#if INST_MEAS || INST_SPEC || INST_BEAM
   hipLaunchKernelGGL(kern, grid, dim3(T), dyn, st, p, meas);
 #else
   hipLaunchKernelGGL(kern, grid, dim3(T), dyn, st, p);
@@ -139,6 +150,9 @@ hipError_t by_team(const InstanceKey& k, dim3 grid, hipStream_t st, const TrialP
 #elif INST_SPEC
 #define MIMO_LAUNCH_NAME MIMO_CAT(MIMO_CAT(launch_trial_F, INST_F), _f64_spec)
 #define MIMO_LAUNCH_MEAS_ARG , double* meas
+#elif INST_BEAM
+#define MIMO_LAUNCH_NAME MIMO_CAT(MIMO_CAT(launch_trial_F, INST_F), _f64_beam)
+#define MIMO_LAUNCH_MEAS_ARG , double* meas
 #elif INST_F64
 #define MIMO_LAUNCH_NAME MIMO_CAT(MIMO_CAT(launch_trial_F, INST_F), _f64)
 #else
@@ -149,7 +163,7 @@ hipError_t by_team(const InstanceKey& k, dim3 grid, hipStream_t st, const TrialP
 #endif
 hipError_t MIMO_LAUNCH_NAME(const InstanceKey& k, dim3 grid, hipStream_t st, const TrialParams<Real>& p, bool* found,
                             hipFuncAttributes* attr MIMO_LAUNCH_MEAS_ARG) {
-#if !INST_MEAS && !INST_SPEC
+#if !INST_MEAS && !INST_SPEC && !INST_BEAM
   double* const meas = nullptr;
 #endif
   *found = false;

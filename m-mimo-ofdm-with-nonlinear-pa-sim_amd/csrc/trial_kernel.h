@@ -72,6 +72,18 @@ constexpr int kMeasFixed = 5;  // MIMO_MEAS_FIXED
 #endif
 constexpr int kSpecFixed = 3;  // MIMO_SPEC_FIXED
 
+// Beam instances (trial_inst.hip with -DINST_BEAM=1, float64 only): the same trial, the same
+// counts, and the main array pass hands every antenna's chain to the beamforming kernel
+// (beam.hip; include/mimo_engine.h mimo_engine_beam_points) through a per-launch buffer of
+// complex128 cells: [grid.x][A][F] of the chain output's registers d (Y_a = d / sqrt(F)), then
+// [grid.x][A][F] of the precoder input where Slots::scatter placed it (X_a = d sqrt(F), 0 off
+// band).  Register m of frequency thread tf is bin tf + T m before the inverse and after the
+// forward transform (the spectrum instances' statement).  Plain 16-byte stores, every cell
+// written once per launch; the buffer pointer is an extra argument of that kernel alone.
+#ifndef MIMO_BEAM_INST
+#define MIMO_BEAM_INST 0
+#endif
+
 constexpr int kMaxCsiAnt = 512;  // CSI-error runs: antennas (dynamic LDS per team, A doubles; engine.hip checks)
 constexpr uint32_t kFixedCsiTrial = 0xFFFFFFFFu;  // CSI stream counter of fixed-channel runs (oracle/sim.py draws)
 // The measured alternatives of the choices below (channel pipeline on / off per precision,
@@ -794,14 +806,23 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel_spec(TrialParams<R> p0,
                                                                                                   double* spec_rows) {
   constexpr double* meas_rows = nullptr;
+#elif MIMO_BEAM_INST
+__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel_beam(TrialParams<R> p0,
+                                                                                                  double* beam_cells) {
+  constexpr double* meas_rows = nullptr;
+  constexpr double* spec_rows = nullptr;
 #else
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel(TrialParams<R> p0) {
   constexpr double* meas_rows = nullptr;
   constexpr double* spec_rows = nullptr;
 #endif
+#if !MIMO_BEAM_INST
+  constexpr double* beam_cells = nullptr;
+#endif
   using C = cx<R>;
   constexpr bool MEAS = MIMO_MEAS_INST != 0 && sizeof(R) == 8;
   constexpr bool SPEC = MIMO_SPEC_INST != 0 && sizeof(R) == 8;
+  constexpr bool BEAM = MIMO_BEAM_INST != 0 && sizeof(R) == 8;
   // ---- which point and trial this block runs (uniform binary search over point_start)
   uint32_t pi = 0;
   if (p0.n_points > 1) {
@@ -1280,6 +1301,15 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
         if (lane == 63) vk_part[vkb][wid] = vk;  // read after the IFFT's first barrier
       }
       SL::scatter(d, x, t0);
+      if constexpr (BEAM) {
+        if (main_pass) {
+          // X_a / sqrt(F) as scattered (0 off band): the buffer's second half, bin tl + T m
+          double2* cell = reinterpret_cast<double2*>(beam_cells) +
+                          ((size_t)gridDim.x * (size_t)A + (size_t)blockIdx.x * (size_t)A + (size_t)a) * (size_t)F + tl;
+#pragma unroll
+          for (int m = 0; m < P; ++m) cell[T * m] = make_double2((double)d[m].x, (double)d[m].y);
+        }
+      }
       // the FFTs take the thread id already laundered for this antenna (tl) where it is the
       // physical one: their own opaque copy of it then costs no register move in run_second
       const int tfft = SPLITFFT ? t : tl;
@@ -1342,6 +1372,15 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
       }
       // keep the vk_part / alpha_s hand-offs ordered when the ablations drop the barriers
       if (MIMO_ABL(p, ABL_FFT) || (ALPHA1 && MIMO_ABL(p, ABL_XCHG))) __syncthreads();
+      if constexpr (BEAM) {
+        if (main_pass) {
+          // Y_a sqrt(F): the thread's P bins of the chain output, bin tl + T m
+          double2* cell =
+              reinterpret_cast<double2*>(beam_cells) + ((size_t)blockIdx.x * (size_t)A + (size_t)a) * (size_t)F + tl;
+#pragma unroll
+          for (int m = 0; m < P; ++m) cell[T * m] = make_double2((double)d[m].x, (double)d[m].y);
+        }
+      }
       if constexpr (SPEC) {
         if (main_pass) {
           // psd: |d|^2 / F (ortho) into the thread's cells, bin tl + T m; 1 / F is a power of two

@@ -46,7 +46,11 @@ struct InstanceKey {
   /* the spectrum instance (float64 only): spec = per-trial rows [grid.x][F + kSpecFixed] */              \
   hipError_t launch_trial_F##FV##_f64_spec(const InstanceKey& k, dim3 grid, hipStream_t st,               \
                                            const TrialParams<double>& p, bool* found,                     \
-                                           hipFuncAttributes* attr, double* spec);
+                                           hipFuncAttributes* attr, double* spec);                        \
+  /* the beam instance (float64 only): cells = [2][grid.x][A][F] complex128 (Y sqrt(F), X / sqrt(F)) */  \
+  hipError_t launch_trial_F##FV##_f64_beam(const InstanceKey& k, dim3 grid, hipStream_t st,               \
+                                           const TrialParams<double>& p, bool* found,                     \
+                                           hipFuncAttributes* attr, double* cells);
 MIMO_DECLARE_LAUNCH(128)
 MIMO_DECLARE_LAUNCH(256)
 MIMO_DECLARE_LAUNCH(512)

@@ -601,6 +601,37 @@ class Link:
             _, _, spec, _, _ = eng.spectrum_points(pts, [_seed64(s) for s in seed_arrs], np.zeros(P, np.int64), n, [0])
         return [_engine.SpectrumStats(spec[i], self.my_mod.n_sub_carr, int(n[i])) for i in range(P)]
 
+    # ------------------------------------------------------------------ beam mode
+    def beampattern(self, reroll_chan: bool, seed_arr, n_trials: int, probes):
+        """Beampattern of the current grid point over trials [0, n_trials) of ``simulate``'s trial
+        sequence: an ``_engine.BeamStats`` -- per probe position (``probes``: [n_probes, 3] in
+        metres, e.g. ``utilities.circle_probes``) the signal, the uncorrelated in-band distortion
+        and the out-of-band power the array radiates towards it through a line-of-sight channel.
+        A fixed number of trials, no stopping rule."""
+        return self.beampattern_points(reroll_chan, [seed_arr], [self.point_params()], n_trials, probes)[0]
+
+    def beampattern_points(self, reroll_chan: bool, seed_arrs, point_params, n_trials, probes) -> list:
+        """``beampattern`` for many grid points of this system in one engine call
+        (mimo_engine_beam_points), all over the same ``probes``; ``point_params`` as for
+        ``simulate_points``, ``n_trials`` one number or one per point.  The pattern is taken before
+        the user's channel and the noise, so a point whose SNR was never set runs at 0 dB.
+        -> a list of ``_engine.BeamStats``.  Single GPU."""
+        P = len(point_params)
+        if len(seed_arrs) != P:
+            raise ValueError("one seed_arr per point")
+        n = np.broadcast_to(np.asarray(n_trials, dtype=np.int64), (P,))
+        if np.any(n < 0):
+            raise ValueError("n_trials must be >= 0")
+        pts = [_engine.Engine.make_point(**dict(pp, snr_db=0.0 if pp["snr_db"] is None else pp["snr_db"]))
+               for pp in point_params]
+        dev = self.device if self.device is not None else _default_device()
+        acquire_device_slot(dev)  # private totals: nobody else closes them, never wait
+        with SlotHeartbeat(dev):
+            eng = self.engine(reroll_chan)
+            _, _, beam, _, _ = eng.beam_points(pts, [_seed64(s) for s in seed_arrs], np.zeros(P, np.int64), n, [0],
+                                               probes)
+        return [_engine.BeamStats(beam[i], int(n[i])) for i in range(P)]
+
     def update_distortion(self, ibo_val_db: float) -> None:
         """(mp_model.py:230-241)"""
         self.my_array.update_distortion(ibo_db=ibo_val_db, avg_sample_pow=self.my_mod.avg_sample_power)

@@ -25,7 +25,7 @@ import time
 
 import numpy as np
 
-from utilities import ebn0_to_snr, save_to_csv
+from utilities import circle_probes, ebn0_to_snr, save_to_csv
 
 
 # BASELINE config 4 at its stated extent (SNR 0-30 dB x IBO 0-7 dB): Eb/N0
@@ -280,6 +280,35 @@ def psd_vs_ibo_rows(stats):
     return list(np.concatenate([stats[0].freq_index[:, None].astype(np.float64), rel], axis=1))
 
 
+def beam_vs_angle(link, angles_deg, ibo_arr, n_trials, seed=2137, reroll_chan=True, radius=None, z=None):
+    """Beampattern of the array over ``angles_deg`` for every IBO of ``ibo_arr``: probes on the
+    horizontal circle around the origin through the user (``radius``, ``z``: the link's nominal
+    receiver's by default), ``n_trials`` trials per point, all points in one
+    ``Link.beampattern_points`` call (one GPU; point i is seeded by ``point_seed(seed, i)``).
+    -> (probes [n_angles, 3], a list of ``_engine.BeamStats``, one per IBO)."""
+    if radius is None or z is None:
+        rx = link.my_standard_rx
+        radius = float(np.hypot(rx.cord_x, rx.cord_y)) if radius is None else radius
+        z = float(rx.cord_z) if z is None else z
+    probes = circle_probes(angles_deg, radius, z)
+    params, seeds = [], []
+    for i, ibo in enumerate(np.asarray(ibo_arr, dtype=np.float64)):
+        link.update_distortion(ibo_val_db=float(ibo))
+        params.append(dict(link.point_params()))
+        seeds.append(point_seed(seed, i))
+    return probes, link.beampattern_points(reroll_chan, seeds, params, n_trials, probes)
+
+
+def beam_vs_angle_rows(angles_deg, stats):
+    """CSV rows of the beam sweep, one per angle: the angle [deg], then per IBO the signal, the
+    uncorrelated in-band distortion and the out-of-band power [dB], each over that IBO's mean
+    signal over the angles."""
+    cols = [np.asarray(angles_deg, dtype=np.float64).reshape(-1)]
+    for st in stats:
+        cols += [st.pattern_db("signal"), st.pattern_db("distortion"), st.pattern_db("power_oob")]
+    return list(np.stack(cols, axis=1))
+
+
 def ber_from_counts(err, bits):
     """BER with NaN where nothing was sent (main_mp_miso_cnc_ber_vs_ebn0.py:134-139)."""
     err = np.asarray(err, dtype=np.float64)
@@ -354,11 +383,15 @@ def _build_link(args, device):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--grid", choices=["ber_vs_ebn0", "fixed_ber", "sdr_vs_ibo", "psd_vs_ibo"], default="fixed_ber",
+    ap.add_argument("--grid", choices=["ber_vs_ebn0", "fixed_ber", "sdr_vs_ibo", "psd_vs_ibo", "beam_vs_angle"],
+                    default="fixed_ber",
                     help="sdr_vs_ibo: measured in-band SDR and per-iteration signal-to-error ratio per IBO "
                          "(--n-trials trials per point at the first --ebn0 value; one GPU).  psd_vs_ibo: the "
                          "array's radiated PSD per FFT bin, out-of-band share, Bussgang gain and efficiency per "
-                         "IBO (--n-trials trials per point; one GPU)")
+                         "IBO (--n-trials trials per point; one GPU).  beam_vs_angle: signal, uncorrelated "
+                         "distortion and out-of-band power radiated towards --angles on the circle through the "
+                         "user, per IBO (--n-trials trials per point; one GPU)")
+    ap.add_argument("--angles", type=str, default="0:180.1:1", help="beam_vs_angle: start:stop:step [deg]")
     ap.add_argument("--n-ant", type=int, default=64)
     ap.add_argument("--n-sc", type=int, default=2048)
     ap.add_argument("--n-fft", type=int, default=4096)
@@ -376,7 +409,8 @@ def main():
     ap.add_argument("--bits-sent-max", type=int, default=int(5e6))
     ap.add_argument("--n-err-min", type=int, default=int(1e5))
     ap.add_argument("--seed", type=int, default=2137)
-    ap.add_argument("--n-trials", type=int, default=4096, help="sdr_vs_ibo, psd_vs_ibo: trials per IBO point")
+    ap.add_argument("--n-trials", type=int, default=4096,
+                    help="sdr_vs_ibo, psd_vs_ibo, beam_vs_angle: trials per IBO point")
     ap.add_argument("--out", type=str, default="figs/csv_results")
     ap.add_argument("--split", choices=["points", "trials", "auto"], default="auto",
                     help="ranks deal whole points by cost (one all-reduce at the end), or share every point's "
@@ -423,6 +457,19 @@ def main():
         save_to_csv(oob_vs_ibo_rows(ibo_arr, stats), "oob_" + name, directory=args.out)
         save_to_csv(psd_vs_ibo_rows(stats), "psd_" + name, directory=args.out)
         print(f"psd sweep done: {len(ibo_arr)} IBO points x {args.n_trials} trials in "
+              f"{time.perf_counter() - t0:.1f} s -> {args.out}")
+        return
+    if args.grid == "beam_vs_angle":
+        if world > 1:
+            raise SystemExit("--grid beam_vs_angle runs on one GPU")
+        angles = rng(args.angles)
+        t0 = time.perf_counter()
+        _, stats = beam_vs_angle(link, angles, ibo_arr, args.n_trials, args.seed)
+        name = "beam_vs_angle_%s_nant%d_nfft%d_nsc%d_ibo_min%d_max%d_step%1.2f_nangles%d_ntrials%d" % (
+            args.channel, args.n_ant, args.n_fft, args.n_sc, min(ibo_arr), max(ibo_arr),
+            ibo_arr[1] - ibo_arr[0] if len(ibo_arr) > 1 else 0.0, len(angles), args.n_trials)
+        save_to_csv(beam_vs_angle_rows(angles, stats), name, directory=args.out)
+        print(f"beam sweep done: {len(ibo_arr)} IBO points x {len(angles)} angles x {args.n_trials} trials in "
               f"{time.perf_counter() - t0:.1f} s -> {args.out}")
         return
     t0 = time.perf_counter()

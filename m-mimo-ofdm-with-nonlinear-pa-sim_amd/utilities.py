@@ -77,6 +77,14 @@ def pts_on_semicircum(radius: float, n_points: int = 100) -> list:
             for x in range(0, n_points + 1)]
 
 
+def circle_probes(angles_deg, radius: float, z: float = 0.0) -> ndarray:
+    """Probe positions ``(r cos theta, r sin theta, z)`` [m] on the horizontal circle of ``radius``
+    around the origin at height ``z``, one row per angle [deg]: the ``probes`` of
+    ``Link.beampattern``."""
+    th = np.deg2rad(np.asarray(angles_deg, dtype=np.float64).reshape(-1))
+    return np.stack([radius * np.cos(th), radius * np.sin(th), np.full(th.shape, float(z))], axis=1)
+
+
 def pts_on_semisphere(radius: float, n_points: int = 100, center_x: float = 0, center_y: float = 0,
                       center_z: float = 0):
     """(utilities.py:170-192)"""
