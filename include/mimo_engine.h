@@ -89,7 +89,26 @@ typedef struct mimo_config {
                                0: the run's seed (ABI 5 behaviour).  (ABI 6) */
 } mimo_config;
 
-/* Grid-point parameters: what Link keeps in its PA / receiver / noise objects. */
+/* Grid-point parameters: what Link keeps in its PA / receiver / noise objects.
+ *
+ * mimo_engine_set_point and every *_points call check each point host-side, before any HIP
+ * call; a point that breaks a rule is MIMO_EINVAL with a message that names the field:
+ *   ibo_db, snr_db    finite (snr_db = 1000 is a noiseless run); avg_symbol_power / 10^(snr_db / 10),
+ *                     the noise power, must be finite too
+ *   avg_symbol_power  finite and > 0
+ *   pa_kind, cnc_pa_kind  MIMO_PA_NONE ... MIMO_PA_TOI, on every engine
+ *   sat_pow           > 0 where pa_kind is softlim or rapp (+inf: a PA that never saturates);
+ *                     not read otherwise (the TOI drivers send 0)
+ *   toi_coeff         finite where pa_kind is toi; not read otherwise
+ *   p_hardness        finite and > 0 where pa_kind, or under a CNC receiver cnc_pa_kind, is rapp:
+ *                     the one hardness of both Rapp models
+ *   cnc_sat_pow       > 0 where the engine's receiver is MIMO_RX_CNC and cnc_pa_kind is softlim or rapp
+ *   cnc_toi_coeff     finite where the receiver is MIMO_RX_CNC and cnc_pa_kind is toi
+ *   cnc_alpha         finite and non-zero
+ *   csi_eps           a number < 1; NaN is refused, not read as perfect CSI
+ *   array_alpha       finite and >= 0
+ * The MCNC receiver re-transmits through the array's PA and reads none of cnc_pa_kind,
+ * cnc_sat_pow, cnc_toi_coeff and cnc_alpha: any values that pass the rules above give the same counts. */
 typedef struct mimo_point {
   double ibo_db;            /* IBO used by the per-antenna Bussgang AGC (mp_model.py:315-317) */
   double snr_db;            /* Link.set_snr value                                    */

@@ -338,11 +338,29 @@ int validate_config(const mimo_config* c) {
 
 int validate_point(const mimo_engine* e, const mimo_point* pt) {
   auto bad_kind = [](int k) { return k < MIMO_PA_NONE || k > MIMO_PA_TOI; };
+  auto saturates = [](int k) { return k == MIMO_PA_SOFTLIM || k == MIMO_PA_RAPP; };
   if (bad_kind(pt->pa_kind) || bad_kind(pt->cnc_pa_kind)) return fail(MIMO_EINVAL, "unknown PA kind");
-  if ((pt->pa_kind == MIMO_PA_SOFTLIM || pt->pa_kind == MIMO_PA_RAPP) && !(pt->sat_pow > 0))
-    return fail(MIMO_EINVAL, "sat_pow must be > 0");
-  if (pt->pa_kind == MIMO_PA_RAPP && !(pt->p_hardness > 0)) return fail(MIMO_EINVAL, "p_hardness must be > 0");
-  if (!(pt->cnc_alpha != 0)) return fail(MIMO_EINVAL, "cnc_alpha must be non-zero");
+  // every test below is written to fail for NaN (the rules stand next to mimo_point in mimo_engine.h)
+  if (!std::isfinite(pt->ibo_db)) return fail(MIMO_EINVAL, "ibo_db must be finite");
+  if (!std::isfinite(pt->snr_db)) return fail(MIMO_EINVAL, "snr_db must be finite");
+  if (!(pt->avg_symbol_power > 0) || !std::isfinite(pt->avg_symbol_power))
+    return fail(MIMO_EINVAL, "avg_symbol_power must be finite and > 0");
+  if (!std::isfinite(pt->avg_symbol_power / std::pow(10.0, pt->snr_db / 10.0)))
+    return fail(MIMO_EINVAL, "snr_db leaves no finite noise power avg_symbol_power / 10^(snr_db / 10)");
+  if (saturates(pt->pa_kind) && !(pt->sat_pow > 0)) return fail(MIMO_EINVAL, "sat_pow must be > 0");
+  if (pt->pa_kind == MIMO_PA_TOI && !std::isfinite(pt->toi_coeff)) return fail(MIMO_EINVAL, "toi_coeff must be finite");
+  // the receiver's own PA copy: read by the CNC loop only (MCNC re-transmits through the array's PA)
+  const bool cnc = e->cfg.receiver_kind == MIMO_RX_CNC;
+  if (cnc && saturates(pt->cnc_pa_kind) && !(pt->cnc_sat_pow > 0)) return fail(MIMO_EINVAL, "cnc_sat_pow must be > 0");
+  if (cnc && pt->cnc_pa_kind == MIMO_PA_TOI && !std::isfinite(pt->cnc_toi_coeff))
+    return fail(MIMO_EINVAL, "cnc_toi_coeff must be finite");
+  // one hardness for both Rapp models
+  if ((pt->pa_kind == MIMO_PA_RAPP || (cnc && pt->cnc_pa_kind == MIMO_PA_RAPP)) &&
+      (!(pt->p_hardness > 0) || !std::isfinite(pt->p_hardness)))
+    return fail(MIMO_EINVAL, "p_hardness must be finite and > 0");
+  if (!(pt->cnc_alpha != 0) || !std::isfinite(pt->cnc_alpha))
+    return fail(MIMO_EINVAL, "cnc_alpha must be finite and non-zero");
+  if (std::isnan(pt->csi_eps)) return fail(MIMO_EINVAL, "csi_eps must be a number (< 0: perfect CSI)");
   if (pt->csi_eps >= 1.0) return fail(MIMO_EINVAL, "csi_eps must be < 1");
   if (pt->csi_eps >= 0 && e->cfg.n_ant > mimo::kMaxCsiAnt) return fail(MIMO_EINVAL, "CSI error supports n_ant <= 512");
   if (!(pt->array_alpha >= 0) || !std::isfinite(pt->array_alpha))

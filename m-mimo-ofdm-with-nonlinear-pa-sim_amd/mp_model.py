@@ -368,6 +368,12 @@ class Link:
         else:
             ck, csat, cp, ctoi = distortion.pa_params(self.my_cnc_rx.impairment)
             calpha = float(self.my_cnc_rx.modem.alpha)
+            # mimo_point has one p_hardness for the array's and the receiver's Rapp model
+            if ck == "rapp" and kind == "rapp" and cp != p:
+                raise ValueError(f"the CNC receiver's Rapp hardness {cp} differs from the array's {p}: "
+                                 "the engine runs both Rapp models with one p_hardness")
+            if ck == "rapp" and kind != "rapp":
+                p = cp  # the array's PA does not read it
         return dict(ibo_db=float(self.ibo_val_db), snr_db=float(self.my_noise.snr_db),
                     avg_symbol_power=float(self.my_mod.avg_symbol_power), pa_kind=kind, sat_pow=sat, p_hardness=p,
                     toi_coeff=toi, cnc_pa_kind=ck, cnc_sat_pow=csat, cnc_toi_coeff=ctoi, cnc_alpha=calpha,

@@ -53,6 +53,14 @@ class SimConfig:
     # every antenna's AGC gain and the CNC receiver's alpha; None: Link's (mp_model.py:315-317)
     array_alpha: float | None = None
     cnc_alpha: float | None = None
+    # the CNC receiver's own PA copy (CncReceiver.impairment, corrector.py:23-50) where it is not the
+    # array's: its kind, the IBO its saturation power / cubic coefficient derive from, or that
+    # coefficient itself.  None: the array's (Link builds both from one object).  A Rapp receiver
+    # shares p_hardness with the array.  cnc_alpha stays calc_alpha(ibo_db) unless set above.
+    # Ignored under MCNC, whose receiver re-transmits through the array's PA.
+    cnc_pa: str | None = None
+    cnc_ibo_db: float | None = None
+    cnc_toi_coeff: float | None = None
 
     def __post_init__(self):
         if self.tx_pos is None:
@@ -92,16 +100,21 @@ def point_params(cfg: SimConfig):
     es = rm.avg_symbol_power(const)
     avg_samp = es * cfg.n_sc / cfg.n_fft
     out = dict(const=const, es=es, avg_samp=avg_samp, snr=10 ** (cfg.snr_db / 10))
-    if cfg.pa == "toi":
-        out["cnc_coeff"] = rm.toi_coeff(cfg.ibo_db, avg_samp)
-        out["cnc_alpha"] = 1.0
+    cnc_pa = cfg.pa if cfg.cnc_pa is None else cfg.cnc_pa
+    cnc_ibo = cfg.ibo_db if cfg.cnc_ibo_db is None else cfg.cnc_ibo_db
+    out["cnc_pa"] = cnc_pa
+    if cnc_pa == "toi":
+        out["cnc_coeff"] = rm.toi_coeff(cnc_ibo, avg_samp)
         out["cnc_sat"] = 0.0
     else:
-        # CncReceiver: sat = 10^(IBO/10) * Es * S/F, alpha = calc_alpha(IBO)
-        # (corrector.py:23-50 + Link.update_distortion, mp_model.py:230-241).
-        out["cnc_sat"] = rm.sat_pow(cfg.ibo_db, avg_samp)
-        out["cnc_alpha"] = float(rm.calc_alpha(cfg.ibo_db))
+        # CncReceiver: sat = 10^(IBO/10) * Es * S/F (corrector.py:23-50 + Link.update_distortion,
+        # mp_model.py:230-241).
+        out["cnc_sat"] = rm.sat_pow(cnc_ibo, avg_samp)
         out["cnc_coeff"] = 0.0
+    # alpha belongs to the array's PA: 1 for the cubic model, else calc_alpha(IBO)
+    out["cnc_alpha"] = 1.0 if cfg.pa == "toi" else float(rm.calc_alpha(cfg.ibo_db))
+    if cfg.cnc_toi_coeff is not None:
+        out["cnc_coeff"] = float(cfg.cnc_toi_coeff)
     if cfg.cnc_alpha is not None:
         out["cnc_alpha"] = float(cfg.cnc_alpha)
     return out
@@ -152,7 +165,7 @@ def run_trial(cfg: SimConfig, labels, z_chan, z_noise, loc_u=None, z_csi=None, i
     z = (r + n) / g["ak_hk_vk"]
     iters = [int(i) for i in iters]
     if cfg.receiver == "cnc":
-        det = rm.cnc_receive(iters, z, const, cfg.n_fft, cfg.pa, pp["cnc_sat"], cfg.p_hardness,
+        det = rm.cnc_receive(iters, z, const, cfg.n_fft, pp["cnc_pa"], pp["cnc_sat"], cfg.p_hardness,
                              pp["cnc_coeff"], pp["cnc_alpha"])
     else:
         det = mcnc_receive(cfg, iters, z, const, p, h_est, g["ak_hk_vk"], pp, gain)

@@ -50,8 +50,8 @@ def trial_row(cfg, d, j, iters, incl_clean):
         n_c = np.sqrt(pp["es"] * g["hk_vk_noise"] / pp["snr"]) * d["z_noise"][j]
         v.append((r_c + n_c) / g["hk_vk"])
     if cfg.receiver == "cnc":
-        vi = rm.cnc_receive(iters, z, const, cfg.n_fft, cfg.pa, pp["cnc_sat"], cfg.p_hardness, pp["cnc_coeff"],
-                            pp["cnc_alpha"], return_bits=False)
+        vi = rm.cnc_receive(iters, z, const, cfg.n_fft, pp["cnc_pa"], pp["cnc_sat"], cfg.p_hardness,
+                            pp["cnc_coeff"], pp["cnc_alpha"], return_bits=False)
     else:
         h_est = rm.csi_error(dbg["h"], cfg.csi_eps, z_csi) if cfg.csi_eps is not None else dbg["h"]
         vi = mcnc_slicer_inputs(cfg, iters, z, const, dbg["p"], h_est, g["ak_hk_vk"], pp, dbg["gain"])

@@ -112,6 +112,150 @@ def test_set_point_array_alpha_validation():
         lib.mimo_engine_destroy(h)
 
 
+NAN, INF = float("nan"), float("inf")
+# a valid soft-limiter / soft-limiter point (make_point keywords), which every case below alters
+GOOD_POINT = dict(ibo_db=3.0, snr_db=20.0, avg_symbol_power=10.0, pa_kind="softlim", sat_pow=1.0, cnc_sat_pow=1.0,
+                  cnc_alpha=0.9)
+
+
+def _run_points_rc(lib, h, pts):
+    """mimo_engine_run_points over ``pts`` (MimoPoint), 4 trials each, iteration 0."""
+    n = len(pts)
+    arr = (_engine.MimoPoint * n)(*pts)
+    u64 = ctypes.POINTER(ctypes.c_uint64)
+    seeds, first, ntr = np.arange(1, n + 1, dtype=np.uint64), np.zeros(n, np.uint64), np.full(n, 4, np.uint64)
+    it = np.zeros(1, np.int32)
+    err, bits = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+    rc = lib.mimo_engine_run_points(h, n, arr, seeds.ctypes.data_as(u64), first.ctypes.data_as(u64),
+                                    ntr.ctypes.data_as(u64), it.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), 1, 0,
+                                    err.ctypes.data_as(u64), bits.ctypes.data_as(u64), None)
+    assert not err.any() and not bits.any()
+    return rc
+
+
+@pytest.mark.parametrize("receiver,change,field", [
+    # the receiver's saturation power where its soft limiter / Rapp model divides by it
+    ("cnc", dict(cnc_sat_pow=0.0), "cnc_sat_pow"),
+    ("cnc", dict(cnc_sat_pow=-1.0), "cnc_sat_pow"),
+    ("cnc", dict(cnc_sat_pow=NAN), "cnc_sat_pow"),
+    ("cnc", dict(cnc_pa_kind="rapp", p_hardness=3.0, cnc_sat_pow=0.0), "cnc_sat_pow"),
+    ("cnc", dict(cnc_pa_kind="rapp", p_hardness=3.0, cnc_sat_pow=NAN), "cnc_sat_pow"),
+    ("cnc", dict(pa_kind="toi", toi_coeff=0.01, sat_pow=0.0, cnc_pa_kind="softlim", cnc_sat_pow=0.0), "cnc_sat_pow"),
+    # the one Rapp hardness, read by a Rapp receiver under any array
+    ("cnc", dict(cnc_pa_kind="rapp", p_hardness=0.0), "p_hardness"),
+    ("cnc", dict(pa_kind="rapp", cnc_pa_kind="rapp", p_hardness=NAN), "p_hardness"),
+    ("cnc", dict(cnc_alpha=NAN), "cnc_alpha"),
+    ("mcnc", dict(cnc_alpha=NAN), "cnc_alpha"),
+    ("cnc", dict(cnc_alpha=0.0), "cnc_alpha"),
+    ("cnc", dict(snr_db=NAN), "snr_db"),
+    ("cnc", dict(snr_db=INF), "snr_db"),
+    ("cnc", dict(snr_db=-INF), "snr_db"),
+    ("cnc", dict(snr_db=-4000.0), "snr_db"),  # 10^-400 underflows: an infinite noise power
+    ("mcnc", dict(snr_db=NAN), "snr_db"),
+    ("cnc", dict(ibo_db=NAN), "ibo_db"),
+    ("cnc", dict(ibo_db=INF), "ibo_db"),
+    ("cnc", dict(avg_symbol_power=NAN), "avg_symbol_power"),
+    ("cnc", dict(avg_symbol_power=INF), "avg_symbol_power"),
+    ("cnc", dict(avg_symbol_power=0.0), "avg_symbol_power"),
+    ("cnc", dict(avg_symbol_power=-10.0), "avg_symbol_power"),
+    ("cnc", dict(pa_kind="toi", cnc_pa_kind="toi", toi_coeff=NAN, cnc_toi_coeff=0.01), "toi_coeff"),
+    ("cnc", dict(pa_kind="toi", cnc_pa_kind="toi", toi_coeff=INF, cnc_toi_coeff=0.01), "toi_coeff"),
+    ("cnc", dict(pa_kind="toi", cnc_pa_kind="toi", toi_coeff=0.01, cnc_toi_coeff=NAN), "cnc_toi_coeff"),
+    ("cnc", dict(cnc_pa_kind="toi", cnc_toi_coeff=-INF), "cnc_toi_coeff"),
+    ("mcnc", dict(pa_kind="toi", cnc_pa_kind="toi", toi_coeff=NAN), "toi_coeff"),
+    ("cnc", dict(csi_eps=NAN), "csi_eps"),
+    ("mcnc", dict(csi_eps=NAN), "csi_eps"),
+    ("cnc", dict(sat_pow=NAN), "sat_pow"),
+    ("cnc", dict(sat_pow=0.0), "sat_pow"),
+])
+def test_point_validation_refuses_bad_fields_by_name(receiver, change, field):
+    """A point whose field would run as something else -- a zero or NaN saturation power of the CNC
+    receiver's PA (soft limiter: the re-synthesised signal scaled to 0; Rapp: the identity), a NaN
+    alpha, SNR, IBO, symbol power or cubic coefficient, a NaN csi_eps (read as perfect CSI) -- is
+    MIMO_EINVAL from mimo_engine_set_point and from mimo_engine_run_points, as the first point or
+    after a valid one; the message names the field; all host-side, no HIP call."""
+    lib = _engine.lib()
+    c, keep = _cfg(n_fft=512, n_sub_carr=256, receiver_kind=_engine.RX_KINDS[receiver])
+    h = lib.mimo_engine_create(ctypes.byref(c))
+    assert h
+    good = _engine.Engine.make_point(**GOOD_POINT)
+    assert lib.mimo_engine_set_point(h, ctypes.byref(good)) == 0
+    bad = _engine.Engine.make_point(**dict(GOOD_POINT, **change))
+    assert lib.mimo_engine_set_point(h, ctypes.byref(bad)) == -1
+    msg = lib.mimo_last_error().decode()
+    assert msg.startswith(field), msg
+    for pts in ([bad], [good, bad]):
+        assert _run_points_rc(lib, h, pts) == -1
+        assert lib.mimo_last_error().decode() == msg
+    lib.mimo_engine_destroy(h)
+
+
+@pytest.mark.parametrize("receiver,change", [
+    ("cnc", dict(pa_kind="toi", cnc_pa_kind="toi", sat_pow=0.0, cnc_sat_pow=0.0, toi_coeff=0.01, cnc_toi_coeff=0.01)),
+    ("cnc", dict(pa_kind="none", cnc_pa_kind="none", sat_pow=0.0, cnc_sat_pow=0.0)),
+    ("cnc", dict(cnc_pa_kind="none", cnc_sat_pow=0.0)),
+    ("cnc", dict(cnc_pa_kind="toi", cnc_sat_pow=0.0, cnc_toi_coeff=0.01)),
+    ("mcnc", dict(cnc_sat_pow=0.0)),                      # MCNC reads no cnc_* field
+    ("mcnc", dict(cnc_pa_kind="rapp", cnc_sat_pow=0.0, p_hardness=0.0)),
+    ("mcnc", dict(cnc_pa_kind="toi", cnc_toi_coeff=NAN)),
+    ("cnc", dict(sat_pow=INF)),                           # an array PA that never saturates
+    ("cnc", dict(cnc_sat_pow=INF)),
+    ("cnc", dict(csi_eps=0.0)),
+    ("cnc", dict(csi_eps=-1.0)),
+    ("cnc", dict(snr_db=1000.0)),                         # noiseless
+    ("cnc", dict(snr_db=-50.0)),
+    ("cnc", dict(toi_coeff=NAN)),                         # not read: the array is a soft limiter
+    ("cnc", dict(cnc_toi_coeff=NAN)),
+    ("cnc", dict(pa_kind="rapp", cnc_pa_kind="softlim", p_hardness=2.5)),   # the receiver's model differs
+    ("cnc", dict(pa_kind="softlim", cnc_pa_kind="rapp", p_hardness=2.5)),
+])
+def test_point_validation_keeps_every_legitimate_edge(receiver, change):
+    """The edges that stay valid: a zero saturation power where no soft limiter / Rapp reads it (the
+    TOI drivers' points, any cnc_* field under MCNC), an infinite one, csi_eps = 0, a noiseless SNR,
+    a receiver PA of another kind than the array's."""
+    lib = _engine.lib()
+    c, keep = _cfg(n_fft=512, n_sub_carr=256, receiver_kind=_engine.RX_KINDS[receiver])
+    h = lib.mimo_engine_create(ctypes.byref(c))
+    pt = _engine.Engine.make_point(**dict(GOOD_POINT, **change))
+    assert lib.mimo_engine_set_point(h, ctypes.byref(pt)) == 0, lib.mimo_last_error()
+    lib.mimo_engine_destroy(h)
+
+
+def test_published_toi_points_pass_the_point_validation():
+    """tools/published_families sends sat_pow = cnc_sat_pow = 0 with its TOI points: still valid."""
+    import published_families as pf
+    lib = _engine.lib()
+    first = {}  # the first TOI curve of each receiver kind
+    for curve in pf.CURVES:
+        if curve["family"] == "toi":
+            first.setdefault(curve["receiver"], curve)
+    assert "cnc" in first
+    for receiver, curve in first.items():
+        c, keep = _cfg(n_fft=512, n_sub_carr=256, receiver_kind=_engine.RX_KINDS[receiver])
+        h = lib.mimo_engine_create(ctypes.byref(c))
+        _, pts = pf.points(dict(curve), np.array([10.0, 15.0]))
+        for pp in pts:
+            assert pp["sat_pow"] == 0.0 and pp["cnc_sat_pow"] == 0.0
+            pt = _engine.Engine.make_point(**pp)
+            assert lib.mimo_engine_set_point(h, ctypes.byref(pt)) == 0, (curve, lib.mimo_last_error())
+        lib.mimo_engine_destroy(h)
+
+
+def test_run_points_refuses_a_mix_of_csi_on_and_off():
+    """All points of one call run one kernel instance, with or without the CSI error model: a call
+    whose points disagree is MIMO_EINVAL before any HIP call, whichever comes first."""
+    lib = _engine.lib()
+    c, keep = _cfg(n_fft=512, n_sub_carr=256)
+    h = lib.mimo_engine_create(ctypes.byref(c))
+    off = _engine.Engine.make_point(**GOOD_POINT)
+    for eps in (0.0, 0.2):
+        on = _engine.Engine.make_point(**dict(GOOD_POINT, csi_eps=eps))
+        for pts in ([off, on], [on, off], [on, on, off]):
+            assert _run_points_rc(lib, h, pts) == -1
+            assert "agree on CSI" in lib.mimo_last_error().decode()
+    lib.mimo_engine_destroy(h)
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     monkeypatch.setattr(_engine, "_lib", None)
     monkeypatch.setattr(_engine, "LIB_PATH", str(tmp_path / "nope.so"))

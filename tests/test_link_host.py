@@ -360,3 +360,42 @@ def test_fixed_toi_array_alpha_is_an_engine_level_parameter():
     for pp in pts:
         assert pp["pa_kind"] == "toi" and pp["array_alpha"] == c["alpha_estimate"] == pp["cnc_alpha"]
         assert _engine.Engine.make_point(**pp).array_alpha == c["alpha_estimate"]
+
+
+def test_point_params_refuses_a_receiver_rapp_of_another_hardness():
+    """mimo_point has one p_hardness: a CNC receiver whose Rapp copy has another hardness than the
+    array's cannot run as built, so point_params() says so, with both values, instead of running
+    the receiver with the array's."""
+    import distortion
+    link, mod = build_link(pa="rapp", p_hard=3.0, ibo=2.0)
+    assert link.point_params()["p_hardness"] == 3.0
+    link.my_cnc_rx.impairment.set_hardness(2.0)
+    with pytest.raises(ValueError, match=r"hardness 2\.0 differs from the array's 3\.0"):
+        link.point_params()
+    link.my_cnc_rx.impairment.set_hardness(3.0)
+    assert link.point_params()["cnc_pa_kind"] == "rapp"
+    # MCNC has no receiver PA copy: nothing to compare
+    mlink, _ = build_link(pa="rapp", p_hard=3.0, ibo=2.0, is_mcnc=True)
+    assert mlink.point_params()["p_hardness"] == 3.0
+    # a Rapp receiver under a soft-limiter array: the one hardness is the receiver's
+    slink, smod = build_link(pa="softlim", ibo=2.0)
+    slink.my_cnc_rx.impairment = distortion.Rapp(ibo_db=2.0, avg_samp_pow=smod.avg_sample_power, p_hardness=2.5)
+    pp = slink.point_params()
+    assert (pp["pa_kind"], pp["cnc_pa_kind"], pp["p_hardness"]) == ("softlim", "rapp", 2.5)
+
+
+def test_point_params_carries_a_receiver_pa_of_another_kind():
+    """A CNC receiver whose PA model is wrong -- a soft limiter for a Rapp array: point_params()
+    forwards the two kinds and each object's own saturation power, and make_point keeps them."""
+    import _engine
+    import distortion
+    link, mod = build_link(n_ant=8, pa="rapp", p_hard=3.0, ibo=1.0)
+    link.my_cnc_rx.impairment = distortion.SoftLimiter(2.5, mod.avg_sample_power)
+    link.set_snr(12.0)
+    pp = link.point_params()
+    assert pp["pa_kind"] == "rapp" and pp["cnc_pa_kind"] == "softlim" and pp["p_hardness"] == 3.0
+    assert pp["sat_pow"] == pytest.approx(10 ** 0.1 * mod.avg_sample_power / 8, rel=1e-12)
+    assert pp["cnc_sat_pow"] == pytest.approx(10 ** 0.25 * mod.avg_sample_power, rel=1e-12)
+    pt = _engine.Engine.make_point(**pp)
+    assert (pt.pa_kind, pt.cnc_pa_kind) == (_engine.PA_KINDS["rapp"], _engine.PA_KINDS["softlim"])
+    assert pt.cnc_sat_pow == pp["cnc_sat_pow"] and pt.sat_pow == pp["sat_pow"]
