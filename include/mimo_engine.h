@@ -56,7 +56,23 @@ enum { MIMO_PREC_F64 = 0, MIMO_PREC_F32 = 1 };
 
 typedef struct mimo_engine mimo_engine;
 
-/* System description: everything Link deep-copies at construction.  Arrays are copied. */
+/* System description: everything Link deep-copies at construction.  Arrays are copied.
+ *
+ * mimo_engine_create checks the description host-side, before any HIP call; one that breaks a
+ * rule gives a null engine and MIMO_EINVAL with a message that names the field.  Next to the
+ * ranges noted at the fields, the geometry:
+ *   tx_pos            required; all 3 n_ant values finite
+ *   rx_pos            finite
+ *   rx_loc_var        finite and >= 0
+ *   carrier_freqs     required; all n_fft values finite and > 0
+ *   chan_table        MIMO_CH_TABLE: required; all 2 n_ant n_fft values finite
+ * One rule is about what a run divides by, and is checked by mimo_engine_run and every *_points
+ * call instead (MIMO_EINVAL, before any HIP call; an engine that is never run may hold it):
+ *   tx_pos, rx_pos    every channel but MIMO_CH_TABLE (which reads no position): no antenna at
+ *                     rx_pos -- the distance of the Rayleigh attenuation must be finite and > 0;
+ *                     MIMO_CH_LOS and MIMO_CH_TWOPATH also: no antenna at (rx_pos[0], rx_pos[0],
+ *                     rx_pos[2]), the centre the jitter is drawn around (both jittered coordinates
+ *                     start from rx_pos[0], as mp_model.py:192-199 draws them) */
 typedef struct mimo_config {
   int32_t n_ant;            /* antennas (AntennaArray.n_elements)                   */
   int32_t n_sub_carr;       /* data sub-carriers S (multiple of 4, S <= n_fft - 2)  */

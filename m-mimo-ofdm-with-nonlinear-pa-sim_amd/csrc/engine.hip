@@ -333,6 +333,47 @@ int validate_config(const mimo_config* c) {
   if (c->chan_replay_period < 0) return fail(MIMO_EINVAL, "chan_replay_period must be >= 0");
   if (c->chan_replay_period > 0 && c->channel_kind != MIMO_CH_RAYLEIGH)
     return fail(MIMO_EINVAL, "chan_replay_period applies to the Rayleigh channel only");
+  // the geometry (the rules stand next to mimo_config in mimo_engine.h); every test fails for NaN
+  for (int i = 0; i < 3 * c->n_ant; ++i)
+    if (!std::isfinite(c->tx_pos[i]))
+      return fail(MIMO_EINVAL, "tx_pos must be finite (antenna " + std::to_string(i / 3) + ")");
+  for (int i = 0; i < 3; ++i)
+    if (!std::isfinite(c->rx_pos[i])) return fail(MIMO_EINVAL, "rx_pos must be finite");
+  if (!(c->rx_loc_var >= 0) || !std::isfinite(c->rx_loc_var))
+    return fail(MIMO_EINVAL, "rx_loc_var must be finite and >= 0");
+  if (!c->carrier_freqs) return fail(MIMO_EINVAL, "carrier_freqs is required");
+  for (int k = 0; k < c->n_fft; ++k)
+    if (!(c->carrier_freqs[k] > 0) || !std::isfinite(c->carrier_freqs[k]))
+      return fail(MIMO_EINVAL, "carrier_freqs must be finite and > 0 (bin " + std::to_string(k) + ")");
+  if (c->channel_kind == MIMO_CH_TABLE)
+    for (size_t i = 0; i < (size_t)c->n_ant * c->n_fft * 2; ++i)
+      if (!std::isfinite(c->chan_table[i]))
+        return fail(MIMO_EINVAL, "chan_table must be finite (antenna " + std::to_string(i / 2 / c->n_fft) + ")");
+  return MIMO_OK;
+}
+
+// The distances the channel divides by, checked by every run call before its first HIP call (an
+// engine that is only created, described or given points may hold any finite positions): the
+// Rayleigh attenuation's, from the nominal RX, and for LoS / two-path the centre the jitter is
+// drawn around, (rx_pos[0], rx_pos[0], rx_pos[2]) (mp_model.py:192-199 uses rx_loc_x for the y
+// coordinate too).  Table channels read no position.
+int validate_distances(const mimo_engine* e) {
+  const mimo_config& c = e->cfg;
+  if (c.channel_kind == MIMO_CH_TABLE) return MIMO_OK;
+  const bool moves = c.channel_kind == MIMO_CH_LOS || c.channel_kind == MIMO_CH_TWOPATH;
+  // (the distance as ensure_device forms it: one that rounds to 0 or overflows is refused too)
+  auto no_distance = [](const double* t, double x, double y, double z) {
+    const double dx = t[0] - x, dy = t[1] - y, dz = t[2] - z, d = std::sqrt(dx * dx + dy * dy + dz * dz);
+    return !(d > 0) || !std::isfinite(d);
+  };
+  for (int a = 0; a < c.n_ant; ++a) {
+    const double* t = e->tx_pos.data() + 3 * a;
+    if (no_distance(t, c.rx_pos[0], c.rx_pos[1], c.rx_pos[2]))
+      return fail(MIMO_EINVAL, "rx_pos is no finite distance > 0 from antenna " + std::to_string(a) + " (tx_pos)");
+    if (moves && no_distance(t, c.rx_pos[0], c.rx_pos[0], c.rx_pos[2]))
+      return fail(MIMO_EINVAL, "rx_pos: the jitter's centre (rx_pos[0], rx_pos[0], rx_pos[2]) is no finite distance > 0 "
+                               "from antenna " + std::to_string(a) + " (tx_pos)");
+  }
   return MIMO_OK;
 }
 
@@ -544,14 +585,7 @@ mimo_engine* mimo_engine_create(const mimo_config* cfg) {
   e->cfg = *cfg;
   const int A = cfg->n_ant, F = cfg->n_fft;
   e->tx_pos.assign(cfg->tx_pos, cfg->tx_pos + 3 * A);
-  e->freqs.resize(F);
-  if (cfg->carrier_freqs) {
-    std::copy(cfg->carrier_freqs, cfg->carrier_freqs + F, e->freqs.begin());
-  } else {
-    fail(MIMO_EINVAL, "carrier_freqs is required");
-    delete e;
-    return nullptr;
-  }
+  e->freqs.assign(cfg->carrier_freqs, cfg->carrier_freqs + F);
   e->cfg.tx_pos = nullptr;
   e->cfg.carrier_freqs = nullptr;
   if (cfg->channel_kind == MIMO_CH_TABLE) {  // keep the in-band columns, bins b(k) (modulation.py:266-267)
@@ -622,6 +656,7 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
     if (n_trials[i] + first_trial[i] > (1ull << 32) || first_trial[i] >= (1ull << 32))
       return fail(MIMO_EINVAL, "trial index must fit 32 bits");
   }
+  if (int rc = validate_distances(e)) return rc;
   const mimo::InstanceKey key = select_instance(e, csi);
   if (int rc = ensure_device(e)) return rc;
   if (csi) {

@@ -3,7 +3,12 @@ import copy
 
 
 def build_link(n_ant=8, n_sc=64, n_fft=128, M=16, cp=4, pa="softlim", ibo=1.0, p_hard=3.0, chan="rayleigh",
-               is_mcnc=False, n_err_min=10 ** 12, bits_sent_max=10 ** 6, csi=None, **kw):
+               is_mcnc=False, n_err_min=10 ** 12, bits_sent_max=10 ** 6, csi=None, array="linear", center_freq=3.5e9,
+               carrier_spacing=15e3, rx_xyz=(212.0, 212.0, 1.5), rx_loc_var=10.0, **kw):
+    """``array``: "linear", "circular" (both of ``n_ant`` elements) or "planar" (``n_ant`` a pair:
+    elements per row, per column); ``center_freq`` / ``carrier_spacing`` [Hz] of every transceiver
+    and of the array's wavelength; ``rx_xyz`` the user's coordinates [m].  The defaults are the
+    reference drivers' system."""
     import antenna_array
     import channel
     import distortion
@@ -21,12 +26,20 @@ def build_link(n_ant=8, n_sc=64, n_fft=128, M=16, cp=4, pa="softlim", ibo=1.0, p
         dist = distortion.ThirdOrderNonLin(toi_db=ibo, avg_samp_pow=mod.avg_sample_power)
     else:
         raise ValueError(pa)
-    tx = transceiver.Transceiver(modem=copy.deepcopy(mod), impairment=copy.deepcopy(dist), center_freq=int(3.5e9),
-                                 carrier_spacing=int(15e3))
-    rx = transceiver.Transceiver(modem=copy.deepcopy(mod), impairment=copy.deepcopy(dist), cord_x=212.0, cord_y=212.0,
-                                 cord_z=1.5, center_freq=int(3.5e9), carrier_spacing=int(15e3))
-    arr = antenna_array.LinearArray(n_elements=n_ant, base_transceiver=tx, center_freq=int(3.5e9), wav_len_spacing=0.5,
-                                    cord_x=0, cord_y=0, cord_z=15)
+    fc, df = int(center_freq), int(carrier_spacing)
+    tx = transceiver.Transceiver(modem=copy.deepcopy(mod), impairment=copy.deepcopy(dist), center_freq=fc,
+                                 carrier_spacing=df)
+    rx = transceiver.Transceiver(modem=copy.deepcopy(mod), impairment=copy.deepcopy(dist), cord_x=rx_xyz[0],
+                                 cord_y=rx_xyz[1], cord_z=rx_xyz[2], center_freq=fc, carrier_spacing=df)
+    place = dict(base_transceiver=tx, center_freq=fc, wav_len_spacing=0.5, cord_x=0, cord_y=0, cord_z=15)
+    if array == "linear":
+        arr = antenna_array.LinearArray(n_elements=n_ant, **place)
+    elif array == "circular":
+        arr = antenna_array.CircularArray(n_elements=n_ant, **place)
+    elif array == "planar":
+        arr = antenna_array.PlanarRectangularArray(n_elements_per_row=n_ant[0], n_elements_per_col=n_ant[1], **place)
+    else:
+        raise ValueError(array)
     if chan == "rayleigh":
         ch = channel.MisoRayleighFd(tx_transceivers=arr.array_elements, rx_transceiver=rx, seed=1234)
     elif chan == "los":
@@ -36,7 +49,7 @@ def build_link(n_ant=8, n_sc=64, n_fft=128, M=16, cp=4, pa="softlim", ibo=1.0, p
         ch = channel.MisoTwoPathFd()
         ch.calc_channel_mat(tx_transceivers=arr.array_elements, rx_transceiver=rx, skip_attenuation=False)
     link = mp_model.Link(mod_obj=mod, array_obj=arr, std_rx_obj=rx, chan_obj=ch, noise_obj=noise.Awgn(snr_db=10, seed=1),
-                         rx_loc_var=10.0, n_err_min=n_err_min, bits_sent_max=bits_sent_max, is_mcnc=is_mcnc,
+                         rx_loc_var=rx_loc_var, n_err_min=n_err_min, bits_sent_max=bits_sent_max, is_mcnc=is_mcnc,
                          csi_epsylon=csi, **kw)
     link.update_distortion(ibo_val_db=ibo)
     return link, mod

@@ -40,15 +40,24 @@ def test_build_entry_checks_the_header_abi():
     assert g._header_abi_version() == _engine.lib().mimo_abi_version() == 8
 
 
-def _cfg(**kw):
-    tx = np.zeros((kw.get("n_ant", 4), 3))
-    fr = np.full(kw.get("n_fft", 256), 3.5e9)
+def _cfg(tx=None, fr=None, rx_pos=(0.0, 0.0, 0.0), table=None, **kw):
+    """A config that mimo_engine_create accepts (every position at the origin: nothing here runs
+    it) altered by ``kw``; ``tx`` [n_ant, 3], ``fr`` [n_fft], ``table`` [n_ant, n_fft] complex
+    replace the arrays, the string "null" passes a null pointer."""
+    dp = ctypes.POINTER(ctypes.c_double)
+    if tx is None:
+        tx = np.zeros((kw.get("n_ant", 4), 3))
+    if fr is None:
+        fr = np.full(kw.get("n_fft", 256), 3.5e9)
+    keep = [None if a is None or isinstance(a, str) else np.ascontiguousarray(a, dtype=t)
+            for a, t in ((tx, np.float64), (fr, np.float64), (table, np.complex128))]
+    ptr = [None if a is None else a.view(np.float64).ctypes.data_as(dp) for a in keep]
     base = dict(n_ant=4, n_sub_carr=128, n_fft=256, constel_size=16, cp_len=16, channel_kind=1, receiver_kind=1,
                 device=-1, rx_loc_var=10.0, reroll_chan=1, precision=0)
     base.update(kw)
-    c = _engine.MimoConfig(**base, tx_pos=tx.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                           carrier_freqs=fr.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
-    return c, (tx, fr)
+    c = _engine.MimoConfig(**base, tx_pos=ptr[0], carrier_freqs=ptr[1], chan_table=ptr[2])
+    c.rx_pos[:] = [float(v) for v in rx_pos]
+    return c, keep
 
 
 @pytest.mark.parametrize("kw,msg", [
@@ -71,6 +80,176 @@ def test_create_rejects_invalid_configs(kw, msg):
     h = lib.mimo_engine_create(ctypes.byref(c))
     assert not h
     assert msg in lib.mimo_last_error().decode()
+
+
+NAN, INF = float("nan"), float("inf")
+
+
+def _geo(**kw):
+    """_cfg on a geometry that can run: antennas 1 m apart on a line 15 m up (_line), the default user."""
+    kw.setdefault("tx", _line())
+    kw.setdefault("rx_pos", (212.0, 212.0, 1.5))
+    return _cfg(**kw)
+
+
+def _line(n_ant=4, **cells):
+    """_geo's antennas with single coordinates replaced: a1y=NAN sets antenna 1's y."""
+    tx = np.stack([np.arange(n_ant, dtype=np.float64), np.zeros(n_ant), np.full(n_ant, 15.0)], axis=1)
+    for key, v in cells.items():
+        tx[int(key[1:-1]), "xyz".index(key[-1])] = v
+    return tx
+
+
+def _freqs(n_fft=256, **bins):
+    """_cfg's carriers with single bins replaced: b5=0.0 sets bin 5."""
+    fr = np.full(n_fft, 3.5e9)
+    for key, v in bins.items():
+        fr[int(key[1:])] = v
+    return fr
+
+
+def _table(n_ant=4, n_fft=256, **cells):
+    """A finite channel table with single entries replaced: a3k255=NAN sets antenna 3, bin 255."""
+    tab = np.full((n_ant, n_fft), 0.5 - 0.25j)
+    for key, v in cells.items():
+        a, k = key[1:].split("k")
+        tab[int(a), int(k)] = v
+    return tab
+
+
+RAYLEIGH, LOS, TWOPATH, TABLE = 1, 2, 3, 4
+GEOMETRY_REJECTS = {
+    # tx_pos: all 3 n_ant values finite -- each coordinate, the first and the last antenna
+    "tx_nan_first_x": (dict(tx=_line(a0x=NAN)), "tx_pos must be finite"),
+    "tx_inf_y": (dict(tx=_line(a1y=INF)), "tx_pos must be finite"),
+    "tx_minus_inf_last_z": (dict(tx=_line(a3z=-INF)), "tx_pos must be finite"),
+    "tx_nan_table_channel": (dict(tx=_line(a2z=NAN), channel_kind=TABLE, table=_table()), "tx_pos must be finite"),
+    # rx_pos: finite, each coordinate
+    "rx_nan_x": (dict(rx_pos=(NAN, 212.0, 1.5)), "rx_pos must be finite"),
+    "rx_inf_y": (dict(rx_pos=(212.0, INF, 1.5)), "rx_pos must be finite"),
+    "rx_minus_inf_z": (dict(rx_pos=(212.0, 212.0, -INF)), "rx_pos must be finite"),
+    "rx_nan_los": (dict(rx_pos=(NAN, 212.0, 1.5), channel_kind=LOS), "rx_pos must be finite"),
+    # rx_loc_var: finite and >= 0
+    "var_nan": (dict(rx_loc_var=NAN), "rx_loc_var must be finite and >= 0"),
+    "var_inf": (dict(rx_loc_var=INF), "rx_loc_var must be finite and >= 0"),
+    "var_minus_inf": (dict(rx_loc_var=-INF), "rx_loc_var must be finite and >= 0"),
+    "var_negative": (dict(rx_loc_var=-10.0, channel_kind=LOS), "rx_loc_var must be finite and >= 0"),
+    # carrier_freqs: required, all n_fft values finite and > 0
+    "freqs_null": (dict(fr="null"), "carrier_freqs is required"),
+    "freq_nan_centre": (dict(fr=_freqs(b0=NAN)), "carrier_freqs must be finite and > 0"),
+    "freq_inf": (dict(fr=_freqs(b7=INF)), "carrier_freqs must be finite and > 0"),
+    "freq_minus_inf": (dict(fr=_freqs(b128=-INF)), "carrier_freqs must be finite and > 0"),
+    "freq_zero_last_bin": (dict(fr=_freqs(b255=0.0)), "carrier_freqs must be finite and > 0"),
+    "freq_negative": (dict(fr=_freqs(b200=-3.5e9)), "carrier_freqs must be finite and > 0"),
+    "freq_zero_out_of_band": (dict(fr=_freqs(b128=0.0)), "carrier_freqs must be finite and > 0"),
+    # TABLE: every entry finite
+    "table_nan_real": (dict(channel_kind=TABLE, table=_table(a0k0=NAN)), "chan_table must be finite"),
+    "table_inf_imag_last": (dict(channel_kind=TABLE, table=_table(a3k255=complex(0.0, INF))), "chan_table must be finite"),
+    "table_minus_inf_out_of_band": (dict(channel_kind=TABLE, table=_table(a1k128=-INF)), "chan_table must be finite"),
+}
+# the rule every run call checks: the distances the channel divides by
+DISTANCE_REJECTS = {
+    # every channel but TABLE: no antenna at rx_pos
+    "user_on_antenna_rayleigh": (dict(rx_pos=(2.0, 0.0, 15.0)), "rx_pos is no finite distance > 0 from antenna 2"),
+    "user_on_antenna_los": (dict(rx_pos=(3.0, 0.0, 15.0), channel_kind=LOS),
+                            "rx_pos is no finite distance > 0 from antenna 3"),
+    "user_on_antenna_two_path": (dict(rx_pos=(0.0, 0.0, 15.0), channel_kind=TWOPATH),
+                                 "rx_pos is no finite distance > 0 from antenna 0"),
+    # ... nor so close that the distance rounds to 0 (the square of 1e-170 underflows)
+    "user_at_rounding_distance": (dict(rx_pos=(1e-170, 0.0, 15.0)), "rx_pos is no finite distance > 0 from antenna 0"),
+    # ... nor so far that it overflows
+    "user_beyond_overflow": (dict(rx_pos=(1e200, 0.0, 15.0)), "rx_pos is no finite distance > 0 from antenna 0"),
+    # LoS and two-path also: no antenna at (rx_pos[0], rx_pos[0], rx_pos[2]), the jitter's centre
+    "jitter_centre_on_antenna_los": (dict(rx_pos=(5.0, 9.0, 15.0), tx=_line(a1x=5.0, a1y=5.0), channel_kind=LOS),
+                                     "rx_pos: the jitter's centre"),
+    "jitter_centre_on_antenna_two_path": (dict(rx_pos=(5.0, 9.0, 15.0), tx=_line(a3x=5.0, a3y=5.0),
+                                               channel_kind=TWOPATH), "rx_pos: the jitter's centre"),
+    # what the host tests of earlier rounds build: every antenna and the user at the origin
+    "everything_at_the_origin": (dict(tx=np.zeros((4, 3)), rx_pos=(0.0, 0.0, 0.0)),
+                                 "rx_pos is no finite distance > 0 from antenna 0"),
+}
+
+
+@pytest.mark.parametrize("name", sorted(GEOMETRY_REJECTS))
+def test_create_rejects_a_broken_geometry_by_field(name):
+    """The geometry rules of mimo_config (include/mimo_engine.h): a NaN or infinite coordinate, a
+    negative or non-finite jitter span, a carrier frequency that is missing, 0, negative or not
+    finite, a non-finite table entry -- each used to reach the kernel and come back as
+    ordinary-looking counts.  Now a null engine and a message that starts with the field; all
+    host-side, no HIP call."""
+    lib = _engine.lib()
+    kw, msg = GEOMETRY_REJECTS[name]
+    c, keep = _geo(**kw)
+    h = lib.mimo_engine_create(ctypes.byref(c))
+    if h:
+        lib.mimo_engine_destroy(h)
+    assert not h, f"{name}: accepted"
+    assert lib.mimo_last_error().decode().startswith(msg), lib.mimo_last_error()
+
+
+@pytest.mark.parametrize("kw", [
+    dict(rx_loc_var=0.0),                                              # a fixed user
+    dict(rx_loc_var=0.0, channel_kind=LOS),
+    dict(rx_pos=(-212.0, -212.0, -1.5), tx=_line(a0x=-3.0, a0z=-15.0)),  # negative coordinates
+    dict(fr=_freqs(b0=1.0, b255=5e-324)),                              # any frequency > 0
+])
+def test_create_keeps_every_legitimate_geometry(kw):
+    lib = _engine.lib()
+    c, keep = _geo(**kw)
+    h = lib.mimo_engine_create(ctypes.byref(c))
+    assert h, lib.mimo_last_error()
+    lib.mimo_engine_destroy(h)
+
+
+@pytest.mark.parametrize("name", sorted(DISTANCE_REJECTS))
+def test_run_refuses_an_antenna_at_the_user_before_any_hip_call(name):
+    """A user standing on an antenna (the attenuation's distance 0: ant_rel = inf), at a distance
+    that rounds to 0 or overflows, or, for LoS / two-path, an antenna at the centre the jitter is
+    really drawn around, used to run and come back as ordinary-looking counts.  The engine can be
+    created, described and given a point as before -- no run, no division -- and
+    mimo_engine_run and mimo_engine_run_points are MIMO_EINVAL with a message that starts with the
+    field, host-side: on a machine without a GPU a HIP call would be MIMO_EHIP instead."""
+    lib = _engine.lib()
+    kw, msg = DISTANCE_REJECTS[name]
+    c, keep = _geo(**kw)
+    h = lib.mimo_engine_create(ctypes.byref(c))
+    assert h, lib.mimo_last_error()
+    good = _engine.Engine.make_point(**GOOD_POINT)
+    assert lib.mimo_engine_set_point(h, ctypes.byref(good)) == 0
+    assert lib.mimo_engine_describe(h).decode().startswith("F=256")
+    it = np.zeros(1, np.int32)
+    err, bits = np.zeros(1, np.uint64), np.zeros(1, np.uint64)
+    u64 = ctypes.POINTER(ctypes.c_uint64)
+    rc = lib.mimo_engine_run(h, 1, 0, 4, it.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), 1, 0,
+                             err.ctypes.data_as(u64), bits.ctypes.data_as(u64), None)
+    assert rc == -1 and not err.any() and not bits.any()  # MIMO_EINVAL
+    assert lib.mimo_last_error().decode().startswith(msg), lib.mimo_last_error()
+    assert _run_points_rc(lib, h, [good, good]) == -1
+    assert lib.mimo_last_error().decode().startswith(msg), lib.mimo_last_error()
+    lib.mimo_engine_destroy(h)
+
+
+def test_engine_class_surfaces_the_geometry_message():
+    """_engine.Engine raises the library's message, as for the other config errors: ValueError
+    from the constructor, EngineError from run and from the measure, spectrum and beam modes."""
+    good = dict(n_ant=4, n_sub_carr=128, n_fft=256, constel_size=16, cp_len=16, channel="los", receiver="cnc",
+                tx_pos=_line(), rx_pos=(212.0, 212.0, 1.5), rx_loc_var=10.0, carrier_freqs=_freqs())
+    _engine.Engine(**good).close()
+    for change, msg in ((dict(carrier_freqs=_freqs(b9=0.0)), "carrier_freqs must be finite and > 0 \\(bin 9\\)"),
+                        (dict(tx_pos=_line(a2z=NAN)), "tx_pos must be finite \\(antenna 2\\)"),
+                        (dict(rx_loc_var=-1.0), "rx_loc_var must be finite and >= 0"),
+                        (dict(channel="table", chan_table=_table(a1k3=NAN)), "chan_table must be finite \\(antenna 1\\)")):
+        with pytest.raises(ValueError, match=msg):
+            _engine.Engine(**dict(good, **change))
+    eng = _engine.Engine(**dict(good, rx_pos=(1.0, 1.0, 15.0), tx_pos=_line(a1y=1.0)))
+    eng.set_point(**GOOD_POINT)
+    msg = "rx_pos is no finite distance > 0 from antenna 1"
+    probes = np.array([[212.0, 212.0, 1.5]])
+    for call in (lambda: eng.run(1, 0, 4, [0]), lambda: eng.measure(1, 0, 4, [0]), lambda: eng.spectrum(1, 0, 4, [0]),
+                 lambda: eng.beam(1, 0, 4, [0], probes)):
+        with pytest.raises(_engine.EngineError, match=msg):
+            call()
+    eng.close()
 
 
 def test_valid_engine_is_host_only_until_run():
