@@ -452,30 +452,55 @@ class Engine:
         _check(self._L.mimo_engine_set_point(self._h, ctypes.byref(pt)))
         self._point = pt  # the one-point measure() runs it
 
-    def run_points(self, points, seeds, first_trials, n_trials, iters, incl_clean=False, per_trial=False):
-        """Many grid points in as few launches as possible (mimo_engine_run_points).
-        points: list of dicts (make_point keywords) or MimoPoint.  -> (err[P, n_idx],
-        bits[P, n_idx], per_trial[sum n_trials, n_idx] or None)."""
+    def _points_call(self, name, points, seeds, first_trials, n_trials, iters, incl_clean, per_trial, rows=None):
+        """Marshals a ``mimo_engine_*_points`` call and makes it (``name``: the C function).
+        ``rows``: None for a plain run, else ``n_idx -> (shape of a point's row, the C arguments
+        that stand ahead of the row pointers)``.  -> (err, bits, per-trial counts or None), for a
+        row mode (err, bits, rows[P, *shape], per-trial counts, per-trial rows [sum n_trials, *shape])."""
         P = len(points)
         arr = (MimoPoint * max(1, P))()
         for i, pt in enumerate(points):
             arr[i] = pt if isinstance(pt, MimoPoint) else self.make_point(**pt)
         it = _c(sorted(set(int(i) for i in iters)), np.int32)
         n_idx = len(it) + (1 if incl_clean else 0)
+        shape, lead = rows(n_idx) if rows else (None, ())
         sd = _c(np.asarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], dtype=np.uint64).reshape(-1), np.uint64)
         ft = _c(np.asarray(first_trials, dtype=np.uint64).reshape(-1), np.uint64)
         nt = _c(np.asarray(n_trials, dtype=np.uint64).reshape(-1), np.uint64)
         if not (len(sd) == len(ft) == len(nt) == P):
             raise ValueError("points, seeds, first_trials and n_trials must have the same length")
-        err = np.zeros((P, n_idx), np.uint64)
-        bits = np.zeros((P, n_idx), np.uint64)
-        pt = np.zeros((int(nt.sum()), n_idx), np.uint32) if per_trial else None
-        _check(self._L.mimo_engine_run_points(self._h, P, arr, _ptr(sd, ctypes.c_uint64), _ptr(ft, ctypes.c_uint64),
-                                              _ptr(nt, ctypes.c_uint64), _ptr(it, ctypes.c_int32), len(it),
-                                              int(bool(incl_clean)), _ptr(err, ctypes.c_uint64),
-                                              _ptr(bits, ctypes.c_uint64),
-                                              _ptr(pt, ctypes.c_uint32) if pt is not None else None))
-        return err, bits, pt
+
+        def out(shape, dtype, ctype, wanted=True):
+            a = np.zeros(shape, dtype) if wanted else None
+            return a, (_ptr(a, ctype) if wanted else None)
+
+        err, p_err = out((P, n_idx), np.uint64, ctypes.c_uint64)
+        bits, p_bits = out((P, n_idx), np.uint64, ctypes.c_uint64)
+        pt, p_pt = out((int(nt.sum()), n_idx), np.uint32, ctypes.c_uint32, per_trial)
+        args = [self._h, P, arr, _ptr(sd, ctypes.c_uint64), _ptr(ft, ctypes.c_uint64), _ptr(nt, ctypes.c_uint64),
+                _ptr(it, ctypes.c_int32), len(it), int(bool(incl_clean)), p_err, p_bits, p_pt]
+        if shape is None:
+            _check(getattr(self._L, name)(*args))
+            return err, bits, pt
+        tot, p_tot = out((P,) + shape, np.float64, ctypes.c_double)
+        pr, p_pr = out((int(nt.sum()),) + shape, np.float64, ctypes.c_double, per_trial)
+        _check(getattr(self._L, name)(*args, *lead, p_tot, p_pr))
+        return err, bits, tot, pt, pr
+
+    def _one_point(self, point):
+        """The point of a one-point row-mode call: ``point``, or the last set_point's."""
+        if point is None:
+            point = getattr(self, "_point", None)
+            if point is None:
+                raise EngineError("mimo_engine_set_point was not called")
+        return point
+
+    def run_points(self, points, seeds, first_trials, n_trials, iters, incl_clean=False, per_trial=False):
+        """Many grid points in as few launches as possible (mimo_engine_run_points).
+        points: list of dicts (make_point keywords) or MimoPoint.  -> (err[P, n_idx],
+        bits[P, n_idx], per_trial[sum n_trials, n_idx] or None)."""
+        return self._points_call("mimo_engine_run_points", points, seeds, first_trials, n_trials, iters, incl_clean,
+                                 per_trial)
 
     def run(self, seed, first_trial, n_trials, iters, incl_clean=False, per_trial=False):
         """-> (err[n_idx], bits[n_idx], per_trial[n_trials, n_idx] or None)."""
@@ -495,39 +520,14 @@ class Engine:
         trials and counts, and per point the row of signal / distortion power sums.
         -> (err[P, n_idx], bits[P, n_idx], meas[P, n_meas], per-trial counts [sum n_trials, n_idx]
         or None, per-trial rows [sum n_trials, n_meas] or None); SignalStats(meas[i], err[i], bits[i])."""
-        P = len(points)
-        arr = (MimoPoint * max(1, P))()
-        for i, pt in enumerate(points):
-            arr[i] = pt if isinstance(pt, MimoPoint) else self.make_point(**pt)
-        it = _c(sorted(set(int(i) for i in iters)), np.int32)
-        n_idx = len(it) + (1 if incl_clean else 0)
-        n_meas = MEAS_FIXED + n_idx
-        sd = _c(np.asarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], dtype=np.uint64).reshape(-1), np.uint64)
-        ft = _c(np.asarray(first_trials, dtype=np.uint64).reshape(-1), np.uint64)
-        nt = _c(np.asarray(n_trials, dtype=np.uint64).reshape(-1), np.uint64)
-        if not (len(sd) == len(ft) == len(nt) == P):
-            raise ValueError("points, seeds, first_trials and n_trials must have the same length")
-        err = np.zeros((P, n_idx), np.uint64)
-        bits = np.zeros((P, n_idx), np.uint64)
-        meas = np.zeros((P, n_meas), np.float64)
-        pt = np.zeros((int(nt.sum()), n_idx), np.uint32) if per_trial else None
-        pm = np.zeros((int(nt.sum()), n_meas), np.float64) if per_trial else None
-        _check(self._L.mimo_engine_measure_points(
-            self._h, P, arr, _ptr(sd, ctypes.c_uint64), _ptr(ft, ctypes.c_uint64), _ptr(nt, ctypes.c_uint64),
-            _ptr(it, ctypes.c_int32), len(it), int(bool(incl_clean)), _ptr(err, ctypes.c_uint64),
-            _ptr(bits, ctypes.c_uint64), _ptr(pt, ctypes.c_uint32) if pt is not None else None,
-            _ptr(meas, ctypes.c_double), _ptr(pm, ctypes.c_double) if pm is not None else None))
-        return err, bits, meas, pt, pm
+        return self._points_call("mimo_engine_measure_points", points, seeds, first_trials, n_trials, iters,
+                                 incl_clean, per_trial, lambda n_idx: ((MEAS_FIXED + n_idx,), ()))
 
     def measure(self, seed, first_trial, n_trials, iters, incl_clean=False, per_trial=False, point=None):
         """One point (the last set_point's, or ``point``: make_point keywords / MimoPoint).
         -> (err[n_idx], bits[n_idx], meas[n_meas], per-trial counts or None, per-trial rows or None)."""
-        if point is None:
-            point = getattr(self, "_point", None)
-            if point is None:
-                raise EngineError("mimo_engine_set_point was not called")
-        err, bits, meas, pt, pm = self.measure_points([point], [seed], [first_trial], [n_trials], iters, incl_clean,
-                                                      per_trial)
+        err, bits, meas, pt, pm = self.measure_points([self._one_point(point)], [seed], [first_trial], [n_trials],
+                                                      iters, incl_clean, per_trial)
         return err[0], bits[0], meas[0], pt, pm
 
     def spectrum_points(self, points, seeds, first_trials, n_trials, iters, incl_clean=False, per_trial=False):
@@ -535,39 +535,14 @@ class Engine:
         trials and counts, and per point the row of the array's radiated PSD per FFT bin, Ex and C.
         -> (err[P, n_idx], bits[P, n_idx], spec[P, n_spec], per-trial counts [sum n_trials, n_idx]
         or None, per-trial rows [sum n_trials, n_spec] or None); SpectrumStats(spec[i], n_sub_carr)."""
-        P = len(points)
-        arr = (MimoPoint * max(1, P))()
-        for i, pt in enumerate(points):
-            arr[i] = pt if isinstance(pt, MimoPoint) else self.make_point(**pt)
-        it = _c(sorted(set(int(i) for i in iters)), np.int32)
-        n_idx = len(it) + (1 if incl_clean else 0)
-        n_spec = self.n_fft + SPEC_FIXED
-        sd = _c(np.asarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], dtype=np.uint64).reshape(-1), np.uint64)
-        ft = _c(np.asarray(first_trials, dtype=np.uint64).reshape(-1), np.uint64)
-        nt = _c(np.asarray(n_trials, dtype=np.uint64).reshape(-1), np.uint64)
-        if not (len(sd) == len(ft) == len(nt) == P):
-            raise ValueError("points, seeds, first_trials and n_trials must have the same length")
-        err = np.zeros((P, n_idx), np.uint64)
-        bits = np.zeros((P, n_idx), np.uint64)
-        spec = np.zeros((P, n_spec), np.float64)
-        pt = np.zeros((int(nt.sum()), n_idx), np.uint32) if per_trial else None
-        ps = np.zeros((int(nt.sum()), n_spec), np.float64) if per_trial else None
-        _check(self._L.mimo_engine_spectrum_points(
-            self._h, P, arr, _ptr(sd, ctypes.c_uint64), _ptr(ft, ctypes.c_uint64), _ptr(nt, ctypes.c_uint64),
-            _ptr(it, ctypes.c_int32), len(it), int(bool(incl_clean)), _ptr(err, ctypes.c_uint64),
-            _ptr(bits, ctypes.c_uint64), _ptr(pt, ctypes.c_uint32) if pt is not None else None,
-            _ptr(spec, ctypes.c_double), _ptr(ps, ctypes.c_double) if ps is not None else None))
-        return err, bits, spec, pt, ps
+        return self._points_call("mimo_engine_spectrum_points", points, seeds, first_trials, n_trials, iters,
+                                 incl_clean, per_trial, lambda n_idx: ((self.n_fft + SPEC_FIXED,), ()))
 
     def spectrum(self, seed, first_trial, n_trials, iters, incl_clean=False, per_trial=False, point=None):
         """One point (the last set_point's, or ``point``: make_point keywords / MimoPoint).
         -> (err[n_idx], bits[n_idx], spec[n_spec], per-trial counts or None, per-trial rows or None)."""
-        if point is None:
-            point = getattr(self, "_point", None)
-            if point is None:
-                raise EngineError("mimo_engine_set_point was not called")
-        err, bits, spec, pt, ps = self.spectrum_points([point], [seed], [first_trial], [n_trials], iters, incl_clean,
-                                                       per_trial)
+        err, bits, spec, pt, ps = self.spectrum_points([self._one_point(point)], [seed], [first_trial], [n_trials],
+                                                       iters, incl_clean, per_trial)
         return err[0], bits[0], spec[0], pt, ps
 
     def beam_points(self, points, seeds, first_trials, n_trials, iters, probes, incl_clean=False, per_trial=False):
@@ -576,43 +551,20 @@ class Engine:
         every point) the row ``[Py_in, Py_oob, Px, Re C, Im C]``.
         -> (err[P, n_idx], bits[P, n_idx], beam[P, n_probes, 5], per-trial counts [sum n_trials, n_idx]
         or None, per-trial rows [sum n_trials, n_probes, 5] or None); BeamStats(beam[i])."""
-        P = len(points)
-        arr = (MimoPoint * max(1, P))()
-        for i, pt in enumerate(points):
-            arr[i] = pt if isinstance(pt, MimoPoint) else self.make_point(**pt)
-        it = _c(sorted(set(int(i) for i in iters)), np.int32)
-        n_idx = len(it) + (1 if incl_clean else 0)
-        pr = _c(probes, np.float64)
-        if pr.ndim != 2 or pr.shape[1] != 3:
-            raise ValueError("probes must be [n_probes, 3]")
-        nq = pr.shape[0]
-        sd = _c(np.asarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], dtype=np.uint64).reshape(-1), np.uint64)
-        ft = _c(np.asarray(first_trials, dtype=np.uint64).reshape(-1), np.uint64)
-        nt = _c(np.asarray(n_trials, dtype=np.uint64).reshape(-1), np.uint64)
-        if not (len(sd) == len(ft) == len(nt) == P):
-            raise ValueError("points, seeds, first_trials and n_trials must have the same length")
-        err = np.zeros((P, n_idx), np.uint64)
-        bits = np.zeros((P, n_idx), np.uint64)
-        beam = np.zeros((P, nq, BEAM_FIXED), np.float64)
-        pt = np.zeros((int(nt.sum()), n_idx), np.uint32) if per_trial else None
-        pb = np.zeros((int(nt.sum()), nq, BEAM_FIXED), np.float64) if per_trial else None
-        _check(self._L.mimo_engine_beam_points(
-            self._h, P, arr, _ptr(sd, ctypes.c_uint64), _ptr(ft, ctypes.c_uint64), _ptr(nt, ctypes.c_uint64),
-            _ptr(it, ctypes.c_int32), len(it), int(bool(incl_clean)), _ptr(err, ctypes.c_uint64),
-            _ptr(bits, ctypes.c_uint64), _ptr(pt, ctypes.c_uint32) if pt is not None else None,
-            _ptr(pr, ctypes.c_double), nq, _ptr(beam, ctypes.c_double),
-            _ptr(pb, ctypes.c_double) if pb is not None else None))
-        return err, bits, beam, pt, pb
+        def rows(n_idx):
+            pr = _c(probes, np.float64)
+            if pr.ndim != 2 or pr.shape[1] != 3:
+                raise ValueError("probes must be [n_probes, 3]")
+            return (pr.shape[0], BEAM_FIXED), (_ptr(pr, ctypes.c_double), pr.shape[0])
+
+        return self._points_call("mimo_engine_beam_points", points, seeds, first_trials, n_trials, iters, incl_clean,
+                                 per_trial, rows)
 
     def beam(self, seed, first_trial, n_trials, iters, probes, incl_clean=False, per_trial=False, point=None):
         """One point (the last set_point's, or ``point``: make_point keywords / MimoPoint).
         -> (err[n_idx], bits[n_idx], beam[n_probes, 5], per-trial counts or None, per-trial rows or None)."""
-        if point is None:
-            point = getattr(self, "_point", None)
-            if point is None:
-                raise EngineError("mimo_engine_set_point was not called")
-        err, bits, beam, pt, pb = self.beam_points([point], [seed], [first_trial], [n_trials], iters, probes,
-                                                   incl_clean, per_trial)
+        err, bits, beam, pt, pb = self.beam_points([self._one_point(point)], [seed], [first_trial], [n_trials], iters,
+                                                   probes, incl_clean, per_trial)
         return err[0], bits[0], beam[0], pt, pb
 
     @property

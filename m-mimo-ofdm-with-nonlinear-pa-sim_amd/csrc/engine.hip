@@ -45,6 +45,43 @@ constexpr double kSpeedOfLight = 299792458.0;  // scipy.constants.c
 
 bool is_pow2(long v) { return v > 0 && (v & (v - 1)) == 0; }
 
+// In-band sub-carrier k of S -> FFT bin of F (modulation.py:266-267).
+int band_bin(int k, int S, int F) { return k < S / 2 ? F - S / 2 + k : k - S / 2 + 1; }
+
+// An owned device (PINNED: pinned host) array that only grows; growing drops the contents.
+// It makes no HIP call while it holds nothing, so an engine that never ran stays host-only.
+template <typename T, bool PINNED = false>
+struct Buf {
+  T* p = nullptr;
+  size_t cap = 0;  // elements
+  Buf() = default;
+  Buf(const Buf&) = delete;
+  Buf& operator=(const Buf&) = delete;
+  ~Buf() { (void)release(); }
+  hipError_t release() {
+    T* old = p;
+    p = nullptr;
+    cap = 0;
+    if (!old) return hipSuccess;
+    if constexpr (PINNED) return hipHostFree(old);
+    else return hipFree(old);
+  }
+  int ensure(size_t need) {
+    if (need <= cap) return MIMO_OK;
+    HIP_TRY(release());
+    if constexpr (PINNED) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p), need * sizeof(T), hipHostMallocDefault));
+    else HIP_TRY(hipMalloc(&p, need * sizeof(T)));
+    cap = need;
+    return MIMO_OK;
+  }
+  int upload(const std::vector<T>& v) {  // a blocking copy; an empty table stays a null pointer
+    if (v.empty()) return MIMO_OK;
+    if (int rc = ensure(v.size())) return rc;
+    HIP_TRY(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return MIMO_OK;
+  }
+};
+
 // Per-point sums of the per-trial counts of one launch: block (k, idx) adds the counts of
 // trial blocks [first[k], first[k + 1]) -- a slice of at most kSlice trials of one point --
 // into tot[point_of[k]][idx] (integer sums: the order does not matter; one 64-bit atomic
@@ -114,69 +151,63 @@ struct mimo_engine {
   std::vector<double> chan_inband;        // MIMO_CH_TABLE: [A][S] (re, im), sub-carrier order k
   mimo_point pt{};
   bool have_point = false;
-  // device state (created lazily on the first run: fork safety)
+  // device state (created lazily on the first run: fork safety); whatever of it exists is released
+  // with the engine, whether or not ensure_device came through
   bool ready = false;
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  float2* d_tw[2] = {nullptr, nullptr};  // fp32 stage twiddles for team_size(F), alt_team_size(F)
-  double2* d_tw64 = nullptr;              // fp64 stage twiddles for team_size64(F)
-  double2* d_twave64 = nullptr;           // wave-split FFT twiddles (wave_fft.h) where the instance uses it
-  float2* d_twave32 = nullptr;
-  double2* d_lut64 = nullptr;             // fp64 Box-Muller tables (lut64_table)
-  float2* d_tab32 = nullptr;              // MIMO_CH_TABLE channel, fp32 / fp64 copies
-  double2* d_tab64 = nullptr;
-  float* d_ant_rel = nullptr;
-  float* d_f_rel = nullptr;
-  double* d_ant_rel64 = nullptr;
-  double* d_f_rel64 = nullptr;
-  double* d_f_over_c = nullptr;
-  double* d_tx_pos = nullptr;
-  uint32_t* d_counts = nullptr;
-  size_t counts_cap = 0;
-  unsigned long long* d_tot = nullptr;    // [points][n_idx] totals of one run
-  size_t tot_cap = 0;
-  // measure calls (mimo_engine_measure_points): per-trial rows of one launch, per-slice partials
-  double* d_meas = nullptr;               // [launch blocks][n_meas]
-  size_t meas_cap = 0;
-  double* d_mpart = nullptr;              // [launch slices][n_meas]
-  size_t mpart_cap = 0;
-  // spectrum calls (mimo_engine_spectrum_points): the same pair, rows of n_fft + MIMO_SPEC_FIXED;
-  // d_spec holds at most MIMO_SPEC_BUFFER_BYTES (it bounds the trials of a spectrum launch)
-  double* d_spec = nullptr;               // [launch blocks][n_spec]
-  size_t spec_cap = 0;
-  double* d_spart = nullptr;              // [launch slices][n_spec]
-  size_t spart_cap = 0;
-  // beam calls (mimo_engine_beam_points): the beam instances' cells of one launch (at most the
-  // beam buffer's bytes: it bounds the trials of a beam launch), the probe geometry, and the
-  // same pair of per-trial rows and slice partials, rows of n_probes MIMO_BEAM_FIXED
-  double* d_bcell = nullptr;              // [2][launch blocks][A][F] complex128
-  size_t bcell_cap = 0;
-  double* d_bgeo = nullptr;               // dist [n_probes][A] | 1 / dist [n_probes][A] | f / c [F]
-  size_t bgeo_cap = 0;
-  double* d_beam = nullptr;               // [launch blocks][n_probes][MIMO_BEAM_FIXED]
-  size_t beam_cap = 0;
-  double* d_bpart = nullptr;              // [launch slices][n_probes][MIMO_BEAM_FIXED]
-  size_t bpart_cap = 0;
   hipEvent_t ev2 = nullptr;               // after the beamforming kernel of a launch
+  Buf<float2> tw[2];                      // fp32 stage twiddles for team_size(F), alt_team_size(F)
+  Buf<double2> tw64;                      // fp64 stage twiddles for team_size64(F)
+  Buf<double2> twave64;                   // wave-split FFT twiddles (wave_fft.h) where the instance uses it
+  Buf<float2> twave32;
+  Buf<double2> lut64;                     // fp64 Box-Muller tables (lut64_table)
+  Buf<float2> tab32;                      // MIMO_CH_TABLE channel, fp32 / fp64 copies
+  Buf<double2> tab64;
+  Buf<float> ant_rel, f_rel;
+  Buf<double> ant_rel64, f_rel64, f_over_c, tx_pos_dev;
+  Buf<uint32_t> counts;
+  Buf<unsigned long long> tot;            // [points][n_idx] totals of one run
+  // row-mode calls (measure, spectrum, beam: one mode per call, so one pair): the per-trial rows of
+  // one launch and their per-slice partials.  Spectrum and beam rows hold at most
+  // MIMO_SPEC_BUFFER_BYTES / MIMO_BEAM_ROWS_BYTES (that bounds the trials of their launches).
+  Buf<double> rows;                       // [launch blocks][row width]
+  Buf<double> part;                       // [launch slices][row width]
+  // beam calls: the beam instances' cells of one launch (at most the beam buffer's bytes: it bounds
+  // the trials of a beam launch) and the probe geometry
+  Buf<double> bcell;                      // [2][launch blocks][A][F] complex128
+  Buf<double> bgeo;                       // dist [n_probes][A] | 1 / dist [n_probes][A] | f / c [F]
   double last_beam_ms = 0.0;
   // per-launch tables in one device blob, filled by one copy from a pinned host buffer:
   // TrialParams<R>[segments] | uint32 block offsets [segments + 1] |
   // uint32 reduction-slice starts [slices + 1] (<= kSlice trials, one point each) | int32 point of slice [slices]
-  char* d_blob = nullptr;
-  char* h_blob = nullptr;
-  size_t blob_cap = 0, hblob_cap = 0;
+  Buf<char> blob;
+  Buf<char, true> h_blob;
   double d0 = 1.0;
   double last_ms = 0.0;
   // fit_alpha results per IBO (bit pattern of 10^(IBO/10)): the long-double fit costs
   // ~0.3 ms, paid once per IBO instead of once per point and batch of a sweep
   std::unordered_map<uint64_t, AlphaFit> alpha_fits;
   std::string desc;
+
+  // (the buffers free themselves after this; no HIP call for an engine that never ran)
+  ~mimo_engine() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    for (hipEvent_t ev : {ev0, ev1, ev2})
+      if (ev) (void)hipEventDestroy(ev);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
 };
 
 namespace {
 
-int team_for(int F) { return mimo::team_size(F); }
+std::string describe(const mimo::InstanceKey& k) {
+  char buf[160];
+  snprintf(buf, sizeof buf, "F=%d T=%d slots=%d %s ch=%d csi=%d %s", k.F, k.T, k.nslot,
+           k.aligned ? "aligned" : "generic", k.ch, (int)k.csi, k.f64 ? "f64" : "f32");
+  return buf;
+}
 
 mimo::InstanceKey select_instance(const mimo_engine* e, bool csi) {
   mimo::InstanceKey k{};
@@ -187,22 +218,16 @@ mimo::InstanceKey select_instance(const mimo_engine* e, bool csi) {
     const int P = k.F / T;
     return (S % (4 * T) == 0) && S < k.F && (S / T == 8 || S / T == 4) && (S / T) < P;
   };
-  k.T = k.f64 ? mimo::team_size64(k.F) : team_for(k.F);
-  if (k.f64) {  // one team size per fp64 instance
-    const int P = k.F / k.T;
-    k.aligned = aligned_at(k.T);
-    k.nslot = k.aligned ? S / k.T : P;
-    k.ch = e->cfg.channel_kind;
-    k.csi = csi;
-    return k;
-  }
-  // Unaligned bands (S % 4T != 0) run the generic predicated path with P slots per
-  // thread; the alternative team has half the points per thread, which measured 1.5x
-  // faster there (60.7 vs 40.7 ms at S = 1000, F = 2048; profiles/r01/ab_generic.json).
-  if (!aligned_at(k.T) && mimo::alt_team_size(k.F) != k.T) k.T = mimo::alt_team_size(k.F);
-  if (const char* env = std::getenv("MIMO_TEAM")) {  // A/B override: MIMO_TEAM=<threads per trial>
-    const int t = std::atoi(env);
-    if (t == mimo::alt_team_size(k.F) || t == mimo::team_size(k.F)) k.T = t;
+  k.T = k.f64 ? mimo::team_size64(k.F) : mimo::team_size(k.F);  // one team size per fp64 instance
+  if (!k.f64) {
+    // Unaligned bands (S % 4T != 0) run the generic predicated path with P slots per
+    // thread; the alternative team has half the points per thread, which measured 1.5x
+    // faster there (60.7 vs 40.7 ms at S = 1000, F = 2048; profiles/r01/ab_generic.json).
+    if (!aligned_at(k.T) && mimo::alt_team_size(k.F) != k.T) k.T = mimo::alt_team_size(k.F);
+    if (const char* env = std::getenv("MIMO_TEAM")) {  // A/B override: MIMO_TEAM=<threads per trial>
+      const int t = std::atoi(env);
+      if (t == mimo::alt_team_size(k.F) || t == mimo::team_size(k.F)) k.T = t;
+    }
   }
   const int P = k.F / k.T;
   k.aligned = aligned_at(k.T);
@@ -212,95 +237,48 @@ mimo::InstanceKey select_instance(const mimo_engine* e, bool csi) {
   return k;
 }
 
-template <typename R>
-hipError_t launch(const mimo::InstanceKey& k, dim3 grid, hipStream_t st, const mimo::TrialParams<R>& p, bool* found,
-                  hipFuncAttributes* attr = nullptr) {
-  constexpr bool F64 = sizeof(R) == 8;
-#define MIMO_LAUNCH_F(FV)                                                                    \
-  if constexpr (F64) return mimo::launch_trial_F##FV##_f64(k, grid, st, p, found, attr);     \
-  else return mimo::launch_trial_F##FV##_f32(k, grid, st, p, found, attr);
-#ifdef MIMO_ONLY_F  // single-size diagnostic / A-B builds (Makefile targets ablation, variant)
-  if (k.F == MIMO_ONLY_F) {
-#if MIMO_ONLY_F == 2048
-    MIMO_LAUNCH_F(2048)
-#elif MIMO_ONLY_F == 4096
-    MIMO_LAUNCH_F(4096)
-#elif MIMO_ONLY_F == 8192
-    MIMO_LAUNCH_F(8192)
-#endif
-  }
+// The launcher of the key's instance in the given mode (trial_launch.h launch_trial).  The only
+// table over the FFT sizes; the combinations that are not built are not found.
+template <typename R, int MODE>
+hipError_t launch_sized(const mimo::InstanceKey& k, dim3 grid, hipStream_t st, const mimo::TrialParams<R>& p,
+                        bool* found, hipFuncAttributes* attr, double* out) {
   *found = false;
-  return hipSuccess;
+#ifdef MIMO_ONLY_F  // single-size diagnostic / A-B builds (Makefile targets ablation, variant): plain only
+  constexpr bool built = MODE == MIMO_MODE_PLAIN;
 #else
-  switch (k.F) {
-    case 128: MIMO_LAUNCH_F(128)
-    case 256: MIMO_LAUNCH_F(256)
-    case 512: MIMO_LAUNCH_F(512)
-    case 1024: MIMO_LAUNCH_F(1024)
-    case 2048: MIMO_LAUNCH_F(2048)
-    case 4096: MIMO_LAUNCH_F(4096)
-    case 8192: MIMO_LAUNCH_F(8192)
-    default: *found = false; return hipSuccess;
-  }
+  constexpr bool built = MODE == MIMO_MODE_PLAIN || sizeof(R) == 8;
 #endif
+  if constexpr (built) {
+#define MIMO_LAUNCH_F(FV) \
+  case FV: return mimo::launch_trial<FV, R, MODE>(k, grid, st, p, found, attr, out);
+    switch (k.F) {
+#ifdef MIMO_ONLY_F
+      MIMO_LAUNCH_F(MIMO_ONLY_F)
+#else
+      MIMO_LAUNCH_F(128)
+      MIMO_LAUNCH_F(256)
+      MIMO_LAUNCH_F(512)
+      MIMO_LAUNCH_F(1024)
+      MIMO_LAUNCH_F(2048)
+      MIMO_LAUNCH_F(4096)
+      MIMO_LAUNCH_F(8192)
+#endif
+      default: break;
+    }
 #undef MIMO_LAUNCH_F
-}
-
-// The measure instance of the key (float64 only); rows: [grid.x][n_meas] doubles.
-hipError_t launch_meas(const mimo::InstanceKey& k, dim3 grid, hipStream_t st, const mimo::TrialParams<double>& p,
-                       double* rows, bool* found) {
-  *found = false;
-#ifndef MIMO_ONLY_F  // the single-size diagnostic builds link no measure instances
-  switch (k.F) {
-    case 128: return mimo::launch_trial_F128_f64_meas(k, grid, st, p, found, nullptr, rows);
-    case 256: return mimo::launch_trial_F256_f64_meas(k, grid, st, p, found, nullptr, rows);
-    case 512: return mimo::launch_trial_F512_f64_meas(k, grid, st, p, found, nullptr, rows);
-    case 1024: return mimo::launch_trial_F1024_f64_meas(k, grid, st, p, found, nullptr, rows);
-    case 2048: return mimo::launch_trial_F2048_f64_meas(k, grid, st, p, found, nullptr, rows);
-    case 4096: return mimo::launch_trial_F4096_f64_meas(k, grid, st, p, found, nullptr, rows);
-    case 8192: return mimo::launch_trial_F8192_f64_meas(k, grid, st, p, found, nullptr, rows);
-    default: break;
   }
-#endif
   return hipSuccess;
 }
 
-// The spectrum instance of the key (float64 only); rows: [grid.x][F + MIMO_SPEC_FIXED] doubles.
-hipError_t launch_spec(const mimo::InstanceKey& k, dim3 grid, hipStream_t st, const mimo::TrialParams<double>& p,
-                       double* rows, bool* found) {
-  *found = false;
-#ifndef MIMO_ONLY_F  // the single-size diagnostic builds link no spectrum instances
-  switch (k.F) {
-    case 128: return mimo::launch_trial_F128_f64_spec(k, grid, st, p, found, nullptr, rows);
-    case 256: return mimo::launch_trial_F256_f64_spec(k, grid, st, p, found, nullptr, rows);
-    case 512: return mimo::launch_trial_F512_f64_spec(k, grid, st, p, found, nullptr, rows);
-    case 1024: return mimo::launch_trial_F1024_f64_spec(k, grid, st, p, found, nullptr, rows);
-    case 2048: return mimo::launch_trial_F2048_f64_spec(k, grid, st, p, found, nullptr, rows);
-    case 4096: return mimo::launch_trial_F4096_f64_spec(k, grid, st, p, found, nullptr, rows);
-    case 8192: return mimo::launch_trial_F8192_f64_spec(k, grid, st, p, found, nullptr, rows);
-    default: break;
+template <typename R>
+hipError_t launch(int mode, const mimo::InstanceKey& k, dim3 grid, hipStream_t st, const mimo::TrialParams<R>& p,
+                  bool* found, hipFuncAttributes* attr, double* out) {
+  switch (mode) {
+    case MIMO_MODE_MEAS: return launch_sized<R, MIMO_MODE_MEAS>(k, grid, st, p, found, attr, out);
+    case MIMO_MODE_SPEC: return launch_sized<R, MIMO_MODE_SPEC>(k, grid, st, p, found, attr, out);
+    case MIMO_MODE_BEAM: return launch_sized<R, MIMO_MODE_BEAM>(k, grid, st, p, found, attr, out);
+    default: return launch_sized<R, MIMO_MODE_PLAIN>(k, grid, st, p, found, attr, out);
   }
-#endif
-  return hipSuccess;
-}
-
-// The beam instance of the key (float64 only); cells: [2][grid.x][A][F] complex128.
-hipError_t launch_beam_inst(const mimo::InstanceKey& k, dim3 grid, hipStream_t st, const mimo::TrialParams<double>& p,
-                            double* cells, bool* found) {
-  *found = false;
-#ifndef MIMO_ONLY_F  // the single-size diagnostic builds link no beam instances
-  switch (k.F) {
-    case 128: return mimo::launch_trial_F128_f64_beam(k, grid, st, p, found, nullptr, cells);
-    case 256: return mimo::launch_trial_F256_f64_beam(k, grid, st, p, found, nullptr, cells);
-    case 512: return mimo::launch_trial_F512_f64_beam(k, grid, st, p, found, nullptr, cells);
-    case 1024: return mimo::launch_trial_F1024_f64_beam(k, grid, st, p, found, nullptr, cells);
-    case 2048: return mimo::launch_trial_F2048_f64_beam(k, grid, st, p, found, nullptr, cells);
-    case 4096: return mimo::launch_trial_F4096_f64_beam(k, grid, st, p, found, nullptr, cells);
-    case 8192: return mimo::launch_trial_F8192_f64_beam(k, grid, st, p, found, nullptr, cells);
-    default: break;
-  }
-#endif
-  return hipSuccess;
 }
 
 // A beam call's probes, checked and turned into the beamforming kernel's tables by the caller
@@ -308,7 +286,26 @@ hipError_t launch_beam_inst(const mimo::InstanceKey& k, dim3 grid, hipStream_t s
 struct BeamCall {
   int n_probes;
   std::vector<double> geo;
-  uint64_t max_trials;  // of one launch: the cells of so many trials fit the beam buffer, their rows the rows buffer
+};
+
+// What a row mode adds to a plain run, filled once by the extern "C" entry point of the mode:
+//  measure (mimo_engine_measure_points): the measure instance runs, and its per-trial rows of
+//   MIMO_MEAS_FIXED + n_idx sums are reduced per slice on the device (reduce_meas) and per point,
+//   in slice order, on the host;
+//  spectrum (mimo_engine_spectrum_points): rows of n_fft + MIMO_SPEC_FIXED sums; the spectrum
+//   instance runs, reduce_spec forms the slice partials, and a launch holds no more trials than
+//   its rows fit MIMO_SPEC_BUFFER_BYTES;
+//  beam (mimo_engine_beam_points): rows of n_probes MIMO_BEAM_FIXED sums; the beam instance runs
+//   and fills the launch's cells, the beamforming kernel (beam.hip) forms the per-trial rows from
+//   them, reduce_spec the slice partials; the cells and rows of a launch fit their buffers.
+struct RowMode {
+  int mode = MIMO_MODE_PLAIN;
+  int width = 0;                        // doubles of one trial's row, and of one point's in out
+  uint64_t max_trials = UINT64_MAX;     // of one launch, where the mode's buffers bound them
+  double* out = nullptr;                // [points][width], added into
+  double* per_trial_out = nullptr;      // [trials of the call][width], or null
+  const BeamCall* beam = nullptr;       // beam only
+  bool rows() const { return mode != MIMO_MODE_PLAIN; }
 };
 
 int validate_config(const mimo_config* c) {
@@ -460,24 +457,14 @@ void fill_point(mimo_engine* e, const mimo_point& pt, uint64_t seed, uint64_t fi
   p.csi_b = csi ? (R)pt.csi_eps : R(0);
 }
 
-template <typename T>
-int ensure_cap(T*& ptr, size_t& cap, size_t need) {
-  if (need <= cap) return MIMO_OK;
-  if (ptr) HIP_TRY(hipFree(ptr));
-  ptr = nullptr;
-  HIP_TRY(hipMalloc(&ptr, need * sizeof(T)));
-  cap = need;
-  return MIMO_OK;
-}
-
+// (A call after one that failed half-way keeps what that one created.)
 int ensure_device(mimo_engine* e) {
   if (e->ready) return MIMO_OK;
   if (e->cfg.device >= 0) HIP_TRY(hipSetDevice(e->cfg.device));
   HIP_TRY(hipGetDevice(&e->device));
-  HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-  HIP_TRY(hipEventCreate(&e->ev0));
-  HIP_TRY(hipEventCreate(&e->ev1));
-  HIP_TRY(hipEventCreate(&e->ev2));
+  if (!e->stream) HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+  for (hipEvent_t* ev : {&e->ev0, &e->ev1, &e->ev2})
+    if (!*ev) HIP_TRY(hipEventCreate(ev));
   const int F = e->cfg.n_fft, S = e->cfg.n_sub_carr, A = e->cfg.n_ant;
   // the FFT tables (host_tables.h): the team FFT's per team size, the split FFT's in place of
   // the fp64 team's where the instance runs it, the wave-split FFT's where used
@@ -500,8 +487,7 @@ int ensure_device(mimo_engine* e) {
   std::vector<double> f_rel64(S), f_over_c(S);
   const double fc = e->freqs[0];  // bin 0 = centre frequency
   for (int k = 0; k < S; ++k) {
-    const int bin = k < S / 2 ? F - S / 2 + k : k - S / 2 + 1;
-    const double f = e->freqs[bin];
+    const double f = e->freqs[band_bin(k, S, F)];
     // table channels carry their full attenuation: nothing is factored out of the loops
     f_rel64[k] = e->cfg.channel_kind == MIMO_CH_TABLE ? 1.0 : fc / f;
     f_rel[k] = (float)f_rel64[k];
@@ -524,44 +510,31 @@ int ensure_device(mimo_engine* e) {
     ant_rel[a] = (float)ant_rel64[a];
   }
 
-  for (int v = 0; v < 2; ++v) {
-    HIP_TRY(hipMalloc(&e->d_tw[v], sizeof(float2) * tws[v].size()));
-    HIP_TRY(hipMemcpy(e->d_tw[v], tws[v].data(), sizeof(float2) * tws[v].size(), hipMemcpyHostToDevice));
+  std::vector<float2> tab32;
+  std::vector<double2> tab64;
+  for (size_t i = 0; i < e->chan_inband.size() / 2; ++i) {
+    tab64.push_back(make_double2(e->chan_inband[2 * i], e->chan_inband[2 * i + 1]));
+    tab32.push_back(make_float2((float)e->chan_inband[2 * i], (float)e->chan_inband[2 * i + 1]));
   }
-  if (!e->chan_inband.empty()) {
-    const size_t n = e->chan_inband.size() / 2;
-    std::vector<float2> t32(n);
-    for (size_t i = 0; i < n; ++i) t32[i] = make_float2((float)e->chan_inband[2 * i], (float)e->chan_inband[2 * i + 1]);
-    HIP_TRY(hipMalloc(&e->d_tab32, sizeof(float2) * n));
-    HIP_TRY(hipMalloc(&e->d_tab64, sizeof(double2) * n));
-    HIP_TRY(hipMemcpy(e->d_tab32, t32.data(), sizeof(float2) * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->d_tab64, e->chan_inband.data(), sizeof(double2) * n, hipMemcpyHostToDevice));
-  }
-  const std::vector<double2> lut = mimo::lut64_table();
-  HIP_TRY(hipMalloc(&e->d_lut64, sizeof(double2) * lut.size()));
-  HIP_TRY(hipMemcpy(e->d_lut64, lut.data(), sizeof(double2) * lut.size(), hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&e->d_tw64, sizeof(double2) * tw64.size()));
-  HIP_TRY(hipMemcpy(e->d_tw64, tw64.data(), sizeof(double2) * tw64.size(), hipMemcpyHostToDevice));
-  if (!twave64.empty()) {
-    HIP_TRY(hipMalloc(&e->d_twave64, sizeof(double2) * twave64.size()));
-    HIP_TRY(hipMemcpy(e->d_twave64, twave64.data(), sizeof(double2) * twave64.size(), hipMemcpyHostToDevice));
-  }
-  if (!twave32.empty()) {
-    HIP_TRY(hipMalloc(&e->d_twave32, sizeof(float2) * twave32.size()));
-    HIP_TRY(hipMemcpy(e->d_twave32, twave32.data(), sizeof(float2) * twave32.size(), hipMemcpyHostToDevice));
-  }
-  HIP_TRY(hipMalloc(&e->d_f_rel64, sizeof(double) * S));
-  HIP_TRY(hipMalloc(&e->d_ant_rel64, sizeof(double) * A));
-  HIP_TRY(hipMemcpy(e->d_f_rel64, f_rel64.data(), sizeof(double) * S, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->d_ant_rel64, ant_rel64.data(), sizeof(double) * A, hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&e->d_f_rel, sizeof(float) * S));
-  HIP_TRY(hipMalloc(&e->d_f_over_c, sizeof(double) * S));
-  HIP_TRY(hipMalloc(&e->d_ant_rel, sizeof(float) * A));
-  HIP_TRY(hipMalloc(&e->d_tx_pos, sizeof(double) * 3 * A));
-  HIP_TRY(hipMemcpy(e->d_f_rel, f_rel.data(), sizeof(float) * S, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->d_f_over_c, f_over_c.data(), sizeof(double) * S, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->d_ant_rel, ant_rel.data(), sizeof(float) * A, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->d_tx_pos, e->tx_pos.data(), sizeof(double) * 3 * A, hipMemcpyHostToDevice));
+  int rc = MIMO_OK;  // the first upload that fails ends them
+  auto up = [&rc](auto& buf, const auto& v) {
+    if (rc == MIMO_OK) rc = buf.upload(v);
+  };
+  up(e->tw[0], tws[0]);
+  up(e->tw[1], tws[1]);
+  up(e->tab32, tab32);
+  up(e->tab64, tab64);
+  up(e->lut64, mimo::lut64_table());
+  up(e->tw64, tw64);
+  up(e->twave64, twave64);
+  up(e->twave32, twave32);
+  up(e->f_rel64, f_rel64);
+  up(e->ant_rel64, ant_rel64);
+  up(e->f_rel, f_rel);
+  up(e->f_over_c, f_over_c);
+  up(e->ant_rel, ant_rel);
+  up(e->tx_pos_dev, e->tx_pos);
+  if (rc) return rc;
   e->ready = true;
   return MIMO_OK;
 }
@@ -593,7 +566,7 @@ mimo_engine* mimo_engine_create(const mimo_config* cfg) {
     e->chan_inband.resize((size_t)A * S * 2);
     for (int a = 0; a < A; ++a)
       for (int k = 0; k < S; ++k) {
-        const int bin = k < S / 2 ? F - S / 2 + k : k - S / 2 + 1;
+        const int bin = band_bin(k, S, F);
         e->chan_inband[((size_t)a * S + k) * 2] = cfg->chan_table[((size_t)a * F + bin) * 2];
         e->chan_inband[((size_t)a * S + k) * 2 + 1] = cfg->chan_table[((size_t)a * F + bin) * 2 + 1];
       }
@@ -614,302 +587,359 @@ int32_t mimo_engine_set_point(mimo_engine* e, const mimo_point* pt) {
 
 namespace {
 
-// Runs n_points grid points of one system in as few launches as possible: every point's
-// trials become a contiguous range of blocks of one launch (split across launches only
-// beyond kChunk blocks), and a segmented reduction sums each point's counts.
-// meas_out != null (mimo_engine_measure_points): the measure instance runs instead, and its
-// per-trial rows of n_meas = MIMO_MEAS_FIXED + n_idx sums are reduced per slice on the device
-// (reduce_meas) and per point, in slice order, here.
-// spec (mimo_engine_spectrum_points): meas_out / per_trial_meas are the spectrum rows instead, of
-// n_fft + MIMO_SPEC_FIXED sums; the spectrum instance runs, reduce_spec forms the slice partials,
-// and a launch holds no more trials than its rows fit MIMO_SPEC_BUFFER_BYTES.
-// beam (mimo_engine_beam_points): the rows are n_probes MIMO_BEAM_FIXED sums; the beam instance
-// runs and fills the launch's cells, the beamforming kernel (beam.hip) forms the per-trial rows
-// from them, reduce_spec the slice partials; a launch holds beam->max_trials trials at most.
-int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64_t* seeds,
-               const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters, int32_t n_iters,
-               int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out, uint32_t* per_trial,
-               double* meas_out = nullptr, double* per_trial_meas = nullptr, bool spec = false,
-               const BeamCall* beam = nullptr) {
-  if (n_points < 0) return fail(MIMO_EINVAL, "n_points must be >= 0");
-  if (n_iters < 1 || !iters) return fail(MIMO_EINVAL, "at least one iteration index is required");
+// The iteration list of a call: the counter columns the kernel records.
+struct Iters {
   uint32_t rec_mask = 0;
   int max_iter = -1;
+};
+
+int validate_iters(const int32_t* iters, int32_t n_iters, Iters* it) {
+  if (n_iters < 1 || !iters) return fail(MIMO_EINVAL, "at least one iteration index is required");
   for (int i = 0; i < n_iters; ++i) {
     if (iters[i] < 0 || iters[i] > 31) return fail(MIMO_EINVAL, "iterations must be in [0, 31]");
     if (i && iters[i] <= iters[i - 1]) return fail(MIMO_EINVAL, "iterations must be sorted and unique");
-    rec_mask |= 1u << iters[i];
-    max_iter = std::max(max_iter, (int)iters[i]);
+    it->rec_mask |= 1u << iters[i];
+    it->max_iter = std::max(it->max_iter, (int)iters[i]);
   }
+  return MIMO_OK;
+}
+
+// Every point of a call (n_points >= 1), and what they must agree on: *csi = CSI error on.
+int validate_points(const mimo_engine* e, int n_points, const mimo_point* pts, const uint64_t* first_trial,
+                    const uint64_t* n_trials, bool* csi) {
+  *csi = pts[0].csi_eps >= 0;
+  for (int i = 0; i < n_points; ++i) {
+    if (int rc = validate_point(e, &pts[i])) return rc;
+    if ((pts[i].csi_eps >= 0) != *csi) return fail(MIMO_EINVAL, "all points of one run must agree on CSI error on/off");
+    if (n_trials[i] + first_trial[i] > (1ull << 32) || first_trial[i] >= (1ull << 32))
+      return fail(MIMO_EINVAL, "trial index must fit 32 bits");
+  }
+  return MIMO_OK;
+}
+
+// The CSI instances add n_ant reals of dynamic LDS (the per-antenna power table) to their
+// static LDS: check the sum against the CU's LDS before launching (F 8192 holds
+// ~157 KiB statically, so A = 512 (4 KiB) is the edge).
+int check_csi_lds(const mimo_engine* e, const mimo::InstanceKey& key) {
+  hipFuncAttributes fa{};
+  bool found = false;
+  const hipError_t qe =
+      key.f64 ? launch(MIMO_MODE_PLAIN, key, dim3(0), e->stream, mimo::TrialParams<double>{}, &found, &fa, nullptr)
+              : launch(MIMO_MODE_PLAIN, key, dim3(0), e->stream, mimo::TrialParams<float>{}, &found, &fa, nullptr);
+  int lds_max = 0;
+  if (!found || qe != hipSuccess ||
+      hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, e->device) != hipSuccess ||
+      lds_max <= 0)
+    return MIMO_OK;
+  const int A = e->cfg.n_ant;
+  const size_t need = fa.sharedSizeBytes + (size_t)A * (key.f64 ? sizeof(double) : sizeof(float));
+  if (need > (size_t)lds_max)
+    return fail(MIMO_EINVAL, "CSI error at n_ant = " + std::to_string(A) + " needs " + std::to_string(need) +
+                                 " B of LDS per team (static " + std::to_string(fa.sharedSizeBytes) +
+                                 " + the per-antenna table), the device has " + std::to_string(lds_max));
+  return MIMO_OK;
+}
+
+// The launches of a call: every point's trials become a contiguous range of blocks of one launch,
+// split across launches only beyond the chunk; a launch is a list of segments.  Per segment the
+// reductions run over slices of at most kSlice trials.
+struct Seg {
+  int point;
+  uint64_t first, n;
+};
+struct Plan {
+  std::vector<std::vector<Seg>> launches{1};
+  size_t max_seg = 0, max_blocks = 0, max_slices = 0;  // of one launch
+  size_t tot_slices = 0;                               // of all
+};
+
+// max_trials: what the mode's buffers allow in one launch.  Without it a launch holds 2^20 trials
+// (MIMO_MAX_LAUNCH_TRIALS lowers it, for tests of the splitting).
+Plan plan_launches(int n_points, const uint64_t* first_trial, const uint64_t* n_trials, uint64_t max_trials) {
+  uint64_t chunk = 1ull << 20;
+  if (const char* env = std::getenv("MIMO_MAX_LAUNCH_TRIALS")) {
+    const uint64_t v = std::strtoull(env, nullptr, 10);
+    if (v >= 1 && v < chunk) chunk = v;
+  }
+  chunk = std::min(chunk, max_trials);
+  Plan plan;
+  uint64_t fill = 0;
+  for (int i = 0; i < n_points; ++i) {
+    uint64_t done = 0;
+    while (done < n_trials[i]) {
+      if (fill == chunk) {
+        plan.launches.emplace_back();
+        fill = 0;
+      }
+      const uint64_t n = std::min(n_trials[i] - done, chunk - fill);
+      plan.launches.back().push_back(Seg{i, first_trial[i] + done, n});
+      done += n;
+      fill += n;
+    }
+  }
+  for (auto& l : plan.launches) {
+    size_t nb = 0, nsl = 0;
+    for (auto& sg : l) {
+      nb += (size_t)sg.n;
+      nsl += (size_t)((sg.n + kSlice - 1) / kSlice);
+    }
+    plan.max_seg = std::max(plan.max_seg, l.size());
+    plan.max_blocks = std::max(plan.max_blocks, nb);
+    plan.max_slices = std::max(plan.max_slices, nsl);
+    plan.tot_slices += nsl;
+  }
+  return plan;
+}
+
+// The kernel parameters every point of the call shares (fill_point adds a point's own).
+template <typename R>
+mimo::TrialParams<R> base_params(const mimo_engine* e, const mimo::InstanceKey& key, const Iters& it,
+                                 int32_t incl_clean, int n_idx) {
+  const mimo_config& c = e->cfg;
+  mimo::TrialParams<R> base{};
+  if constexpr (sizeof(R) == 8) {
+    base.tw = e->tw64.p;
+    base.tw_wave = e->twave64.p;
+    base.ant_rel = e->ant_rel64.p;
+    base.f_rel = e->f_rel64.p;
+    base.chan_tab = e->tab64.p;
+  } else {
+    base.tw = e->tw[key.T == mimo::team_size(c.n_fft) ? 0 : 1].p;
+    base.tw_wave = key.T == mimo::team_size(c.n_fft) ? e->twave32.p : nullptr;
+    base.ant_rel = e->ant_rel.p;
+    base.f_rel = e->f_rel.p;
+    base.chan_tab = e->tab32.p;
+  }
+  base.f_over_c = e->f_over_c.p;
+  base.tx_pos = e->tx_pos_dev.p;
+  base.lut = e->lut64.p;
+  base.n_ant = c.n_ant;
+  base.n_sc = c.n_sub_carr;
+  const int L = (int)std::lround(std::sqrt((double)c.constel_size));
+  base.qam_l = L;
+  base.half_bits = (int)std::lround(std::log2((double)L));
+  base.label_mask = (uint32_t)c.constel_size - 1u;
+  base.inv_vk0 = (R)((double)c.n_ant / c.n_sub_carr);
+  base.inv_vk0_f = (R)((double)c.n_ant * c.n_fft / c.n_sub_carr);
+  base.inv_sqrt_f = (R)(1.0 / std::sqrt((double)c.n_fft));
+  base.receiver = c.receiver_kind;
+  base.max_iter = it.max_iter;
+  base.rec_mask = it.rec_mask;
+  base.incl_clean = incl_clean ? 1 : 0;
+  base.n_idx = n_idx;
+  base.rx_x0 = c.rx_pos[0];
+  base.rx_z = c.rx_pos[2];
+  base.rx_var = c.reroll_chan ? c.rx_loc_var : 0.0;
+  base.d0 = e->d0;
+  base.ablate = 0;
+#ifdef MIMO_ABLATION
+  if (const char* env = std::getenv("MIMO_ABLATE")) base.ablate = (uint32_t)std::strtoul(env, nullptr, 0);
+#endif
+  base.counts = e->counts.p;
+  base.chan_period = (uint32_t)std::max(0, c.chan_replay_period);
+  return base;
+}
+
+// Byte offsets of the per-launch tables in the blob (mimo_engine::blob), each 16-byte aligned.
+struct BlobLayout {
+  size_t start, slice, point_of, bytes;
+};
+BlobLayout blob_layout(const Plan& plan, size_t params_bytes) {
+  auto up16 = [](size_t b) { return (b + 15) & ~size_t(15); };
+  BlobLayout o{};
+  o.start = up16(plan.max_seg * params_bytes);
+  o.slice = o.start + up16((plan.max_seg + 1) * sizeof(uint32_t));
+  o.point_of = o.slice + up16((plan.max_slices + 1) * sizeof(uint32_t));
+  o.bytes = o.point_of + up16(plan.max_slices * sizeof(int32_t));
+  return o;
+}
+
+// What the launches of a call leave for its totals.
+struct Progress {
+  uint64_t trials_done = 0;
+  // row modes: the slice partials of every launch, in launch and slice order, and their points
+  std::vector<double> part;
+  std::vector<int> part_point;
+  double ms = 0.0, beam_ms = 0.0;
+};
+
+// The tables of one launch, written into the host blob: the segments' parameters and block
+// offsets, the reduction slices' starts and points.
+struct LaunchTables {
+  size_t nseg = 0, nsl = 0;  // segments, slices
+  uint32_t nb = 0;           // blocks (trials)
+  const int32_t* point_of = nullptr;  // [nsl], host
+};
+template <typename R>
+LaunchTables fill_launch_tables(char* h_blob, const BlobLayout& o, const std::vector<mimo::TrialParams<R>>& ptab,
+                                const std::vector<Seg>& segs) {
+  using TP = mimo::TrialParams<R>;
+  TP* seg_tab = reinterpret_cast<TP*>(h_blob);
+  uint32_t* start = reinterpret_cast<uint32_t*>(h_blob + o.start);
+  uint32_t* slice_first = reinterpret_cast<uint32_t*>(h_blob + o.slice);
+  int32_t* point_of = reinterpret_cast<int32_t*>(h_blob + o.point_of);
+  LaunchTables t;
+  t.point_of = point_of;
+  start[0] = 0u;
+  slice_first[0] = 0u;
+  for (auto& sg : segs) {
+    TP q = ptab[sg.point];
+    q.first_trial = sg.first;
+    seg_tab[t.nseg] = q;
+    const uint32_t b0 = start[t.nseg];
+    start[++t.nseg] = b0 + (uint32_t)sg.n;
+    for (uint32_t s = 0; s < (uint32_t)sg.n; s += kSlice) {
+      slice_first[++t.nsl] = b0 + std::min<uint32_t>((uint32_t)sg.n, s + kSlice);
+      point_of[t.nsl - 1] = sg.point;
+    }
+  }
+  t.nb = start[t.nseg];
+  return t;
+}
+
+// One launch: its tables into the blob, the trial kernel of the mode, for beam the beamforming
+// kernel, the count and row reductions and the copies back; waits for the launch and times it.
+template <typename R>
+int run_launch(mimo_engine* e, const mimo::InstanceKey& key, const mimo::TrialParams<R>& base,
+               const std::vector<mimo::TrialParams<R>>& ptab, const BlobLayout& o, const std::vector<Seg>& segs,
+               const RowMode& rm, uint32_t* per_trial, Progress* pg) {
+  using TP = mimo::TrialParams<R>;
+  const int n_idx = base.n_idx;
+  const LaunchTables t = fill_launch_tables(e->h_blob.p, o, ptab, segs);
+  const size_t nsl = t.nsl;
+  const uint32_t nb = t.nb;
+  if (nb == 0) return MIMO_OK;  // every point of the call has n_trials == 0: nothing to launch
+  const uint32_t* d_slice_first = reinterpret_cast<const uint32_t*>(e->blob.p + o.slice);
+  TP kp = base;
+  kp.points = reinterpret_cast<const TP*>(e->blob.p);
+  kp.point_start = reinterpret_cast<const uint32_t*>(e->blob.p + o.start);
+  kp.n_points = (int)t.nseg;
+  kp.seed = ptab[segs[0].point].seed;  // unused by the kernel (read from the table)
+  // the whole blob (unused tails included: one contiguous DMA)
+  HIP_TRY(hipMemcpyAsync(e->blob.p, e->h_blob.p, o.point_of + nsl * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipEventRecord(e->ev0, e->stream));
+  bool found = false;
+  // (the beam instances fill the launch's cells; the beamforming kernel forms the rows from them)
+  const hipError_t le =
+      launch(rm.mode, key, dim3(nb), e->stream, kp, &found, nullptr, rm.beam ? e->bcell.p : e->rows.p);
+  if (!found) return fail(MIMO_ENOKERNEL, "no kernel instance for " + e->desc);
+  if (le != hipSuccess) return fail(MIMO_EHIP, std::string("trial kernel launch: ") + hipGetErrorString(le));
+  HIP_TRY(hipEventRecord(e->ev1, e->stream));
+#ifndef MIMO_ONLY_F  // (the single-size diagnostic builds found no beam instance above)
+  if (rm.beam) {
+    const mimo_config& c = e->cfg;
+    const size_t na = (size_t)rm.beam->n_probes * (size_t)c.n_ant;
+    const hipError_t be = mimo::launch_beam(e->stream, e->bcell.p, e->bgeo.p, e->bgeo.p + na, e->bgeo.p + 2 * na,
+                                            (int)nb, c.n_ant, c.n_fft, c.n_sub_carr, rm.beam->n_probes, e->rows.p);
+    if (be != hipSuccess) return fail(MIMO_EHIP, std::string("beamforming kernel launch: ") + hipGetErrorString(be));
+    HIP_TRY(hipEventRecord(e->ev2, e->stream));
+  }
+#endif
+  hipLaunchKernelGGL(reduce_counts, dim3((unsigned)nsl, n_idx), dim3(256), 0, e->stream, e->counts.p, d_slice_first,
+                     reinterpret_cast<const int32_t*>(e->blob.p + o.point_of), n_idx, e->tot.p);
+  HIP_TRY(hipGetLastError());
+  if (per_trial)
+    HIP_TRY(hipMemcpyAsync(per_trial + pg->trials_done * n_idx, e->counts.p, (size_t)nb * n_idx * sizeof(uint32_t),
+                           hipMemcpyDeviceToHost, e->stream));
+  if (rm.rows()) {
+    const int w = rm.width;
+    if (rm.mode == MIMO_MODE_MEAS)
+      hipLaunchKernelGGL(reduce_meas, dim3((unsigned)nsl, w), dim3(kReduceMeasThreads), 0, e->stream, e->rows.p,
+                         d_slice_first, w, e->part.p);
+    else
+      hipLaunchKernelGGL(reduce_spec, dim3((unsigned)nsl, (unsigned)((w + kReduceSpecThreads - 1) / kReduceSpecThreads)),
+                         dim3(kReduceSpecThreads), 0, e->stream, e->rows.p, d_slice_first, w, e->part.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(pg->part.data() + pg->part_point.size() * w, e->part.p, nsl * w * sizeof(double),
+                           hipMemcpyDeviceToHost, e->stream));
+    pg->part_point.insert(pg->part_point.end(), t.point_of, t.point_of + nsl);
+    if (rm.per_trial_out)
+      HIP_TRY(hipMemcpyAsync(rm.per_trial_out + pg->trials_done * w, e->rows.p, (size_t)nb * w * sizeof(double),
+                             hipMemcpyDeviceToHost, e->stream));
+  }
+  pg->trials_done += nb;
+  // the host tables of the next launch are rewritten: wait for this one's copies
+  HIP_TRY(hipEventSynchronize(e->ev1));
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+  pg->ms += ms;
+  if (rm.beam) {
+    HIP_TRY(hipEventSynchronize(e->ev2));
+    HIP_TRY(hipEventElapsedTime(&ms, e->ev1, e->ev2));
+    pg->beam_ms += ms;
+  }
+  return MIMO_OK;
+}
+
+// Every launch of the plan in the engine's arithmetic type R.
+template <typename R>
+int run_launches(mimo_engine* e, const mimo::InstanceKey& key, const mimo::TrialParams<R>& base, const Plan& plan,
+                 int n_points, const mimo_point* pts, const uint64_t* seeds, const RowMode& rm, uint32_t* per_trial,
+                 Progress* pg) {
+  // per-point parameter table (host), built once
+  std::vector<mimo::TrialParams<R>> ptab(n_points, base);
+  for (int i = 0; i < n_points; ++i) fill_point(e, pts[i], seeds[i], 0, ptab[i]);
+  const BlobLayout o = blob_layout(plan, sizeof(mimo::TrialParams<R>));
+  if (int rc = e->blob.ensure(o.bytes)) return rc;
+  if (int rc = e->h_blob.ensure(o.bytes)) return rc;
+  for (auto& segs : plan.launches)
+    if (int rc = run_launch(e, key, base, ptab, o, segs, rm, per_trial, pg)) return rc;
+  return MIMO_OK;
+}
+
+// Runs n_points grid points of one system in as few launches as possible (plan_launches), and a
+// segmented reduction sums each point's counts; rm: the rows a mode adds (RowMode; none: plain).
+int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64_t* seeds,
+               const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters, int32_t n_iters,
+               int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out, uint32_t* per_trial, const RowMode& rm) {
+  if (n_points < 0) return fail(MIMO_EINVAL, "n_points must be >= 0");
+  Iters it;
+  if (int rc = validate_iters(iters, n_iters, &it)) return rc;
   if (!err_out || !bits_out) return fail(MIMO_EINVAL, "null counters");
   if (n_points == 0) return MIMO_OK;
   if (!pts || !seeds || !first_trial || !n_trials) return fail(MIMO_EINVAL, "null point arrays");
   const int n_idx = n_iters + (incl_clean ? 1 : 0);
   const mimo_config& c = e->cfg;
-  const int n_meas = beam   ? beam->n_probes * MIMO_BEAM_FIXED  // row width of the mode
-                     : spec ? c.n_fft + MIMO_SPEC_FIXED
-                            : MIMO_MEAS_FIXED + n_idx;
-  const bool csi = pts[0].csi_eps >= 0;
-  for (int i = 0; i < n_points; ++i) {
-    if (int rc = validate_point(e, &pts[i])) return rc;
-    if ((pts[i].csi_eps >= 0) != csi) return fail(MIMO_EINVAL, "all points of one run must agree on CSI error on/off");
-    if (n_trials[i] + first_trial[i] > (1ull << 32) || first_trial[i] >= (1ull << 32))
-      return fail(MIMO_EINVAL, "trial index must fit 32 bits");
-  }
+  bool csi = false;
+  if (int rc = validate_points(e, n_points, pts, first_trial, n_trials, &csi)) return rc;
   if (int rc = validate_distances(e)) return rc;
   const mimo::InstanceKey key = select_instance(e, csi);
   if (int rc = ensure_device(e)) return rc;
-  if (csi) {
-    // the CSI instances add n_ant reals of dynamic LDS (the per-antenna power table) to their
-    // static LDS: check the sum against the CU's LDS before launching (F 8192 holds
-    // ~157 KiB statically, so A = 512 (4 KiB) is the edge)
-    hipFuncAttributes fa{};
-    bool found = false;
-    hipError_t qe = key.f64 ? launch(key, dim3(0), e->stream, mimo::TrialParams<double>{}, &found, &fa)
-                            : launch(key, dim3(0), e->stream, mimo::TrialParams<float>{}, &found, &fa);
-    int lds_max = 0;
-    if (found && qe == hipSuccess &&
-        hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, e->device) == hipSuccess &&
-        lds_max > 0) {
-      const size_t need = fa.sharedSizeBytes + (size_t)c.n_ant * (key.f64 ? sizeof(double) : sizeof(float));
-      if (need > (size_t)lds_max)
-        return fail(MIMO_EINVAL, "CSI error at n_ant = " + std::to_string(c.n_ant) + " needs " + std::to_string(need) +
-                                     " B of LDS per team (static " + std::to_string(fa.sharedSizeBytes) +
-                                     " + the per-antenna table), the device has " + std::to_string(lds_max));
-    }
-  }
+  if (csi)
+    if (int rc = check_csi_lds(e, key)) return rc;
   if (!c.reroll_chan && (c.channel_kind == MIMO_CH_LOS || c.channel_kind == MIMO_CH_TWOPATH)) {
     // fixed RX: jitter span 0 around (x0, x0); only consistent when rx_y == rx_x
     // (table channels never use the RX position)
     if (c.rx_pos[1] != c.rx_pos[0]) return fail(MIMO_EINVAL, "reroll_chan=0 requires rx_pos[1] == rx_pos[0]");
   }
-  char buf[160];
-  snprintf(buf, sizeof buf, "F=%d T=%d slots=%d %s ch=%d csi=%d %s", key.F, key.T, key.nslot,
-           key.aligned ? "aligned" : "generic", key.ch, (int)key.csi, key.f64 ? "f64" : "f32");
-  e->desc = buf;
+  e->desc = describe(key);
 
-  // segments (point, first trial, count) packed into launches of <= kChunk blocks
-  // Trials per launch: 2^20 (MIMO_MAX_LAUNCH_TRIALS lowers it, for tests of the splitting).
-  uint64_t kChunk = 1ull << 20;
-  if (const char* env = std::getenv("MIMO_MAX_LAUNCH_TRIALS")) {
-    const uint64_t v = std::strtoull(env, nullptr, 10);
-    if (v >= 1 && v < kChunk) kChunk = v;
+  const Plan plan = plan_launches(n_points, first_trial, n_trials, rm.max_trials);
+  Progress pg;
+  if (rm.rows()) {
+    if (int rc = e->rows.ensure(std::max<size_t>(1, plan.max_blocks * rm.width))) return rc;
+    if (int rc = e->part.ensure(std::max<size_t>(1, plan.max_slices * rm.width))) return rc;
+    pg.part.resize(plan.tot_slices * rm.width);
+    pg.part_point.reserve(plan.tot_slices);
   }
-  if (spec) kChunk = std::min<uint64_t>(kChunk, MIMO_SPEC_BUFFER_BYTES / (sizeof(double) * (size_t)n_meas));
-  if (beam) kChunk = std::min<uint64_t>(kChunk, beam->max_trials);
-  double*& d_rows = beam ? e->d_beam : spec ? e->d_spec : e->d_meas;  // per-trial rows and slice partials of the mode
-  size_t& rows_cap = beam ? e->beam_cap : spec ? e->spec_cap : e->meas_cap;
-  double*& d_part = beam ? e->d_bpart : spec ? e->d_spart : e->d_mpart;
-  size_t& part_cap = beam ? e->bpart_cap : spec ? e->spart_cap : e->mpart_cap;
-  struct Seg {
-    int point;
-    uint64_t first, n;
-  };
-  std::vector<std::vector<Seg>> launches(1);
-  uint64_t fill = 0;
-  for (int i = 0; i < n_points; ++i) {
-    uint64_t done = 0;
-    while (done < n_trials[i]) {
-      if (fill == kChunk) {
-        launches.emplace_back();
-        fill = 0;
-      }
-      const uint64_t n = std::min(n_trials[i] - done, kChunk - fill);
-      launches.back().push_back(Seg{i, first_trial[i] + done, n});
-      done += n;
-      fill += n;
-    }
+  if (rm.beam) {
+    const size_t cells = 2 * plan.max_blocks * (size_t)c.n_ant * (size_t)c.n_fft * 2;  // doubles
+    if (int rc = e->bcell.ensure(std::max<size_t>(2, cells))) return rc;
+    if (int rc = e->bgeo.ensure(rm.beam->geo.size())) return rc;
+    HIP_TRY(hipMemcpyAsync(e->bgeo.p, rm.beam->geo.data(), sizeof(double) * rm.beam->geo.size(), hipMemcpyHostToDevice,
+                           e->stream));
   }
-  size_t max_seg = 0;
-  for (auto& l : launches) max_seg = std::max(max_seg, l.size());
-  // measure calls: the slice partials of every launch, in launch and slice order, and their points
-  std::vector<double> mpart;
-  std::vector<int> mpart_point;
-  if (meas_out) {
-    size_t max_blocks = 0, max_sl = 0, tot_sl = 0;
-    for (auto& l : launches) {
-      size_t nb = 0, nsl = 0;
-      for (auto& sg : l) {
-        nb += (size_t)sg.n;
-        nsl += (size_t)((sg.n + kSlice - 1) / kSlice);
-      }
-      max_blocks = std::max(max_blocks, nb);
-      max_sl = std::max(max_sl, nsl);
-      tot_sl += nsl;
-    }
-    if (int rc = ensure_cap(d_rows, rows_cap, std::max<size_t>(1, max_blocks * n_meas))) return rc;
-    if (int rc = ensure_cap(d_part, part_cap, std::max<size_t>(1, max_sl * n_meas))) return rc;
-    mpart.resize(tot_sl * n_meas);
-    mpart_point.reserve(tot_sl);
-    if (beam) {
-      const size_t cells = 2 * max_blocks * (size_t)c.n_ant * (size_t)c.n_fft * 2;  // doubles
-      if (int rc = ensure_cap(e->d_bcell, e->bcell_cap, std::max<size_t>(2, cells))) return rc;
-      if (int rc = ensure_cap(e->d_bgeo, e->bgeo_cap, beam->geo.size())) return rc;
-      HIP_TRY(hipMemcpyAsync(e->d_bgeo, beam->geo.data(), sizeof(double) * beam->geo.size(), hipMemcpyHostToDevice,
-                             e->stream));
-    }
-  }
-  size_t mpart_done = 0;
-  if (int rc = ensure_cap(e->d_counts, e->counts_cap, (size_t)(1ull << 20) * n_idx)) return rc;
-  if (int rc = ensure_cap(e->d_tot, e->tot_cap, (size_t)n_points * n_idx)) return rc;
-  const size_t max_slices = max_seg + (size_t)(kChunk / kSlice) + 1;
-  HIP_TRY(hipMemsetAsync(e->d_tot, 0, sizeof(unsigned long long) * n_points * n_idx, e->stream));
-  double ms_total = 0.0, beam_ms_total = 0.0;
-  uint64_t rows_done = 0;
+  if (int rc = e->counts.ensure((size_t)(1ull << 20) * n_idx)) return rc;
+  if (int rc = e->tot.ensure((size_t)n_points * n_idx)) return rc;
+  HIP_TRY(hipMemsetAsync(e->tot.p, 0, sizeof(unsigned long long) * n_points * n_idx, e->stream));
+  if (int rc = key.f64 ? run_launches(e, key, base_params<double>(e, key, it, incl_clean, n_idx), plan, n_points, pts,
+                                      seeds, rm, per_trial, &pg)
+                       : run_launches(e, key, base_params<float>(e, key, it, incl_clean, n_idx), plan, n_points, pts,
+                                      seeds, rm, per_trial, &pg))
+    return rc;
 
-  auto run_as = [&](auto zero) -> int {
-    using R = decltype(zero);
-    using TP = mimo::TrialParams<R>;
-    constexpr bool F64 = sizeof(R) == 8;
-    TP base{};
-    if constexpr (F64) {
-      base.tw = e->d_tw64;
-      base.tw_wave = e->d_twave64;
-      base.ant_rel = e->d_ant_rel64;
-      base.f_rel = e->d_f_rel64;
-      base.chan_tab = e->d_tab64;
-    } else {
-      base.tw = e->d_tw[key.T == mimo::team_size(c.n_fft) ? 0 : 1];
-      base.tw_wave = key.T == mimo::team_size(c.n_fft) ? e->d_twave32 : nullptr;
-      base.ant_rel = e->d_ant_rel;
-      base.f_rel = e->d_f_rel;
-      base.chan_tab = e->d_tab32;
-    }
-    base.f_over_c = e->d_f_over_c;
-    base.tx_pos = e->d_tx_pos;
-    base.lut = e->d_lut64;
-    base.n_ant = c.n_ant;
-    base.n_sc = c.n_sub_carr;
-    const int L = (int)std::lround(std::sqrt((double)c.constel_size));
-    base.qam_l = L;
-    base.half_bits = (int)std::lround(std::log2((double)L));
-    base.label_mask = (uint32_t)c.constel_size - 1u;
-    base.inv_vk0 = (R)((double)c.n_ant / c.n_sub_carr);
-    base.inv_vk0_f = (R)((double)c.n_ant * c.n_fft / c.n_sub_carr);
-    base.inv_sqrt_f = (R)(1.0 / std::sqrt((double)c.n_fft));
-    base.receiver = c.receiver_kind;
-    base.max_iter = max_iter;
-    base.rec_mask = rec_mask;
-    base.incl_clean = incl_clean ? 1 : 0;
-    base.n_idx = n_idx;
-    base.rx_x0 = c.rx_pos[0];
-    base.rx_z = c.rx_pos[2];
-    base.rx_var = c.reroll_chan ? c.rx_loc_var : 0.0;
-    base.d0 = e->d0;
-    base.ablate = 0;
-#ifdef MIMO_ABLATION
-    if (const char* env = std::getenv("MIMO_ABLATE")) base.ablate = (uint32_t)std::strtoul(env, nullptr, 0);
-#endif
-    base.counts = e->d_counts;
-    base.chan_period = (uint32_t)std::max(0, c.chan_replay_period);
-    // per-point parameter table (host), built once
-    std::vector<TP> ptab(n_points, base);
-    for (int i = 0; i < n_points; ++i) fill_point(e, pts[i], seeds[i], 0, ptab[i]);
-    auto up16 = [](size_t b) { return (b + 15) & ~size_t(15); };
-    const size_t o_start = up16(max_seg * sizeof(TP)), o_slice = o_start + up16((max_seg + 1) * sizeof(uint32_t)),
-                 o_pof = o_slice + up16((max_slices + 1) * sizeof(uint32_t)),
-                 blob = o_pof + up16(max_slices * sizeof(int32_t));
-    if (int rc = ensure_cap(e->d_blob, e->blob_cap, blob)) return rc;
-    if (blob > e->hblob_cap) {
-      if (e->h_blob) HIP_TRY(hipHostFree(e->h_blob));
-      e->h_blob = nullptr;
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->h_blob), blob, hipHostMallocDefault));
-      e->hblob_cap = blob;
-    }
-    TP* seg_tab = reinterpret_cast<TP*>(e->h_blob);
-    uint32_t* start = reinterpret_cast<uint32_t*>(e->h_blob + o_start);
-    uint32_t* slice_first = reinterpret_cast<uint32_t*>(e->h_blob + o_slice);
-    int32_t* point_of = reinterpret_cast<int32_t*>(e->h_blob + o_pof);
-    for (auto& l : launches) {
-      size_t nseg = 0, nsl = 0;
-      start[0] = 0u;
-      slice_first[0] = 0u;
-      for (auto& sg : l) {
-        TP q = ptab[sg.point];
-        q.first_trial = sg.first;
-        seg_tab[nseg] = q;
-        const uint32_t b0 = start[nseg];
-        start[++nseg] = b0 + (uint32_t)sg.n;
-        for (uint32_t o = 0; o < (uint32_t)sg.n; o += kSlice) {
-          slice_first[++nsl] = b0 + std::min<uint32_t>((uint32_t)sg.n, o + kSlice);
-          point_of[nsl - 1] = sg.point;
-        }
-      }
-      const uint32_t nb = start[nseg];
-      if (nb == 0) continue;  // every point of the call has n_trials == 0: nothing to launch
-      TP kp = base;
-      kp.points = reinterpret_cast<const TP*>(e->d_blob);
-      kp.point_start = reinterpret_cast<const uint32_t*>(e->d_blob + o_start);
-      kp.n_points = (int)nseg;
-      kp.seed = seg_tab[0].seed;  // unused by the kernel (read from the table)
-      // the whole blob (unused tails included: one contiguous DMA)
-      HIP_TRY(hipMemcpyAsync(e->d_blob, e->h_blob, o_pof + nsl * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-      HIP_TRY(hipEventRecord(e->ev0, e->stream));
-      bool found = false;
-      hipError_t le = hipSuccess;
-      if constexpr (F64) {
-        le = beam       ? launch_beam_inst(key, dim3(nb), e->stream, kp, e->d_bcell, &found)
-             : spec     ? launch_spec(key, dim3(nb), e->stream, kp, d_rows, &found)
-             : meas_out ? launch_meas(key, dim3(nb), e->stream, kp, d_rows, &found)
-                        : launch(key, dim3(nb), e->stream, kp, &found);
-      } else {
-        le = launch(key, dim3(nb), e->stream, kp, &found);
-      }
-      if (!found) return fail(MIMO_ENOKERNEL, std::string("no kernel instance for ") + buf);
-      if (le != hipSuccess) return fail(MIMO_EHIP, std::string("trial kernel launch: ") + hipGetErrorString(le));
-      HIP_TRY(hipEventRecord(e->ev1, e->stream));
-#ifndef MIMO_ONLY_F  // (the single-size diagnostic builds found no beam instance above)
-      if (beam) {
-        const size_t na = (size_t)beam->n_probes * (size_t)c.n_ant;
-        const hipError_t be = mimo::launch_beam(e->stream, e->d_bcell, e->d_bgeo, e->d_bgeo + na, e->d_bgeo + 2 * na,
-                                                (int)nb, c.n_ant, c.n_fft, c.n_sub_carr, beam->n_probes, d_rows);
-        if (be != hipSuccess)
-          return fail(MIMO_EHIP, std::string("beamforming kernel launch: ") + hipGetErrorString(be));
-        HIP_TRY(hipEventRecord(e->ev2, e->stream));
-      }
-#endif
-      hipLaunchKernelGGL(reduce_counts, dim3((unsigned)nsl, n_idx), dim3(256), 0, e->stream, e->d_counts,
-                         reinterpret_cast<const uint32_t*>(e->d_blob + o_slice),
-                         reinterpret_cast<const int32_t*>(e->d_blob + o_pof), n_idx, e->d_tot);
-      HIP_TRY(hipGetLastError());
-      if (per_trial)
-        HIP_TRY(hipMemcpyAsync(per_trial + rows_done * n_idx, e->d_counts, (size_t)nb * n_idx * sizeof(uint32_t),
-                               hipMemcpyDeviceToHost, e->stream));
-      if (meas_out) {
-        if (spec || beam)
-          hipLaunchKernelGGL(reduce_spec,
-                             dim3((unsigned)nsl, (unsigned)((n_meas + kReduceSpecThreads - 1) / kReduceSpecThreads)),
-                             dim3(kReduceSpecThreads), 0, e->stream, d_rows,
-                             reinterpret_cast<const uint32_t*>(e->d_blob + o_slice), n_meas, d_part);
-        else
-          hipLaunchKernelGGL(reduce_meas, dim3((unsigned)nsl, n_meas), dim3(kReduceMeasThreads), 0, e->stream, d_rows,
-                             reinterpret_cast<const uint32_t*>(e->d_blob + o_slice), n_meas, d_part);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(mpart.data() + mpart_done * n_meas, d_part, nsl * n_meas * sizeof(double),
-                               hipMemcpyDeviceToHost, e->stream));
-        for (size_t i = 0; i < nsl; ++i) mpart_point.push_back(point_of[i]);
-        mpart_done += nsl;
-        if (per_trial_meas)
-          HIP_TRY(hipMemcpyAsync(per_trial_meas + rows_done * n_meas, d_rows, (size_t)nb * n_meas * sizeof(double),
-                                 hipMemcpyDeviceToHost, e->stream));
-      }
-      rows_done += nb;
-      // the host tables of the next launch are rewritten: wait for this one's copies
-      HIP_TRY(hipEventSynchronize(e->ev1));
-      float ms = 0.f;
-      HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-      ms_total += ms;
-      if (beam) {
-        HIP_TRY(hipEventSynchronize(e->ev2));
-        HIP_TRY(hipEventElapsedTime(&ms, e->ev1, e->ev2));
-        beam_ms_total += ms;
-      }
-    }
-    return MIMO_OK;
-  };
-  if (int rc = key.f64 ? run_as(0.0) : run_as(0.0f)) return rc;
   std::vector<unsigned long long> tot((size_t)n_points * n_idx);
-  HIP_TRY(hipMemcpyAsync(tot.data(), e->d_tot, sizeof(unsigned long long) * tot.size(), hipMemcpyDeviceToHost,
+  HIP_TRY(hipMemcpyAsync(tot.data(), e->tot.p, sizeof(unsigned long long) * tot.size(), hipMemcpyDeviceToHost,
                          e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   const uint64_t bits_per_trial = (uint64_t)c.n_sub_carr * (uint64_t)std::lround(std::log2((double)c.constel_size));
@@ -918,16 +948,17 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
       err_out[(size_t)i * n_idx + j] += tot[(size_t)i * n_idx + j];
       bits_out[(size_t)i * n_idx + j] += bits_per_trial * n_trials[i];
     }
-  if (meas_out) {
+  if (rm.rows()) {
     // per point, its slice partials in slice order (a fixed order: equal calls, equal bits),
     // then one add into the caller's row
-    std::vector<double> ptot((size_t)n_points * n_meas, 0.0);
-    for (size_t k = 0; k < mpart_point.size(); ++k)
-      for (int j = 0; j < n_meas; ++j) ptot[(size_t)mpart_point[k] * n_meas + j] += mpart[k * n_meas + j];
-    for (size_t i = 0; i < ptot.size(); ++i) meas_out[i] += ptot[i];
+    const int w = rm.width;
+    std::vector<double> ptot((size_t)n_points * w, 0.0);
+    for (size_t k = 0; k < pg.part_point.size(); ++k)
+      for (int j = 0; j < w; ++j) ptot[(size_t)pg.part_point[k] * w + j] += pg.part[k * w + j];
+    for (size_t i = 0; i < ptot.size(); ++i) rm.out[i] += ptot[i];
   }
-  e->last_ms = ms_total;
-  e->last_beam_ms = beam_ms_total;
+  e->last_ms = pg.ms;
+  e->last_beam_ms = pg.beam_ms;
   return MIMO_OK;
 }
 
@@ -941,10 +972,10 @@ int32_t mimo_engine_run(mimo_engine* e, uint64_t seed, uint64_t first_trial, uin
   if (!e->have_point) return fail(MIMO_EINVAL, "mimo_engine_set_point was not called");
   if (n_trials == 0) {  // validate the iteration list, add nothing
     return run_points(e, 0, nullptr, nullptr, nullptr, nullptr, iters, n_iters, incl_clean, err_out, bits_out,
-                      per_trial);
+                      per_trial, RowMode{});
   }
   return run_points(e, 1, &e->pt, &seed, &first_trial, &n_trials, iters, n_iters, incl_clean, err_out, bits_out,
-                    per_trial);
+                    per_trial, RowMode{});
 }
 
 int32_t mimo_engine_run_points(mimo_engine* e, int32_t n_points, const mimo_point* points, const uint64_t* seeds,
@@ -953,7 +984,7 @@ int32_t mimo_engine_run_points(mimo_engine* e, int32_t n_points, const mimo_poin
                                uint32_t* per_trial) {
   if (!e) return fail(MIMO_EINVAL, "null engine");
   return run_points(e, n_points, points, seeds, first_trial, n_trials, iters, n_iters, incl_clean, err_out, bits_out,
-                    per_trial);
+                    per_trial, RowMode{});
 }
 
 int32_t mimo_measure_width(int32_t n_iters, int32_t incl_clean) {
@@ -969,8 +1000,13 @@ int32_t mimo_engine_measure_points(mimo_engine* e, int32_t n_points, const mimo_
   if (e->cfg.precision != MIMO_PREC_F64)
     return fail(MIMO_EINVAL, "measure needs a float64 engine (no float32 measure instances are built)");
   if (!meas_out) return fail(MIMO_EINVAL, "null meas_out");
+  RowMode rm;
+  rm.mode = MIMO_MODE_MEAS;
+  rm.width = MIMO_MEAS_FIXED + n_iters + (incl_clean ? 1 : 0);  // (run_points checks n_iters before it reads this)
+  rm.out = meas_out;
+  rm.per_trial_out = per_trial_meas;
   return run_points(e, n_points, points, seeds, first_trial, n_trials, iters, n_iters, incl_clean, err_out, bits_out,
-                    per_trial, meas_out, per_trial_meas);
+                    per_trial, rm);
 }
 
 int32_t mimo_spectrum_width(int32_t n_fft) {
@@ -987,8 +1023,14 @@ int32_t mimo_engine_spectrum_points(mimo_engine* e, int32_t n_points, const mimo
   if (e->cfg.precision != MIMO_PREC_F64)
     return fail(MIMO_EINVAL, "spectrum needs a float64 engine (no float32 spectrum instances are built)");
   if (!spec_out) return fail(MIMO_EINVAL, "null spec_out");
+  RowMode rm;
+  rm.mode = MIMO_MODE_SPEC;
+  rm.width = e->cfg.n_fft + MIMO_SPEC_FIXED;
+  rm.max_trials = MIMO_SPEC_BUFFER_BYTES / (sizeof(double) * (size_t)rm.width);
+  rm.out = spec_out;
+  rm.per_trial_out = per_trial_spec;
   return run_points(e, n_points, points, seeds, first_trial, n_trials, iters, n_iters, incl_clean, err_out, bits_out,
-                    per_trial, spec_out, per_trial_spec, true);
+                    per_trial, rm);
 }
 
 int32_t mimo_beam_width(int32_t n_probes) {
@@ -1011,6 +1053,12 @@ int32_t mimo_engine_beam_points(mimo_engine* e, int32_t n_points, const mimo_poi
   const int A = e->cfg.n_ant, F = e->cfg.n_fft;
   BeamCall bc;
   bc.n_probes = n_probes;
+  RowMode rm;
+  rm.mode = MIMO_MODE_BEAM;
+  rm.width = n_probes * MIMO_BEAM_FIXED;
+  rm.out = beam_out;
+  rm.per_trial_out = per_trial_beam;
+  rm.beam = &bc;
   // the launch's cells: Y and X of every antenna and bin, complex128
   const uint64_t per_trial_bytes = 2ull * (uint64_t)A * (uint64_t)F * 16ull;
   uint64_t buffer = MIMO_BEAM_BUFFER_BYTES;
@@ -1018,14 +1066,14 @@ int32_t mimo_engine_beam_points(mimo_engine* e, int32_t n_points, const mimo_poi
     const uint64_t v = std::strtoull(env, nullptr, 10);
     if (v >= 1 && v < buffer) buffer = v;
   }
-  bc.max_trials = buffer / per_trial_bytes;
-  if (bc.max_trials < 1)
+  rm.max_trials = buffer / per_trial_bytes;
+  if (rm.max_trials < 1)
     return fail(MIMO_EINVAL, "one trial's beam cells (" + std::to_string(per_trial_bytes) + " B at n_ant " +
                                  std::to_string(A) + ", n_fft " + std::to_string(F) +
                                  ") do not fit the beam buffer of " + std::to_string(buffer) + " B");
   // ... and its per-trial rows, as for the spectrum mode (one trial's 40 n_probes bytes always fit)
-  bc.max_trials = std::min<uint64_t>(
-      bc.max_trials, MIMO_BEAM_ROWS_BYTES / (sizeof(double) * (uint64_t)MIMO_BEAM_FIXED * (uint64_t)n_probes));
+  rm.max_trials = std::min<uint64_t>(
+      rm.max_trials, MIMO_BEAM_ROWS_BYTES / (sizeof(double) * (uint64_t)MIMO_BEAM_FIXED * (uint64_t)n_probes));
   const size_t na = (size_t)n_probes * (size_t)A;
   bc.geo.resize(2 * na + (size_t)F);
   for (int q = 0; q < n_probes; ++q) {
@@ -1046,7 +1094,7 @@ int32_t mimo_engine_beam_points(mimo_engine* e, int32_t n_points, const mimo_poi
   }
   for (int k = 0; k < F; ++k) bc.geo[2 * na + k] = e->freqs[k] / kSpeedOfLight;
   return run_points(e, n_points, points, seeds, first_trial, n_trials, iters, n_iters, incl_clean, err_out, bits_out,
-                    per_trial, beam_out, per_trial_beam, false, &bc);
+                    per_trial, rm);
 }
 
 double mimo_engine_last_kernel_ms(const mimo_engine* e) { return e ? e->last_ms : 0.0; }
@@ -1054,52 +1102,12 @@ double mimo_engine_last_beam_ms(const mimo_engine* e) { return e ? e->last_beam_
 
 const char* mimo_engine_describe(const mimo_engine* e) {
   if (!e) return "";
-  if (e->desc.empty()) {
-    const mimo::InstanceKey k = select_instance(e, e->have_point && e->pt.csi_eps >= 0);
-    char buf[160];
-    snprintf(buf, sizeof buf, "F=%d T=%d slots=%d %s ch=%d csi=%d %s", k.F, k.T, k.nslot,
-             k.aligned ? "aligned" : "generic", k.ch, (int)k.csi, k.f64 ? "f64" : "f32");
-    const_cast<mimo_engine*>(e)->desc = buf;
-  }
+  if (e->desc.empty())
+    const_cast<mimo_engine*>(e)->desc = describe(select_instance(e, e->have_point && e->pt.csi_eps >= 0));
   return e->desc.c_str();
 }
 
-void mimo_engine_destroy(mimo_engine* e) {
-  if (!e) return;
-  if (e->ready) {
-    (void)hipStreamSynchronize(e->stream);
-    (void)hipFree(e->d_tw[0]);
-    (void)hipFree(e->d_tw[1]);
-    (void)hipFree(e->d_f_rel);
-    (void)hipFree(e->d_tw64);
-    if (e->d_twave64) (void)hipFree(e->d_twave64);
-    if (e->d_twave32) (void)hipFree(e->d_twave32);
-    (void)hipFree(e->d_lut64);
-    if (e->d_tab32) (void)hipFree(e->d_tab32);
-    if (e->d_tab64) (void)hipFree(e->d_tab64);
-    (void)hipFree(e->d_f_rel64);
-    (void)hipFree(e->d_ant_rel64);
-    (void)hipFree(e->d_f_over_c);
-    (void)hipFree(e->d_ant_rel);
-    (void)hipFree(e->d_tx_pos);
-    if (e->d_tot) (void)hipFree(e->d_tot);
-    if (e->d_counts) (void)hipFree(e->d_counts);
-    if (e->d_meas) (void)hipFree(e->d_meas);
-    if (e->d_mpart) (void)hipFree(e->d_mpart);
-    if (e->d_spec) (void)hipFree(e->d_spec);
-    if (e->d_spart) (void)hipFree(e->d_spart);
-    if (e->d_bcell) (void)hipFree(e->d_bcell);
-    if (e->d_bgeo) (void)hipFree(e->d_bgeo);
-    if (e->d_beam) (void)hipFree(e->d_beam);
-    if (e->d_bpart) (void)hipFree(e->d_bpart);
-    if (e->d_blob) (void)hipFree(e->d_blob);
-    if (e->h_blob) (void)hipHostFree(e->h_blob);
-    (void)hipEventDestroy(e->ev0);
-    (void)hipEventDestroy(e->ev1);
-    (void)hipEventDestroy(e->ev2);
-    (void)hipStreamDestroy(e->stream);
-  }
-  delete e;
-}
+// Whatever device state exists goes with the engine (~mimo_engine), ready or not.
+void mimo_engine_destroy(mimo_engine* e) { delete e; }
 
 }  // extern "C"

@@ -1,8 +1,6 @@
-// Instantiates the fused trial kernel for one FFT size and arithmetic type
-// (compiled once per -DINST_F=<size> -DINST_F64=<0|1>), and once more per size with
-// -DINST_F64=1 -DINST_MEAS=1 for the measure instances (trial_kernel.h MIMO_MEAS_INST) and with
-// -DINST_F64=1 -DINST_SPEC=1 for the spectrum instances (MIMO_SPEC_INST) and with
-// -DINST_F64=1 -DINST_BEAM=1 for the beam instances (MIMO_BEAM_INST).
+// Instantiates the fused trial kernel for one FFT size, arithmetic type and run mode: compiled
+// once per -DINST_F=<size> -DINST_F64=<0|1>, and once more per size with -DINST_F64=1
+// -DINST_MODE=<1 measure | 2 spectrum | 3 beam> (trial_kernel.h MIMO_MODE_*; 0, plain, by default).
 #include <type_traits>
 
 #ifndef INST_F
@@ -11,32 +9,26 @@
 #ifndef INST_F64
 #define INST_F64 0
 #endif
-#ifndef INST_MEAS
-#define INST_MEAS 0
+#ifndef INST_MODE
+#define INST_MODE 0
 #endif
-#if INST_MEAS && !INST_F64
-#error "measure instances are float64 only"
+#if INST_MODE && !INST_F64
+#error "the measure, spectrum and beam instances are float64 only"
 #endif
-#define MIMO_MEAS_INST INST_MEAS
-#ifndef INST_SPEC
-#define INST_SPEC 0
-#endif
-#if INST_SPEC && (!INST_F64 || INST_MEAS)
-#error "spectrum instances are float64 only, and objects of their own"
-#endif
-#define MIMO_SPEC_INST INST_SPEC
-#ifndef INST_BEAM
-#define INST_BEAM 0
-#endif
-#if INST_BEAM && (!INST_F64 || INST_MEAS || INST_SPEC)
-#error "beam instances are float64 only, and objects of their own"
-#endif
-#define MIMO_BEAM_INST INST_BEAM
+#define MIMO_INST_MODE INST_MODE
 
 #include "trial_launch.h"
 
-#define MIMO_CAT2(a, b) a##b
-#define MIMO_CAT(a, b) MIMO_CAT2(a, b)
+// the one kernel trial_kernel.h defines for the mode
+#if INST_MODE == MIMO_MODE_MEAS
+#define MIMO_TRIAL_KERNEL trial_kernel_meas
+#elif INST_MODE == MIMO_MODE_SPEC
+#define MIMO_TRIAL_KERNEL trial_kernel_spec
+#elif INST_MODE == MIMO_MODE_BEAM
+#define MIMO_TRIAL_KERNEL trial_kernel_beam
+#else
+#define MIMO_TRIAL_KERNEL trial_kernel
+#endif
 
 namespace mimo {
 namespace {
@@ -76,26 +68,16 @@ constexpr Profile profile_for(int T, bool aligned, int ch) {
 
 // attr != null: no launch, the instance's attributes instead (its static LDS, which the
 // engine checks with the CSI table's dynamic LDS against the device limit before a launch).
-// meas: the measure instances' per-trial rows [grid.x][kMeasFixed + n_idx], the spectrum
-// instances' [grid.x][kF + kSpecFixed], the beam instances' cells [2][grid.x][A][kF] complex128
-// (unused otherwise).
+// out: the kernel's extra argument (trial_launch.h launch_trial; the plain kernel has none).
 template <int T, int NSLOT, bool AL, int CH, bool CSI>
-hipError_t go(dim3 grid, hipStream_t st, const TrialParams<Real>& p, hipFuncAttributes* attr, double* meas) {
+hipError_t go(dim3 grid, hipStream_t st, const TrialParams<Real>& p, hipFuncAttributes* attr, double* out) {
   constexpr Profile pr = profile_for(T, AL, CH);
-#if INST_MEAS
-  auto* kern = &trial_kernel_meas<Real, kF, T, NSLOT, AL, CH, CSI, pr.minw, pr.nbuf, pr.symw_lds>;
-#elif INST_SPEC
-  auto* kern = &trial_kernel_spec<Real, kF, T, NSLOT, AL, CH, CSI, pr.minw, pr.nbuf, pr.symw_lds>;
-#elif INST_BEAM
-  auto* kern = &trial_kernel_beam<Real, kF, T, NSLOT, AL, CH, CSI, pr.minw, pr.nbuf, pr.symw_lds>;
-#else
-  auto* kern = &trial_kernel<Real, kF, T, NSLOT, AL, CH, CSI, pr.minw, pr.nbuf, pr.symw_lds>;
-#endif
+  auto* kern = &MIMO_TRIAL_KERNEL<Real, kF, T, NSLOT, AL, CH, CSI, pr.minw, pr.nbuf, pr.symw_lds>;
   if (attr) return hipFuncGetAttributes(attr, reinterpret_cast<const void*>(kern));
   // CSI: the per-antenna power table is dynamic LDS, A reals (trial_kernel pw_csi)
   const size_t dyn = CSI ? sizeof(Real) * (size_t)p.n_ant : 0;
-#if INST_MEAS || INST_SPEC || INST_BEAM
-  hipLaunchKernelGGL(kern, grid, dim3(T), dyn, st, p, meas);
+#if INST_MODE
+  hipLaunchKernelGGL(kern, grid, dim3(T), dyn, st, p, out);
 #else
   hipLaunchKernelGGL(kern, grid, dim3(T), dyn, st, p);
 #endif
@@ -144,36 +126,17 @@ hipError_t by_team(const InstanceKey& k, dim3 grid, hipStream_t st, const TrialP
 
 }  // namespace
 
-#if INST_MEAS
-#define MIMO_LAUNCH_NAME MIMO_CAT(MIMO_CAT(launch_trial_F, INST_F), _f64_meas)
-#define MIMO_LAUNCH_MEAS_ARG , double* meas
-#elif INST_SPEC
-#define MIMO_LAUNCH_NAME MIMO_CAT(MIMO_CAT(launch_trial_F, INST_F), _f64_spec)
-#define MIMO_LAUNCH_MEAS_ARG , double* meas
-#elif INST_BEAM
-#define MIMO_LAUNCH_NAME MIMO_CAT(MIMO_CAT(launch_trial_F, INST_F), _f64_beam)
-#define MIMO_LAUNCH_MEAS_ARG , double* meas
-#elif INST_F64
-#define MIMO_LAUNCH_NAME MIMO_CAT(MIMO_CAT(launch_trial_F, INST_F), _f64)
-#else
-#define MIMO_LAUNCH_NAME MIMO_CAT(MIMO_CAT(launch_trial_F, INST_F), _f32)
-#endif
-#ifndef MIMO_LAUNCH_MEAS_ARG
-#define MIMO_LAUNCH_MEAS_ARG
-#endif
-hipError_t MIMO_LAUNCH_NAME(const InstanceKey& k, dim3 grid, hipStream_t st, const TrialParams<Real>& p, bool* found,
-                            hipFuncAttributes* attr MIMO_LAUNCH_MEAS_ARG) {
-#if !INST_MEAS && !INST_SPEC && !INST_BEAM
-  double* const meas = nullptr;
-#endif
+template <>
+hipError_t launch_trial<kF, Real, INST_MODE>(const InstanceKey& k, dim3 grid, hipStream_t st, const TrialParams<Real>& p,
+                                             bool* found, hipFuncAttributes* attr, double* out) {
   *found = false;
   if (k.F != kF || k.f64 != kF64) return hipSuccess;
   if constexpr (kF64) {
-    if (k.T == team_size64(kF)) return by_team<team_size64(kF)>(k, grid, st, p, found, attr, meas);
+    if (k.T == team_size64(kF)) return by_team<team_size64(kF)>(k, grid, st, p, found, attr, out);
   } else {
-    if (k.T == team_size(kF)) return by_team<team_size(kF)>(k, grid, st, p, found, attr, meas);
+    if (k.T == team_size(kF)) return by_team<team_size(kF)>(k, grid, st, p, found, attr, out);
     if constexpr (alt_team_size(kF) != team_size(kF)) {
-      if (k.T == alt_team_size(kF)) return by_team<alt_team_size(kF)>(k, grid, st, p, found, attr, meas);
+      if (k.T == alt_team_size(kF)) return by_team<alt_team_size(kF)>(k, grid, st, p, found, attr, out);
     }
   }
   return hipSuccess;

@@ -43,18 +43,25 @@ enum PaKind : int { PA_NONE = 0, PA_SOFTLIM = 1, PA_RAPP = 2, PA_TOI = 3 };
 enum ChanKind : int { CH_RAYLEIGH = 1, CH_LOS = 2, CH_TWOPATH = 3, CH_TABLE = 4 };
 enum RxKind : int { RX_CNC = 1, RX_MCNC = 2 };
 
-// Measure instances (trial_inst.hip with -DINST_MEAS=1, float64 only): the same trial, the same
+// The run mode of the instances a translation unit builds (trial_inst.hip -DINST_MODE=<mode>): one
+// kernel per unit, named and shaped by the mode.  The three row modes are float64 only.
+#define MIMO_MODE_PLAIN 0  // trial_kernel: the counts alone
+#define MIMO_MODE_MEAS 1   // trial_kernel_meas
+#define MIMO_MODE_SPEC 2   // trial_kernel_spec
+#define MIMO_MODE_BEAM 3   // trial_kernel_beam
+#ifndef MIMO_INST_MODE
+#define MIMO_INST_MODE MIMO_MODE_PLAIN
+#endif
+
+// Measure instances (MIMO_MODE_MEAS): the same trial, the same
 // counts, and per trial a row of kMeasFixed + n_idx power sums over the valid in-band slots
 // (include/mimo_engine.h mimo_engine_measure_points: Es, Ez0, Re C, Im C, Ed0, then Ee_i per
 // counter index).  The row pointer is an extra argument of that kernel alone: TrialParams is
 // the stride of the per-point table and its layout is tuned (see csi_seed), and the plain
 // instances compile to the code they had (profiles/r08/measure/isa_diff.txt).
-#ifndef MIMO_MEAS_INST
-#define MIMO_MEAS_INST 0
-#endif
 constexpr int kMeasFixed = 5;  // MIMO_MEAS_FIXED
 
-// Spectrum instances (trial_inst.hip with -DINST_SPEC=1, float64 only): the same trial, the same
+// Spectrum instances (MIMO_MODE_SPEC): the same trial, the same
 // counts, and per trial a row of F + kSpecFixed doubles from the main array pass alone
 // (include/mimo_engine.h mimo_engine_spectrum_points): psd[k] = sum_a |Y_a[k]|^2 for every FFT
 // bin k (numpy.fft order, ortho transform pair), then Ex = sum_a sum_band |X_a|^2 and Re / Im of
@@ -67,12 +74,9 @@ constexpr int kMeasFixed = 5;  // MIMO_MEAS_FIXED
 // instances sit at their register cap with scratch already -- 168 VGPRs up to F 2048, 256 from
 // F 4096 -- so P more f64 registers would spill to the same memory.)  As for the measure
 // instances the row pointer is an extra argument of that kernel alone.
-#ifndef MIMO_SPEC_INST
-#define MIMO_SPEC_INST 0
-#endif
 constexpr int kSpecFixed = 3;  // MIMO_SPEC_FIXED
 
-// Beam instances (trial_inst.hip with -DINST_BEAM=1, float64 only): the same trial, the same
+// Beam instances (MIMO_MODE_BEAM): the same trial, the same
 // counts, and the main array pass hands every antenna's chain to the beamforming kernel
 // (beam.hip; include/mimo_engine.h mimo_engine_beam_points) through a per-launch buffer of
 // complex128 cells: [grid.x][A][F] of the chain output's registers d (Y_a = d / sqrt(F)), then
@@ -80,9 +84,6 @@ constexpr int kSpecFixed = 3;  // MIMO_SPEC_FIXED
 // band).  Register m of frequency thread tf is bin tf + T m before the inverse and after the
 // forward transform (the spectrum instances' statement).  Plain 16-byte stores, every cell
 // written once per launch; the buffer pointer is an extra argument of that kernel alone.
-#ifndef MIMO_BEAM_INST
-#define MIMO_BEAM_INST 0
-#endif
 
 constexpr int kMaxCsiAnt = 512;  // CSI-error runs: antennas (dynamic LDS per team, A doubles; engine.hip checks)
 constexpr uint32_t kFixedCsiTrial = 0xFFFFFFFFu;  // CSI stream counter of fixed-channel runs (oracle/sim.py draws)
@@ -798,15 +799,15 @@ __device__ __forceinline__ void fill_tw1(C* tw1_s, const C* twsrc) {
 // the LDS), SYMW_LDS = keep the pre-weighted symbols in LDS (thread-private) instead of
 // registers.  F = 2048 runs (3, 1, true): 25 KiB LDS and <= 168 VGPRs per 128-thread team.
 template <typename R, int F, int T, int NSLOT, bool ALIGNED, int CH, bool CSI, int MINW, int NBUF, bool SYMW_LDS>
-#if MIMO_MEAS_INST
+#if MIMO_INST_MODE == MIMO_MODE_MEAS
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel_meas(TrialParams<R> p0,
                                                                                                   double* meas_rows) {
   constexpr double* spec_rows = nullptr;
-#elif MIMO_SPEC_INST
+#elif MIMO_INST_MODE == MIMO_MODE_SPEC
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel_spec(TrialParams<R> p0,
                                                                                                   double* spec_rows) {
   constexpr double* meas_rows = nullptr;
-#elif MIMO_BEAM_INST
+#elif MIMO_INST_MODE == MIMO_MODE_BEAM
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel_beam(TrialParams<R> p0,
                                                                                                   double* beam_cells) {
   constexpr double* meas_rows = nullptr;
@@ -816,13 +817,13 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
   constexpr double* meas_rows = nullptr;
   constexpr double* spec_rows = nullptr;
 #endif
-#if !MIMO_BEAM_INST
+#if MIMO_INST_MODE != MIMO_MODE_BEAM
   constexpr double* beam_cells = nullptr;
 #endif
   using C = cx<R>;
-  constexpr bool MEAS = MIMO_MEAS_INST != 0 && sizeof(R) == 8;
-  constexpr bool SPEC = MIMO_SPEC_INST != 0 && sizeof(R) == 8;
-  constexpr bool BEAM = MIMO_BEAM_INST != 0 && sizeof(R) == 8;
+  constexpr bool MEAS = MIMO_INST_MODE == MIMO_MODE_MEAS && sizeof(R) == 8;
+  constexpr bool SPEC = MIMO_INST_MODE == MIMO_MODE_SPEC && sizeof(R) == 8;
+  constexpr bool BEAM = MIMO_INST_MODE == MIMO_MODE_BEAM && sizeof(R) == 8;
   // ---- which point and trial this block runs (uniform binary search over point_start)
   uint32_t pi = 0;
   if (p0.n_points > 1) {

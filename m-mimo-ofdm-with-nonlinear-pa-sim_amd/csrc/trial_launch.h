@@ -31,26 +31,26 @@ struct InstanceKey {
   bool f64;  // arithmetic type of the instance (TrialParams<double>)
 };
 
-// attr != null: return the instance's attributes (static LDS ...) instead of launching it
-#define MIMO_DECLARE_LAUNCH(FV)                                                                           \
-  hipError_t launch_trial_F##FV##_f32(const InstanceKey& k, dim3 grid, hipStream_t st,                    \
-                                      const TrialParams<float>& p, bool* found,                           \
-                                      hipFuncAttributes* attr = nullptr);                                 \
-  hipError_t launch_trial_F##FV##_f64(const InstanceKey& k, dim3 grid, hipStream_t st,                    \
-                                      const TrialParams<double>& p, bool* found,                          \
-                                      hipFuncAttributes* attr = nullptr);                                 \
-  /* the measure instance (float64 only): meas = per-trial rows [grid.x][kMeasFixed + n_idx] */           \
-  hipError_t launch_trial_F##FV##_f64_meas(const InstanceKey& k, dim3 grid, hipStream_t st,               \
-                                           const TrialParams<double>& p, bool* found,                     \
-                                           hipFuncAttributes* attr, double* meas);                        \
-  /* the spectrum instance (float64 only): spec = per-trial rows [grid.x][F + kSpecFixed] */              \
-  hipError_t launch_trial_F##FV##_f64_spec(const InstanceKey& k, dim3 grid, hipStream_t st,               \
-                                           const TrialParams<double>& p, bool* found,                     \
-                                           hipFuncAttributes* attr, double* spec);                        \
-  /* the beam instance (float64 only): cells = [2][grid.x][A][F] complex128 (Y sqrt(F), X / sqrt(F)) */  \
-  hipError_t launch_trial_F##FV##_f64_beam(const InstanceKey& k, dim3 grid, hipStream_t st,               \
-                                           const TrialParams<double>& p, bool* found,                     \
-                                           hipFuncAttributes* attr, double* cells);
+// The launcher of the instances of one FFT size, arithmetic type and mode (MIMO_MODE_*), defined by
+// the trial_inst.hip object built for them: *found = the key names one of its instances.
+// attr != null: return the instance's attributes (static LDS ...) instead of launching it.
+// out: the kernel's extra argument -- the measure instances' per-trial rows [grid.x][kMeasFixed +
+// n_idx], the spectrum instances' [grid.x][F + kSpecFixed], the beam instances' cells
+// [2][grid.x][A][F] complex128 (Y sqrt(F), X / sqrt(F)); the plain instances ignore it.
+template <int F, typename R, int MODE>
+hipError_t launch_trial(const InstanceKey& k, dim3 grid, hipStream_t st, const TrialParams<R>& p, bool* found,
+                        hipFuncAttributes* attr, double* out) = delete;
+// the combinations that are built: float32 is plain only
+#define MIMO_DECLARE_LAUNCH_AS(FV, R, MODE)                                                                  \
+  template <>                                                                                                \
+  hipError_t launch_trial<FV, R, MODE>(const InstanceKey&, dim3, hipStream_t, const TrialParams<R>&, bool*, \
+                                       hipFuncAttributes*, double*);
+#define MIMO_DECLARE_LAUNCH(FV)                           \
+  MIMO_DECLARE_LAUNCH_AS(FV, float, MIMO_MODE_PLAIN)      \
+  MIMO_DECLARE_LAUNCH_AS(FV, double, MIMO_MODE_PLAIN)     \
+  MIMO_DECLARE_LAUNCH_AS(FV, double, MIMO_MODE_MEAS)      \
+  MIMO_DECLARE_LAUNCH_AS(FV, double, MIMO_MODE_SPEC)      \
+  MIMO_DECLARE_LAUNCH_AS(FV, double, MIMO_MODE_BEAM)
 MIMO_DECLARE_LAUNCH(128)
 MIMO_DECLARE_LAUNCH(256)
 MIMO_DECLARE_LAUNCH(512)
@@ -59,5 +59,6 @@ MIMO_DECLARE_LAUNCH(2048)
 MIMO_DECLARE_LAUNCH(4096)
 MIMO_DECLARE_LAUNCH(8192)
 #undef MIMO_DECLARE_LAUNCH
+#undef MIMO_DECLARE_LAUNCH_AS
 
 }  // namespace mimo

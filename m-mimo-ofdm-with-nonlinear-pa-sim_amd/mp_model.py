@@ -559,24 +559,33 @@ class Link:
         """``measure`` for many grid points of this system in one engine call
         (mimo_engine_measure_points); ``point_params`` as for ``simulate_points``, ``n_trials``
         one number or one per point.  -> a list of ``_engine.SignalStats``.  Single GPU."""
+        def call(eng, *args):
+            uniq = sorted(set(int(i) for i in np.asarray(cnc_n_iter_lst, dtype=np.int64).reshape(-1)))
+            return eng.measure_points(*args, uniq, incl_clean_run)
+
+        (err, bits, meas, _, _), _ = self._fixed_trials_call(reroll_chan, seed_arrs, point_params, n_trials, call,
+                                                             need_snr="measure")
+        return [_engine.SignalStats(meas[i], err[i], bits[i]) for i in range(len(point_params))]
+
+    def _fixed_trials_call(self, reroll_chan, seed_arrs, point_params, n_trials, call, need_snr=None):
+        """The engine call of a mode that runs a fixed number of trials, on this link's device slot:
+        ``call(engine, points, seeds, first_trials, n_trials)``.  A point whose SNR was never set
+        is refused in the name of ``need_snr``, or without it runs at 0 dB.
+        -> (what ``call`` returned, the trial count per point)."""
         P = len(point_params)
         if len(seed_arrs) != P:
             raise ValueError("one seed_arr per point")
-        for pp in point_params:
-            if pp["snr_db"] is None:
-                raise ValueError("set_snr() must be called before measure()")
+        if need_snr and any(pp["snr_db"] is None for pp in point_params):
+            raise ValueError(f"set_snr() must be called before {need_snr}()")
         n = np.broadcast_to(np.asarray(n_trials, dtype=np.int64), (P,))
         if np.any(n < 0):
             raise ValueError("n_trials must be >= 0")
+        pts = [_engine.Engine.make_point(**dict(pp, snr_db=0.0 if pp["snr_db"] is None else pp["snr_db"]))
+               for pp in point_params]
         dev = self.device if self.device is not None else _default_device()
         acquire_device_slot(dev)  # private totals: nobody else closes them, never wait
         with SlotHeartbeat(dev):
-            eng = self.engine(reroll_chan)
-            uniq = sorted(set(int(i) for i in np.asarray(cnc_n_iter_lst, dtype=np.int64).reshape(-1)))
-            err, bits, meas, _, _ = eng.measure_points([_engine.Engine.make_point(**pp) for pp in point_params],
-                                                       [_seed64(s) for s in seed_arrs], np.zeros(P, np.int64), n,
-                                                       uniq, incl_clean_run)
-        return [_engine.SignalStats(meas[i], err[i], bits[i]) for i in range(P)]
+            return call(self.engine(reroll_chan), pts, [_seed64(s) for s in seed_arrs], np.zeros(P, np.int64), n), n
 
     # ------------------------------------------------------------------ spectrum mode
     def spectrum(self, reroll_chan: bool, seed_arr, n_trials: int):
@@ -592,20 +601,9 @@ class Link:
         one number or one per point.  The spectrum is taken before the channel and the noise, so
         a point whose SNR was never set runs at 0 dB.  -> a list of ``_engine.SpectrumStats``.
         Single GPU."""
-        P = len(point_params)
-        if len(seed_arrs) != P:
-            raise ValueError("one seed_arr per point")
-        n = np.broadcast_to(np.asarray(n_trials, dtype=np.int64), (P,))
-        if np.any(n < 0):
-            raise ValueError("n_trials must be >= 0")
-        pts = [_engine.Engine.make_point(**dict(pp, snr_db=0.0 if pp["snr_db"] is None else pp["snr_db"]))
-               for pp in point_params]
-        dev = self.device if self.device is not None else _default_device()
-        acquire_device_slot(dev)  # private totals: nobody else closes them, never wait
-        with SlotHeartbeat(dev):
-            eng = self.engine(reroll_chan)
-            _, _, spec, _, _ = eng.spectrum_points(pts, [_seed64(s) for s in seed_arrs], np.zeros(P, np.int64), n, [0])
-        return [_engine.SpectrumStats(spec[i], self.my_mod.n_sub_carr, int(n[i])) for i in range(P)]
+        (_, _, spec, _, _), n = self._fixed_trials_call(reroll_chan, seed_arrs, point_params, n_trials,
+                                                        lambda eng, *args: eng.spectrum_points(*args, [0]))
+        return [_engine.SpectrumStats(spec[i], self.my_mod.n_sub_carr, int(n[i])) for i in range(len(n))]
 
     # ------------------------------------------------------------------ beam mode
     def beampattern(self, reroll_chan: bool, seed_arr, n_trials: int, probes):
@@ -622,21 +620,9 @@ class Link:
         ``simulate_points``, ``n_trials`` one number or one per point.  The pattern is taken before
         the user's channel and the noise, so a point whose SNR was never set runs at 0 dB.
         -> a list of ``_engine.BeamStats``.  Single GPU."""
-        P = len(point_params)
-        if len(seed_arrs) != P:
-            raise ValueError("one seed_arr per point")
-        n = np.broadcast_to(np.asarray(n_trials, dtype=np.int64), (P,))
-        if np.any(n < 0):
-            raise ValueError("n_trials must be >= 0")
-        pts = [_engine.Engine.make_point(**dict(pp, snr_db=0.0 if pp["snr_db"] is None else pp["snr_db"]))
-               for pp in point_params]
-        dev = self.device if self.device is not None else _default_device()
-        acquire_device_slot(dev)  # private totals: nobody else closes them, never wait
-        with SlotHeartbeat(dev):
-            eng = self.engine(reroll_chan)
-            _, _, beam, _, _ = eng.beam_points(pts, [_seed64(s) for s in seed_arrs], np.zeros(P, np.int64), n, [0],
-                                               probes)
-        return [_engine.BeamStats(beam[i], int(n[i])) for i in range(P)]
+        (_, _, beam, _, _), n = self._fixed_trials_call(reroll_chan, seed_arrs, point_params, n_trials,
+                                                        lambda eng, *args: eng.beam_points(*args, [0], probes))
+        return [_engine.BeamStats(beam[i], int(n[i])) for i in range(len(n))]
 
     def update_distortion(self, ibo_val_db: float) -> None:
         """(mp_model.py:230-241)"""
