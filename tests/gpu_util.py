@@ -39,6 +39,20 @@ def assert_counts_equal(per, ref, label=""):
     assert bad.size == 0, f"{label}: {len(bad)} of {per.size} entries differ, first {bad[:5].tolist()}"
 
 
+def assert_f32_counts_close(per, ref, label=""):
+    """The project's float32 criterion (tests/test_gpu_geometry.py test_counts_vs_oracle): at least
+    95 % of the entries equal the float64 oracle's, none is off by more than 2 bits, and every
+    column total is within 2 % + 4."""
+    per = np.asarray(per, np.int64)
+    ref = np.asarray(ref, np.int64)
+    assert per.shape == ref.shape, (per.shape, ref.shape)
+    agree = count_agreement(per, ref)
+    assert agree >= 0.95, f"{label}: agreement {agree:.4f}"
+    assert np.abs(per - ref).max() <= 2, f"{label}: an entry is off by {int(np.abs(per - ref).max())}"
+    tot, tot_ref = per.sum(0).astype(float), ref.sum(0).astype(float)
+    assert np.all(np.abs(tot - tot_ref) <= 0.02 * tot_ref + 4), (label, tot, tot_ref)
+
+
 def count_agreement(a, b):
     """Fraction of (trial, index) entries that agree exactly."""
     a = np.asarray(a, np.int64)

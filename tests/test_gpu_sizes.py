@@ -8,7 +8,8 @@ fp64 instances have one team size per FFT size, so those cases run in f32 only.
 import numpy as np
 import pytest
 
-from gpu_util import PRECISIONS, assert_counts_equal, count_agreement, engine_for
+import limit_cases as lc
+from gpu_util import PRECISIONS, assert_counts_equal, assert_f32_counts_close, count_agreement, engine_for
 from oracle import sim
 
 pytestmark = pytest.mark.gpu
@@ -217,3 +218,36 @@ def test_csi_at_max_antennas_vs_oracle(F, S, n):
     _, _, per = eng.run(88, 0, n, iters, True, per_trial=True)
     print("csi max ant", F, eng.describe(), per.sum(0), ref.sum(0))
     assert_counts_equal(per, ref, f"CSI A=512 F={F} f64")
+
+
+@pytest.mark.parametrize("prec", PRECISIONS)
+@pytest.mark.parametrize("i", lc.LARGE_NUMBERS, ids=lc.large_id)
+def test_large_constellations_on_the_level_packing_instances(i, prec):
+    """1024- and 4096-QAM (lattice levels up to |63|, 12-bit labels) where the kernel keeps the
+    symbols as packed levels: int8 pairs with sign extension at F 4096 float64 (the 256-thread
+    team), one word per slot at F 2048, the LDS copy at F 8192 (tests/limit_cases.py LARGE; every
+    other test of these paths stops at 64-QAM, levels up to |7|).  float64: per-trial counts EXACTLY
+    the oracle's.  float32: the float32 criterion on the clean and iteration-0 columns, and on all
+    columns of the settling (MCNC) cases."""
+    A, S, F, M, ebn0, receiver, totals = lc.LARGE[i]
+    cfg = lc.large_config(i)
+    ref = lc.large_reference(i)
+    eng = engine_for(cfg, precision=prec)
+    err, bits, per = eng.run(lc.LARGE_SEED, 0, lc.LARGE_TRIALS, lc.LARGE_ITERS, True, per_trial=True)
+    desc = eng.describe()
+    eng.close()
+    per = np.asarray(per, np.int64)
+    print(f"LIMITS_LARGE {lc.large_id(i)} prec={prec} [{desc}] agreement={count_agreement(per, ref):.4f} "
+          f"per_column={(per == ref).mean(0).round(3).tolist()} max_off={int(np.abs(per - ref).max())} "
+          f"gpu={per.sum(0).tolist()} oracle={ref.sum(0).tolist()}")
+    assert desc.endswith(prec), desc
+    np.testing.assert_array_equal(err, per.sum(0))
+    assert all(int(b) == lc.LARGE_TRIALS * S * int(np.log2(M)) for b in bits)
+    if prec == "f64":
+        assert f"F={F} T={lc.LARGE_TEAM64[F]} slots={S // lc.LARGE_TEAM64[F]} aligned" in desc, desc  # F 4096: the int8-level instance
+        assert_counts_equal(per, ref, f"{lc.large_id(i)} f64")
+        assert per.sum(0).tolist() == totals
+    else:
+        assert_f32_counts_close(per[:, :2], ref[:, :2], f"{lc.large_id(i)} f32 clean and iteration 0")
+        if i in lc.LARGE_SETTLING:
+            assert_f32_counts_close(per, ref, f"{lc.large_id(i)} f32 all columns")
