@@ -169,6 +169,34 @@ __device__ __forceinline__ double ln_unit(double x) {
   const double de = (double)e;
   return fma(de, kLn2Hi, cl.y) + fma(de, kLn2Lo, p);
 }
+// ln_unit's three terms before they are added: ln(x 2^ESC) = tab + poly + de ln 2, with
+// tab = -ln c_i from the table, poly = log1p(t) and de = the exponent.  For sums of weighted logs
+// (the trial kernel's pass 1): sum_a c_a ln u_a = sum c_a tab_a + sum c_a poly_a +
+// ln 2 sum c_a de_a, three FMAs per term and ln_sum() once, instead of ln_unit's two FMAs and
+// an add and then the weighted add.
+template <int ESC = 0>
+__device__ __forceinline__ void ln_unit_parts(double x, double& tab, double& poly, double& de) {
+  const double m = __builtin_amdgcn_frexp_mant(x);
+  const int e = __builtin_amdgcn_frexp_exp(x) + ESC;
+  const uint32_t hi = (uint32_t)__double2hiint(x);
+  const double2 cl = lut64[lut_idx((hi >> 11) & 511u)];
+  const double t = fma(m, cl.x, -1.0);
+  double q = -1.0 / 6;
+  q = fma(q, t, 1.0 / 5);
+  q = fma(q, t, -1.0 / 4);
+  q = fma(q, t, 1.0 / 3);
+  q = fma(q, t, -0.5);
+  poly = fma(t * t, q, t);
+  tab = cl.y;
+  de = (double)e;
+}
+// tab + poly + ex ln 2 of such sums, ln 2 in ln_unit's two parts (the high part with the table
+// terms, the low part with the polynomial terms, as ln_unit adds them)
+__device__ __forceinline__ double ln_sum(double tab, double poly, double ex) {
+  constexpr double kLn2Hi = 6.93147180369123816490e-01;
+  constexpr double kLn2Lo = 1.90821492927058770002e-10;
+  return fma(ex, kLn2Hi, tab) + fma(ex, kLn2Lo, poly);
+}
 // sqrt of a positive normal double by the v_rsq_f64 seed (~2^-25) and one Newton step
 // (<= 2^-47.5 relative: 2^-47.83 measured on the device, tests/test_gpu_probe_math.py).
 __device__ __forceinline__ double sqrt_n1(double x) {

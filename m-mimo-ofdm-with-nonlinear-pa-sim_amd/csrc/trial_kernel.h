@@ -587,6 +587,48 @@ struct Channel {
     }
   }
 
+  // power() summed over the antennas in place (pass 1 of the aligned fp64 instances, tuning.h
+  // P1_HOIST / P1_SUMS3): acc[.][slot] takes antenna a's term of every slot.
+  // SUMS3: the logs stay in real.h ln_unit_parts' three terms, acc[0..2][s] += c (tab, poly, e)
+  // (ln_sum() assembles them once per trial); else acc[0][s] += c ln u as power() and its caller.
+  // SWAP = false: no pair swap, and q0 is the first call's counter for j = 0, formed by the caller
+  // once per trial (S/2 - 1 for thread 0, else S/4 - 1 + t): thread 0's sums of slots 0 and Q
+  // then sit in each other's place, which the caller puts right once after the loop.
+  template <bool SUMS3, bool SWAP, class PP>
+  static __device__ __forceinline__ void power_acc(const PP& p, Key key, uint32_t trial, int a, int t, uint32_t q0,
+                                                   R (&acc)[SUMS3 ? 3 : 1][NSLOT]) {
+    static_assert(ALIGNED && sizeof(R) == 8, "aligned fp64 instances");
+    constexpr int Q = SL::HALF / 2;
+    const int S = p.n_sc;
+    const R sa = p.ant_rel[a];
+    const R c = bm_c<R>(sa * sa);
+    const bool t0 = (t == 0);
+    const int qp = (S >> 2) - 1 + t;
+    auto add = [&](int s, uint32_t w0) __attribute__((always_inline)) {
+      if constexpr (SUMS3) {
+        R tab, poly, de;
+        ln_unit_parts<-32>((double)w0 + 0.5, tab, poly, de);
+        acc[0][s] = fmar(c, tab, acc[0][s]);
+        acc[1][s] = fmar(c, poly, acc[1][s]);
+        acc[2][s] = fmar(c, de, acc[2][s]);
+      } else {
+        acc[0][s] += c * bm_log(w0, R(0));
+      }
+    };
+#pragma unroll
+    for (int j = 0; j < Q; ++j) {
+      const bool sw = SWAP && (j == 0) && t0;
+      uint32_t q = (uint32_t)(qp + T * j);
+      if (j == 0) q = SWAP ? (t0 ? (uint32_t)((S >> 1) - 1) : q) : q0;
+      uint4 w = philox4x32_10<kUni>(make_uint4(q, trial, ST_CHAN, (uint32_t)a), key);
+      add(j, sw ? w.z : w.x);
+      add(j + Q, sw ? w.x : w.z);
+      w = philox4x32_10<kUni>(make_uint4((uint32_t)(t + T * j), trial, ST_CHAN, (uint32_t)a), key);
+      add(SL::HALF + j, w.x);
+      add(SL::HALF + j + Q, w.z);
+    }
+  }
+
   // Polar form of normals() (aligned instances): rho^2 = c ln u1 and the angle word w1 of
   // every slot's draw (the draw is rho e^{j 2 pi w1 2^-32}, box_muller), no sqrt / sin / cos.
   // fn(slot, rho^2, angle word) per slot, one Philox call (two slots) at a time.
@@ -875,6 +917,16 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
   // -1.4 % / -1.0 % together with them (profiles/r06/k4096/; alone +0.8 % in round 5)
   constexpr bool ALPHA1 = MIMO_ALPHA1 != 0 && (F != 4096 || (MIMO_ALPHA1_4096 != 0 && sizeof(R) == 8));
   __shared__ R alpha_s[2];
+  // VK_LDS (tuning.h; fp64 wave-split instances without CSI): the waves hand their vk partials
+  // over per thread, one ds_write_b64 each in place of the DPP tree, and the alpha wave of the
+  // antenna adds them per lane to its own (kept in registers) and runs the one tree.  W - 1
+  // regions of 64 partials, rotated with the alpha wave: wave w writes region (w - a - 1) mod W.
+  // (1.5 KiB at T 256: the F 2048 instance's LDS 51,824 -> 53,296 B, and three teams per CU are
+  // admitted up to 54,613 B; the alpha wave needs no store.)  One buffer, as vk_part with ALPHA1:
+  // written before the inverse transform's barrier, read by the alpha wave between that barrier
+  // and the forward transform's, which the next antenna's writes follow.
+  constexpr bool VK_LDS = MIMO_VK_LDS != 0 && ALPHA1 && sizeof(R) == 8 && wave_fft_used(F, T, true) && !CSI && T > 64;
+  __shared__ R vk_thr[VK_LDS ? (T / 64 - 1) * 64 : 1];
   // per-antenna mean |H|^2 (CSI model): dynamic LDS of A doubles (the launch sizes it), not
   // a static kMaxCsiAnt table -- the static 4 KiB cost F 4096 its second team per CU and F
   // 2048 its stage-2 twiddle rows (and with them the cot-tan FFT stages)
@@ -973,9 +1025,37 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
   const bool clean_cc = CSI && p.incl_clean;
   // pass 1 of the Rayleigh CSI instances in polar form (below; MIMO_CSI_POLAR=0: Cartesian)
   constexpr bool CSI_POLAR = MIMO_CSI_POLAR != 0 && CSI && CH == CH_RAYLEIGH && ALIGNED && sizeof(R) == 8;
+  // Perfect-CSI Rayleigh pass 1 of the fp64 wave-split instances (tuning.h): the array pass's
+  // register budget does not bind here (its d, r, g, h and the FFT temporaries are not live
+  // yet), so the thread id is laundered once per pass, not per antenna (P1_HOIST: the slot-to-
+  // counter maps leave the loop, and thread 0's pair swap moves from the words to the finished
+  // sums), and the weighted log sum runs as three sums per slot (P1_SUMS3).  One opaque copy per
+  // pass: nothing is shared with the array pass's loop.
+  constexpr bool P1_RAY64 = sizeof(R) == 8 && WAVEFFT && ALIGNED && CH == CH_RAYLEIGH && !CSI;
+  constexpr bool P1_HOIST = MIMO_P1_HOIST != 0 && P1_RAY64;
+  constexpr bool P1_SUMS3 = MIMO_P1_SUMS3 != 0 && P1_RAY64;
+  constexpr bool P1_ACC = P1_HOIST || P1_SUMS3;
+  R p1_acc[P1_SUMS3 ? 3 : 1][P1_ACC ? NSLOT : 1];
+  int tl_p1 = tf;
+  uint32_t q0_p1 = 0;
+  if constexpr (P1_ACC) {
+#pragma unroll
+    for (int s = 0; s < NSLOT; ++s)
+      for (int i = 0; i < (P1_SUMS3 ? 3 : 1); ++i) p1_acc[i][s] = R(0);
+  }
+  if constexpr (P1_HOIST) {
+    tl_p1 = opaque(tf);
+    q0_p1 = tl_p1 == 0 ? (uint32_t)((S >> 1) - 1) : (uint32_t)((S >> 2) - 1 + tl_p1);
+  }
   for (int a = 0; a < (MIMO_ABL(p, ABL_PASS1) ? 1 : A); ++a) {
     MIMO_ISA_MARK("pass1");
-    const int tl = opaque(tf);
+    const int tl = P1_HOIST ? tl_p1 : opaque(tf);
+    if constexpr (P1_ACC) {
+      if (!MIMO_ABL(p, ABL_RNG)) {
+        CHN::template power_acc<P1_SUMS3, !P1_HOIST>(p, key, ch_trial, a, tl, q0_p1, p1_acc);
+        continue;
+      }
+    }
     if constexpr (CH == CH_RAYLEIGH && !CSI) {
       if (!MIMO_ABL(p, ABL_RNG)) {
         R e2[NSLOT];
@@ -1056,6 +1136,22 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
     }
 #pragma unroll
     for (int s = 0; s < NSLOT; ++s) nrm2[s] = fmar(h[s].x, h[s].x, fmar(h[s].y, h[s].y, nrm2[s]));
+  }
+  if constexpr (P1_ACC) {
+    if (!MIMO_ABL(p, ABL_RNG)) {
+#pragma unroll
+      for (int s = 0; s < NSLOT; ++s) {
+        if constexpr (P1_SUMS3) nrm2[s] = ln_sum(p1_acc[0][s], p1_acc[1][s], p1_acc[2][s]);
+        else nrm2[s] = p1_acc[0][s];
+      }
+      if constexpr (P1_HOIST) {
+        // thread 0's first pair was drawn unswapped: bins S/2 and S/4 are slots 0 and Q
+        constexpr int Q = SL::HALF / 2;
+        const R n0 = nrm2[0], nq = nrm2[Q];
+        nrm2[0] = t0 ? nq : n0;
+        nrm2[Q] = t0 ? n0 : nq;
+      }
+    }
   }
   R inv_nrm[NSLOT];
   R etac_p = R(0);  // sum_k ||Hhat_k||^2 for the clean-run noise scaler (mp_model.py:304)
@@ -1298,8 +1394,13 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
         }
       }
       if (main_pass) {
-        vk = wave_sum_lane63(vk);
-        if (lane == 63) vk_part[vkb][wid] = vk;  // read after the IFFT's first barrier
+        if constexpr (VK_LDS) {
+          const int aw = a & (W - 1);
+          if (wid != aw) vk_thr[((wid - aw - 1) & (W - 1)) * 64 + lane] = vk;  // read after the IFFT's first barrier
+        } else {
+          vk = wave_sum_lane63(vk);
+          if (lane == 63) vk_part[vkb][wid] = vk;  // read after the IFFT's first barrier
+        }
       }
       SL::scatter(d, x, t0);
       if constexpr (BEAM) {
@@ -1320,9 +1421,22 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
       if (!MIMO_ABL(p, ABL_PA)) pa_block<COLD_OUT>(p.pa_kind, d, p.sat_tx, p.sqrt_sat_tx, p.inv_sat_tx, p.rapp_p, p.toi_tx);
       // alpha_a (Bussgang gain of antenna a's PA from its precoding power, main pass only)
       auto alpha_of_vk = [&]() __attribute__((always_inline)) -> R {
-        R vks = vk_part[vkb][0];
+        R vks;
+        if constexpr (VK_LDS) {
+          // the alpha wave: its own partials and the other waves', region by region, then the
+          // one tree; lane 63's sum to every lane, so that the branches below stay uniform
+          vks = vk;
 #pragma unroll
-        for (int i = 1; i < W; ++i) vks += vk_part[vkb][i];
+          for (int i = 0; i < W - 1; ++i) vks += vk_thr[i * 64 + lane];
+          const uint64_t u = __builtin_bit_cast(uint64_t, (double)wave_sum_lane63(vks));
+          const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, 63);
+          const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), 63);
+          vks = (R)__builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+        } else {
+          vks = vk_part[vkb][0];
+#pragma unroll
+          for (int i = 1; i < W; ++i) vks += vk_part[vkb][i];
+        }
         const R x = fmar(vks, PRE_EW ? p.inv_vk0_f : p.inv_vk0, -R(1));
         // Polynomial alpha: -7 % at F = 2048, but +3 % at F = 8192 (SGPR pressure of the
         // 8 waves/team instance, tools/ab_libs.py), so only up to F = 4096.

@@ -28,6 +28,39 @@
 #define MIMO_ALPHA1_4096 1
 #endif
 
+// ---- pass 1 of the fp64 wave-split instances (F <= 2048) with a perfect-CSI Rayleigh channel
+// (trial_kernel.h P1_*).  The array pass's register budget does not bind there: its d, r, g, h and
+// the FFT temporaries are not live yet.  Config 2, 100 interleaved rounds, A/A spread 0.03 ms
+// (profiles/r16/pass1_vk/ab_long.json): HOIST -0.22 ms (-0.5 %), SUMS3 -0.10 ms (-0.2 %), both
+// -0.35 ms (-0.8 %); the pass-1 loop 157 -> 141 VALU per antenna-wave, registers and scratch as
+// before.
+// P1_HOIST: the thread id laundered once ahead of the loop instead of per antenna, so the
+// counters of the two Philox calls are formed once, and thread 0's pair swap is applied to the
+// finished sums once per trial, not to every antenna's words (0: per antenna, as the array pass
+// must).
+// P1_SUMS3: three running sums per slot, c tab, c poly and c e of real.h ln_unit_parts, assembled
+// into the norm once per trial (3 FMAs per draw instead of 4; 0: every log finished per draw).
+// The sum order differs, so the norm moves in its last bits: against the long-double sum 4.1
+// units of the last place at most where the per-draw form has 7.3
+// (tests/test_pass1_logsum_cpu.py).
+#ifndef MIMO_P1_HOIST
+#define MIMO_P1_HOIST 1
+#endif
+#ifndef MIMO_P1_SUMS3
+#define MIMO_P1_SUMS3 1
+#endif
+
+// ---- the vk partials of the fp64 wave-split instances without CSI per thread in LDS (1.5 KiB
+// per 256-thread team: 53,296 B of LDS, three teams per CU still): one ds_write_b64 per thread
+// of the three other waves, and the antenna's alpha wave adds them per lane to its own and runs
+// the one DPP tree (0: every wave reduces its own partial).  The sum order differs from the
+// tree-per-wave form, so alpha moves in its last bits.  Config 2 -0.34 ms (-0.8 %), with the two
+// above -0.59 ms (-1.3 %), SQ_INSTS_VALU 2.012e10 -> 1.972e10 per launch
+// (profiles/r16/pass1_vk/).
+#ifndef MIMO_VK_LDS
+#define MIMO_VK_LDS 1
+#endif
+
 // ---- Philox rounds whose words are uniform across the team on the SALU (philox.h kUni)
 // Always in the fp64 wave-split instances (F <= 2048).  F 4096: with CSI only (-2.4 % on the
 // paper-CSI line, +1.1 % without CSI, profiles/r06/k4096/).  F 8192: with the folded weight

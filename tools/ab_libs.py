@@ -3,8 +3,10 @@
     python tools/ab_libs.py abl/lib_base.so m-mimo-ofdm-with-nonlinear-pa-sim_amd/libmimo_engine.so
 
 Each library gets its own engine (BASELINE config 2 via bench.make_engine); launches
-alternate between them round by round.  Prints median / min kernel ms per launch and the
-error totals (builds that differ only in fp32 rounding agree to a few errors in 1e7 bits).
+alternate between them round by round.  Prints median / min kernel ms per launch, every round's
+time, the per-round difference to the first library (median / min / max: naming the first library
+twice gives the A/A spread a gain is judged against) and the error totals (builds that differ
+only in fp32 rounding agree to a few errors in 1e7 bits).
 """
 import argparse
 import ctypes
@@ -54,8 +56,12 @@ def main():
     out = []
     for i, path in enumerate(args.libs):
         ms = np.asarray(res[i])
+        # per round against the first library: the paired difference takes the drift of the box out
+        d = ms - np.asarray(res[0])
         out.append(dict(lib=path, desc=errs[i][1], median_ms=float(np.median(ms)), min_ms=float(ms.min()),
-                        trials_per_s=args.batch / (np.median(ms) / 1e3), errors=errs[i][0]))
+                        trials_per_s=args.batch / (np.median(ms) / 1e3), errors=errs[i][0],
+                        diff_median_ms=float(np.median(d)), diff_min_ms=float(d.min()), diff_max_ms=float(d.max()),
+                        ms=[round(float(x), 4) for x in ms]))
     print(json.dumps(out, indent=1))
 
 
