@@ -14,6 +14,8 @@
  *                                  (out-of-band emission, Bussgang gain, efficiency)
  *     mimo_engine_beam_points      the same trials with the signal, distortion and out-of-band power
  *                                  the array radiates towards a list of probe positions (beampattern)
+ *     mimo_engine_envelope_points  the same trials with the distribution of the instantaneous power at
+ *                                  every antenna's PA input and output (CCDF / PAPR, compression)
  *     mimo_engine_run_points    <- the drivers' grid loops over (IBO, Eb/N0), one launch
  *                                  for many points   main_mp_miso_cnc_constant_ber_req_ebn0_vs_ibo.py:100-215
  *   fine seams (float64 stage kernels, caller-owned host arrays)
@@ -254,6 +256,48 @@ int32_t mimo_engine_beam_points(mimo_engine* e, int32_t n_points, const mimo_poi
                                 int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
                                 uint32_t* per_trial, const double* probes, int32_t n_probes, double* beam_out,
                                 double* per_trial_beam);
+/* Envelope mode (float64 engines): the trials, arguments, launch splitting and point rules of
+ * mimo_engine_run_points and the same counts, plus per point a row of
+ * n_env = 2 MIMO_ENV_BINS + MIMO_ENV_FIXED = 260 sums over the main transmission of every trial, over
+ * all antennas a and all n_fft time samples n, with x_a[n] the PA input -- the ortho IFFT of the
+ * precoded input X_a, as the spectrum mode defines X_a -- and y_a[n] = PA(x_a[n]):
+ *   [b], b < 128       hist_in[b]: the number of samples whose |x_a[n]|^2 falls in bin b
+ *   [128 + b]          hist_out[b]: the same for |y_a[n]|^2
+ *   [256]              Pin = sum |x|^2
+ *   [257]              Pout = sum |y|^2
+ *   [258], [259]       Re, Im of C = sum y conj(x)
+ * (by Parseval the three fixed sums equal the spectrum mode's Ex, sum_k psd[k] and C), from which
+ * the CCDF of the instantaneous power before and after the PA, the PAPR at a probability, the
+ * efficiency Pout / Pin and the Bussgang gain C / Pin follow.  The bins are floating-point bins,
+ * defined on the bits of a double so that the device and any reference compute them with the same
+ * integer operation: with scale = 1.0625 / ref_pow formed once on the host in double and
+ * v = pw scale, pw = re re + im im of the sample,
+ *   bin = clamp((bits(v) >> 49) - 8088, 0, 127),   8088 = (1023 - 12) << 3
+ * -- 8 linear sub-bins per octave over 16 octaves; bin 0 also takes everything below (0 included),
+ * bin 127 everything above (+inf included).  The lower edge of bin b >= 1 in units of
+ * u = |.|^2 / ref_pow is 2^(-12 + b/8) (1 + (b%8)/8) 16/17 (integer division): about -36.4 dB to
+ * +11.5 dB in steps of 0.28 to 0.51 dB.  The factor 17/16 keeps round figures off the edges: a soft
+ * limiter puts every clipped sample at exactly sat_pow, which with ref_pow the mean power is
+ * u = 10^(IBO/10), and u = 10^(i/10) for every integer i in [-3, 9] dB lies at least 0.8 % inside a
+ * bin (IBO 0 dB would sit on the edge u = 1 without it).  MCNC re-transmissions and the CNC
+ * receiver's chain do not contribute.  env_out: [n_points][n_env] totals (ADDED to; the histogram
+ * cells are integers held exactly in doubles -- a trial has at most 2^25 samples -- so they are
+ * bit-identical whatever the order or split; the fixed sums are summed in a fixed order: equal calls
+ * return equal bits).  per_trial_env: optional [sum n_trials][n_env] rows in point order, NULL to
+ * skip; they do not depend on how the call is split into launches.  The per-trial rows of one launch
+ * live in a device buffer of at most MIMO_ENV_BUFFER_BYTES (256 MiB, a design figure), so an
+ * envelope launch holds floor(2^28 / (8 n_env)) = 129,055 trials, or fewer
+ * (MIMO_MAX_LAUNCH_TRIALS).  MIMO_EINVAL, before any HIP call: a float32 engine, a null env_out,
+ * a ref_pow that is not finite or not > 0, or whose 1.0625 / ref_pow is not finite or not > 0.
+ * (Added within ABI 8: a library without it is reported by name.) */
+enum { MIMO_ENV_BINS = 128, MIMO_ENV_FIXED = 4 };
+#define MIMO_ENV_BUFFER_BYTES (256u << 20)
+int32_t mimo_envelope_width(void);              /* 2 MIMO_ENV_BINS + MIMO_ENV_FIXED = 260; host only */
+int32_t mimo_envelope_edges(double* edges_out); /* MIMO_ENV_BINS - 1 lower edges of bins 1..127, as u; host only */
+int32_t mimo_engine_envelope_points(mimo_engine* e, int32_t n_points, const mimo_point* points, const uint64_t* seeds,
+                                    const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters,
+                                    int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
+                                    uint32_t* per_trial, double ref_pow, double* env_out, double* per_trial_env);
 /* Device time of the trial kernels of the last run, in ms (HIP events on the engine stream). */
 double mimo_engine_last_kernel_ms(const mimo_engine* e);
 /* ... and of the beamforming kernels of the last beam call (0 after any other call). */

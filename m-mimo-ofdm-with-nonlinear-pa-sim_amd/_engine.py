@@ -75,6 +75,11 @@ SYMBOLS = {
     "mimo_engine_beam_points": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(MimoPoint), _u64p,
                                                  _u64p, _u64p, _i32p, ctypes.c_int32, ctypes.c_int32, _u64p, _u64p,
                                                  _u32p, _dp, ctypes.c_int32, _dp, _dp]),
+    "mimo_envelope_width": (ctypes.c_int32, []),
+    "mimo_envelope_edges": (ctypes.c_int32, [_dp]),
+    "mimo_engine_envelope_points": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(MimoPoint), _u64p,
+                                                     _u64p, _u64p, _i32p, ctypes.c_int32, ctypes.c_int32, _u64p, _u64p,
+                                                     _u32p, ctypes.c_double, _dp, _dp]),
     "mimo_engine_last_kernel_ms": (ctypes.c_double, [ctypes.c_void_p]),
     "mimo_engine_last_beam_ms": (ctypes.c_double, [ctypes.c_void_p]),
     "mimo_engine_describe": (ctypes.c_char_p, [ctypes.c_void_p]),
@@ -111,6 +116,9 @@ ABI_VERSION = 8  # include/mimo_engine.h MIMO_ABI_VERSION
 MEAS_FIXED = 5   # include/mimo_engine.h MIMO_MEAS_FIXED
 SPEC_FIXED = 3   # include/mimo_engine.h MIMO_SPEC_FIXED
 BEAM_FIXED = 5   # include/mimo_engine.h MIMO_BEAM_FIXED
+ENV_BINS = 128   # include/mimo_engine.h MIMO_ENV_BINS
+ENV_FIXED = 4    # include/mimo_engine.h MIMO_ENV_FIXED
+ENV_WIDTH = 2 * ENV_BINS + ENV_FIXED
 
 
 def lib():
@@ -400,6 +408,100 @@ class BeamStats:
                 f"distortion directivity={self.directivity('distortion'):.3f})")
 
 
+def envelope_edges():
+    """Lower edges of the envelope bins 1 ... 127 in units of u = |.|^2 / ref_pow (mimo_envelope_edges)."""
+    out = np.empty(ENV_BINS - 1, np.float64)
+    _check(lib().mimo_envelope_edges(_ptr(out, ctypes.c_double)))
+    return out
+
+
+class EnvelopeStats:
+    """Envelope of an envelope call (mimo_engine_envelope_points): one row
+    ``[hist_in[0..127], hist_out[0..127], Pin, Pout, Re C, Im C]`` of sums over trials, antennas and
+    time samples -- the histograms of the instantaneous power at the PA inputs and outputs over the
+    bins whose lower edges are ``edges`` (in units of ``u = |.|^2 / ref_pow``; bin 0 takes everything
+    below ``edges[0]``), the two total powers and the correlation of output and input.
+    ``a + b`` pools two measurements of one system taken with the same ``ref_pow``."""
+
+    def __init__(self, row, n_ant, n_fft, n_trials, ref_pow):
+        self.row = np.array(row, np.float64).reshape(-1)
+        if self.row.size != ENV_WIDTH:
+            raise ValueError(f"an envelope row has {ENV_WIDTH} entries")
+        self.n_ant, self.n_fft, self.n_trials = int(n_ant), int(n_fft), int(n_trials)
+        self.ref_pow = float(ref_pow)
+        if self.n_ant < 1 or self.n_fft < 1 or self.n_trials < 0 or not self.ref_pow > 0:
+            raise ValueError("n_ant and n_fft are >= 1, n_trials >= 0 and ref_pow > 0")
+        self.edges = envelope_edges()
+
+    hist_in = property(lambda self: self.row[:ENV_BINS].copy())
+    hist_out = property(lambda self: self.row[ENV_BINS:2 * ENV_BINS].copy())
+    p_in = property(lambda self: float(self.row[2 * ENV_BINS]))
+    p_out = property(lambda self: float(self.row[2 * ENV_BINS + 1]))
+    c = property(lambda self: complex(self.row[2 * ENV_BINS + 2], self.row[2 * ENV_BINS + 3]))
+
+    @property
+    def edges_db(self):
+        return 10.0 * np.log10(self.edges)
+
+    @property
+    def n_samples(self):
+        """Samples per histogram: trials x antennas x n_fft."""
+        return self.n_trials * self.n_ant * self.n_fft
+
+    def _ccdf(self, hist):
+        # exact tail sums: the cells are integers, their sums stay below 2^53
+        tail = np.cumsum(hist[::-1])[::-1][1:]
+        out = np.zeros(ENV_BINS - 1)
+        if self.n_samples > 0:
+            out = tail / float(self.n_samples)
+        return out
+
+    @property
+    def ccdf_in(self):
+        """P(u >= edges[i]) at the PA inputs."""
+        return self._ccdf(self.row[:ENV_BINS])
+
+    @property
+    def ccdf_out(self):
+        """P(u >= edges[i]) at the PA outputs."""
+        return self._ccdf(self.row[ENV_BINS:2 * ENV_BINS])
+
+    @property
+    def mean_in_db(self):
+        """Mean input sample power over ref_pow, in dB."""
+        return _ratio_db(self.p_in, self.n_samples * self.ref_pow)
+
+    @property
+    def efficiency(self):
+        """Pout / Pin: radiated power over PA input power."""
+        return self.p_out / self.p_in if self.p_in > 0 else np.inf
+
+    @property
+    def gain(self):
+        """C / Pin: the array's measured Bussgang gain."""
+        return self.c / self.p_in if self.p_in > 0 else complex(np.inf)
+
+    def level_db(self, prob, which="in"):
+        """The smallest edge [dB] whose CCDF is <= ``prob`` (``which``: "in" or "out"); nan if none."""
+        if which not in ("in", "out"):
+            raise ValueError('which must be "in" or "out"')
+        ccdf = self.ccdf_in if which == "in" else self.ccdf_out
+        ok = np.flatnonzero(ccdf <= prob)
+        return float(self.edges_db[ok[0]]) if ok.size else float("nan")
+
+    def __add__(self, other):
+        if not isinstance(other, EnvelopeStats):
+            return NotImplemented
+        if (other.n_ant, other.n_fft, other.ref_pow) != (self.n_ant, self.n_fft, self.ref_pow):
+            raise ValueError("envelopes of different systems or reference powers cannot be pooled")
+        return EnvelopeStats(self.row + other.row, self.n_ant, self.n_fft, self.n_trials + other.n_trials, self.ref_pow)
+
+    def __repr__(self):
+        return (f"EnvelopeStats(n_samples={self.n_samples}, mean_in_db={self.mean_in_db:.3f}, "
+                f"level_db(1e-3)={self.level_db(1e-3):.2f}, efficiency={self.efficiency:.4f}, "
+                f"gain={abs(self.gain):.4f})")
+
+
 class Engine:
     """One configured system (the deep-copied objects of a ``Link``) on one GPU."""
 
@@ -434,6 +536,7 @@ class Engine:
         self._h, self._L = h, L   # the library this handle belongs to
         self.n_sub_carr, self.constel_size = n_sub_carr, constel_size
         self.n_fft = n_fft
+        self.n_ant = n_ant
 
     @staticmethod
     def make_point(ibo_db, snr_db, avg_symbol_power, pa_kind, sat_pow=0.0, p_hardness=0.0, toi_coeff=0.0,
@@ -566,6 +669,23 @@ class Engine:
         err, bits, beam, pt, pb = self.beam_points([self._one_point(point)], [seed], [first_trial], [n_trials], iters,
                                                    probes, incl_clean, per_trial)
         return err[0], bits[0], beam[0], pt, pb
+
+    def envelope_points(self, points, seeds, first_trials, n_trials, iters, ref_pow, incl_clean=False,
+                        per_trial=False):
+        """run_points in envelope mode (mimo_engine_envelope_points; float64 engines): the same trials
+        and counts, and per point the row of the two instantaneous-power histograms (PA input and
+        output, bins relative to ``ref_pow``), Pin, Pout and C.
+        -> (err[P, n_idx], bits[P, n_idx], env[P, 260], per-trial counts [sum n_trials, n_idx] or None,
+        per-trial rows [sum n_trials, 260] or None); EnvelopeStats(env[i], n_ant, n_fft, n_trials[i], ref_pow)."""
+        return self._points_call("mimo_engine_envelope_points", points, seeds, first_trials, n_trials, iters,
+                                 incl_clean, per_trial, lambda n_idx: ((ENV_WIDTH,), (ctypes.c_double(float(ref_pow)),)))
+
+    def envelope(self, seed, first_trial, n_trials, iters, ref_pow, incl_clean=False, per_trial=False, point=None):
+        """One point (the last set_point's, or ``point``: make_point keywords / MimoPoint).
+        -> (err[n_idx], bits[n_idx], env[260], per-trial counts or None, per-trial rows or None)."""
+        err, bits, env, pt, pe = self.envelope_points([self._one_point(point)], [seed], [first_trial], [n_trials],
+                                                      iters, ref_pow, incl_clean, per_trial)
+        return err[0], bits[0], env[0], pt, pe
 
     @property
     def kernel_ms(self):

@@ -169,9 +169,10 @@ struct mimo_engine {
   Buf<double> ant_rel64, f_rel64, f_over_c, tx_pos_dev;
   Buf<uint32_t> counts;
   Buf<unsigned long long> tot;            // [points][n_idx] totals of one run
-  // row-mode calls (measure, spectrum, beam: one mode per call, so one pair): the per-trial rows of
-  // one launch and their per-slice partials.  Spectrum and beam rows hold at most
-  // MIMO_SPEC_BUFFER_BYTES / MIMO_BEAM_ROWS_BYTES (that bounds the trials of their launches).
+  // row-mode calls (measure, spectrum, beam, envelope: one mode per call, so one pair): the per-trial
+  // rows of one launch and their per-slice partials.  Spectrum, beam and envelope rows hold at most
+  // MIMO_SPEC_BUFFER_BYTES / MIMO_BEAM_ROWS_BYTES / MIMO_ENV_BUFFER_BYTES (that bounds the trials of
+  // their launches).
   Buf<double> rows;                       // [launch blocks][row width]
   Buf<double> part;                       // [launch slices][row width]
   // beam calls: the beam instances' cells of one launch (at most the beam buffer's bytes: it bounds
@@ -241,7 +242,7 @@ mimo::InstanceKey select_instance(const mimo_engine* e, bool csi) {
 // table over the FFT sizes; the combinations that are not built are not found.
 template <typename R, int MODE>
 hipError_t launch_sized(const mimo::InstanceKey& k, dim3 grid, hipStream_t st, const mimo::TrialParams<R>& p,
-                        bool* found, hipFuncAttributes* attr, double* out) {
+                        bool* found, hipFuncAttributes* attr, double* out, double aux) {
   *found = false;
 #ifdef MIMO_ONLY_F  // single-size diagnostic / A-B builds (Makefile targets ablation, variant): plain only
   constexpr bool built = MODE == MIMO_MODE_PLAIN;
@@ -250,7 +251,7 @@ hipError_t launch_sized(const mimo::InstanceKey& k, dim3 grid, hipStream_t st, c
 #endif
   if constexpr (built) {
 #define MIMO_LAUNCH_F(FV) \
-  case FV: return mimo::launch_trial<FV, R, MODE>(k, grid, st, p, found, attr, out);
+  case FV: return mimo::launch_trial<FV, R, MODE>(k, grid, st, p, found, attr, out, aux);
     switch (k.F) {
 #ifdef MIMO_ONLY_F
       MIMO_LAUNCH_F(MIMO_ONLY_F)
@@ -272,12 +273,13 @@ hipError_t launch_sized(const mimo::InstanceKey& k, dim3 grid, hipStream_t st, c
 
 template <typename R>
 hipError_t launch(int mode, const mimo::InstanceKey& k, dim3 grid, hipStream_t st, const mimo::TrialParams<R>& p,
-                  bool* found, hipFuncAttributes* attr, double* out) {
+                  bool* found, hipFuncAttributes* attr, double* out, double aux = 0.0) {
   switch (mode) {
-    case MIMO_MODE_MEAS: return launch_sized<R, MIMO_MODE_MEAS>(k, grid, st, p, found, attr, out);
-    case MIMO_MODE_SPEC: return launch_sized<R, MIMO_MODE_SPEC>(k, grid, st, p, found, attr, out);
-    case MIMO_MODE_BEAM: return launch_sized<R, MIMO_MODE_BEAM>(k, grid, st, p, found, attr, out);
-    default: return launch_sized<R, MIMO_MODE_PLAIN>(k, grid, st, p, found, attr, out);
+    case MIMO_MODE_MEAS: return launch_sized<R, MIMO_MODE_MEAS>(k, grid, st, p, found, attr, out, aux);
+    case MIMO_MODE_SPEC: return launch_sized<R, MIMO_MODE_SPEC>(k, grid, st, p, found, attr, out, aux);
+    case MIMO_MODE_BEAM: return launch_sized<R, MIMO_MODE_BEAM>(k, grid, st, p, found, attr, out, aux);
+    case MIMO_MODE_ENV: return launch_sized<R, MIMO_MODE_ENV>(k, grid, st, p, found, attr, out, aux);
+    default: return launch_sized<R, MIMO_MODE_PLAIN>(k, grid, st, p, found, attr, out, aux);
   }
 }
 
@@ -297,7 +299,11 @@ struct BeamCall {
 //   its rows fit MIMO_SPEC_BUFFER_BYTES;
 //  beam (mimo_engine_beam_points): rows of n_probes MIMO_BEAM_FIXED sums; the beam instance runs
 //   and fills the launch's cells, the beamforming kernel (beam.hip) forms the per-trial rows from
-//   them, reduce_spec the slice partials; the cells and rows of a launch fit their buffers.
+//   them, reduce_spec the slice partials; the cells and rows of a launch fit their buffers;
+//  envelope (mimo_engine_envelope_points): rows of 2 MIMO_ENV_BINS + MIMO_ENV_FIXED sums (the two
+//   histograms' cells are integers in doubles); the envelope instance runs with the bin scale
+//   1.0625 / ref_pow as its second extra argument, reduce_spec forms the slice partials, and a
+//   launch holds no more trials than its rows fit MIMO_ENV_BUFFER_BYTES.
 struct RowMode {
   int mode = MIMO_MODE_PLAIN;
   int width = 0;                        // doubles of one trial's row, and of one point's in out
@@ -305,6 +311,7 @@ struct RowMode {
   double* out = nullptr;                // [points][width], added into
   double* per_trial_out = nullptr;      // [trials of the call][width], or null
   const BeamCall* beam = nullptr;       // beam only
+  double aux = 0.0;                     // envelope only: the kernel's bin scale
   bool rows() const { return mode != MIMO_MODE_PLAIN; }
 };
 
@@ -619,12 +626,14 @@ int validate_points(const mimo_engine* e, int n_points, const mimo_point* pts, c
 
 // The CSI instances add n_ant reals of dynamic LDS (the per-antenna power table) to their
 // static LDS: check the sum against the CU's LDS before launching (F 8192 holds
-// ~157 KiB statically, so A = 512 (4 KiB) is the edge).
-int check_csi_lds(const mimo_engine* e, const mimo::InstanceKey& key) {
+// ~157 KiB statically, so A = 512 (4 KiB) is the edge).  mode: the instance the call launches --
+// the envelope instances hold their histogram on top of the plain instance's static LDS (the
+// measure, spectrum and beam instances hold what the plain one holds).
+int check_csi_lds(const mimo_engine* e, const mimo::InstanceKey& key, int mode) {
   hipFuncAttributes fa{};
   bool found = false;
   const hipError_t qe =
-      key.f64 ? launch(MIMO_MODE_PLAIN, key, dim3(0), e->stream, mimo::TrialParams<double>{}, &found, &fa, nullptr)
+      key.f64 ? launch(mode, key, dim3(0), e->stream, mimo::TrialParams<double>{}, &found, &fa, nullptr)
               : launch(MIMO_MODE_PLAIN, key, dim3(0), e->stream, mimo::TrialParams<float>{}, &found, &fa, nullptr);
   int lds_max = 0;
   if (!found || qe != hipSuccess ||
@@ -821,7 +830,7 @@ int run_launch(mimo_engine* e, const mimo::InstanceKey& key, const mimo::TrialPa
   bool found = false;
   // (the beam instances fill the launch's cells; the beamforming kernel forms the rows from them)
   const hipError_t le =
-      launch(rm.mode, key, dim3(nb), e->stream, kp, &found, nullptr, rm.beam ? e->bcell.p : e->rows.p);
+      launch(rm.mode, key, dim3(nb), e->stream, kp, &found, nullptr, rm.beam ? e->bcell.p : e->rows.p, rm.aux);
   if (!found) return fail(MIMO_ENOKERNEL, "no kernel instance for " + e->desc);
   if (le != hipSuccess) return fail(MIMO_EHIP, std::string("trial kernel launch: ") + hipGetErrorString(le));
   HIP_TRY(hipEventRecord(e->ev1, e->stream));
@@ -906,7 +915,7 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
   const mimo::InstanceKey key = select_instance(e, csi);
   if (int rc = ensure_device(e)) return rc;
   if (csi)
-    if (int rc = check_csi_lds(e, key)) return rc;
+    if (int rc = check_csi_lds(e, key, rm.mode)) return rc;
   if (!c.reroll_chan && (c.channel_kind == MIMO_CH_LOS || c.channel_kind == MIMO_CH_TWOPATH)) {
     // fixed RX: jitter span 0 around (x0, x0); only consistent when rx_y == rx_x
     // (table channels never use the RX position)
@@ -1093,6 +1102,40 @@ int32_t mimo_engine_beam_points(mimo_engine* e, int32_t n_points, const mimo_poi
     }
   }
   for (int k = 0; k < F; ++k) bc.geo[2 * na + k] = e->freqs[k] / kSpeedOfLight;
+  return run_points(e, n_points, points, seeds, first_trial, n_trials, iters, n_iters, incl_clean, err_out, bits_out,
+                    per_trial, rm);
+}
+
+int32_t mimo_envelope_width(void) { return 2 * MIMO_ENV_BINS + MIMO_ENV_FIXED; }
+
+// The lower edge of bin b >= 1 in units of u = |.|^2 / ref_pow: the smallest v = 1.0625 u whose
+// bits >> 49 are 8088 + b is 2^(-12 + b / 8) (1 + (b % 8) / 8), exactly.
+int32_t mimo_envelope_edges(double* edges_out) {
+  if (!edges_out) return fail(MIMO_EINVAL, "null edges_out");
+  for (int b = 1; b < MIMO_ENV_BINS; ++b)
+    edges_out[b - 1] = std::ldexp(1.0 + (b % 8) / 8.0, -12 + b / 8) * 16.0 / 17.0;
+  return MIMO_OK;
+}
+
+int32_t mimo_engine_envelope_points(mimo_engine* e, int32_t n_points, const mimo_point* points, const uint64_t* seeds,
+                                    const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters,
+                                    int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
+                                    uint32_t* per_trial, double ref_pow, double* env_out, double* per_trial_env) {
+  if (!e) return fail(MIMO_EINVAL, "null engine");
+  if (e->cfg.precision != MIMO_PREC_F64)
+    return fail(MIMO_EINVAL, "envelope needs a float64 engine (no float32 envelope instances are built)");
+  if (!env_out) return fail(MIMO_EINVAL, "null env_out");
+  if (!(ref_pow > 0) || !std::isfinite(ref_pow)) return fail(MIMO_EINVAL, "ref_pow must be finite and > 0");
+  const double scale = 1.0625 / ref_pow;
+  if (!(scale > 0) || !std::isfinite(scale))
+    return fail(MIMO_EINVAL, "ref_pow leaves no finite bin scale 1.0625 / ref_pow > 0");
+  RowMode rm;
+  rm.mode = MIMO_MODE_ENV;
+  rm.width = 2 * MIMO_ENV_BINS + MIMO_ENV_FIXED;
+  rm.max_trials = MIMO_ENV_BUFFER_BYTES / (sizeof(double) * (size_t)rm.width);
+  rm.out = env_out;
+  rm.per_trial_out = per_trial_env;
+  rm.aux = scale;
   return run_points(e, n_points, points, seeds, first_trial, n_trials, iters, n_iters, incl_clean, err_out, bits_out,
                     per_trial, rm);
 }

@@ -1,6 +1,7 @@
 // Instantiates the fused trial kernel for one FFT size, arithmetic type and run mode: compiled
 // once per -DINST_F=<size> -DINST_F64=<0|1>, and once more per size with -DINST_F64=1
-// -DINST_MODE=<1 measure | 2 spectrum | 3 beam> (trial_kernel.h MIMO_MODE_*; 0, plain, by default).
+// -DINST_MODE=<1 measure | 2 spectrum | 3 beam | 4 envelope> (trial_kernel.h MIMO_MODE_*; 0, plain, by
+// default).
 #include <type_traits>
 
 #ifndef INST_F
@@ -13,7 +14,7 @@
 #define INST_MODE 0
 #endif
 #if INST_MODE && !INST_F64
-#error "the measure, spectrum and beam instances are float64 only"
+#error "the measure, spectrum, beam and envelope instances are float64 only"
 #endif
 #define MIMO_INST_MODE INST_MODE
 
@@ -26,6 +27,8 @@
 #define MIMO_TRIAL_KERNEL trial_kernel_spec
 #elif INST_MODE == MIMO_MODE_BEAM
 #define MIMO_TRIAL_KERNEL trial_kernel_beam
+#elif INST_MODE == MIMO_MODE_ENV
+#define MIMO_TRIAL_KERNEL trial_kernel_env
 #else
 #define MIMO_TRIAL_KERNEL trial_kernel
 #endif
@@ -57,7 +60,8 @@ constexpr Profile profile_for(int T, bool aligned, int ch) {
   // fp64 up to F 2048: 3 waves/SIMD (168 VGPRs; the symbols rebuilt from the labels and
   // |Hhat|^2 after the FFT, so 49.5 KiB of LDS per 256-thread team and 3 teams per CU):
   // -8.5 % at config 2 (profiles/r03/ab_w3/).
-  if (kF64 && kF <= 2048) return Profile{MIMO_W64_2048, 1, false};
+  // (the envelope instances: 2 waves/SIMD, 256 VGPRs, for the PA input they hold across the PA)
+  if (kF64 && kF <= 2048) return Profile{INST_MODE == MIMO_MODE_ENV ? MIMO_ENV_W64_2048 : MIMO_W64_2048, 1, false};
   if (kF64 && kF == 4096) return Profile{2, 1, false};  // 16-point team, symbols from levels: 2 teams/CU
   if (kF64) return Profile{2, 1, true};
   if (!aligned) return Profile{2, kF >= 4096 ? 1 : 2, true};  // one buffer from F = 4096: 2 teams/CU
@@ -68,15 +72,19 @@ constexpr Profile profile_for(int T, bool aligned, int ch) {
 
 // attr != null: no launch, the instance's attributes instead (its static LDS, which the
 // engine checks with the CSI table's dynamic LDS against the device limit before a launch).
-// out: the kernel's extra argument (trial_launch.h launch_trial; the plain kernel has none).
+// out, aux: the kernel's extra arguments (trial_launch.h launch_trial; the plain kernel has none,
+// the envelope kernel alone takes aux).
 template <int T, int NSLOT, bool AL, int CH, bool CSI>
-hipError_t go(dim3 grid, hipStream_t st, const TrialParams<Real>& p, hipFuncAttributes* attr, double* out) {
+hipError_t go(dim3 grid, hipStream_t st, const TrialParams<Real>& p, hipFuncAttributes* attr, double* out,
+              double aux) {
   constexpr Profile pr = profile_for(T, AL, CH);
   auto* kern = &MIMO_TRIAL_KERNEL<Real, kF, T, NSLOT, AL, CH, CSI, pr.minw, pr.nbuf, pr.symw_lds>;
   if (attr) return hipFuncGetAttributes(attr, reinterpret_cast<const void*>(kern));
   // CSI: the per-antenna power table is dynamic LDS, A reals (trial_kernel pw_csi)
   const size_t dyn = CSI ? sizeof(Real) * (size_t)p.n_ant : 0;
-#if INST_MODE
+#if INST_MODE == MIMO_MODE_ENV
+  hipLaunchKernelGGL(kern, grid, dim3(T), dyn, st, p, out, aux);
+#elif INST_MODE
   hipLaunchKernelGGL(kern, grid, dim3(T), dyn, st, p, out);
 #else
   hipLaunchKernelGGL(kern, grid, dim3(T), dyn, st, p);
@@ -86,21 +94,21 @@ hipError_t go(dim3 grid, hipStream_t st, const TrialParams<Real>& p, hipFuncAttr
 
 template <int T, int NSLOT, bool AL>
 hipError_t by_channel(const InstanceKey& k, dim3 grid, hipStream_t st, const TrialParams<Real>& p, bool* found,
-                      hipFuncAttributes* a, double* m) {
+                      hipFuncAttributes* a, double* m, double x) {
   *found = true;
   switch (k.ch) {
     case CH_RAYLEIGH:
-      return k.csi ? go<T, NSLOT, AL, CH_RAYLEIGH, true>(grid, st, p, a, m)
-                   : go<T, NSLOT, AL, CH_RAYLEIGH, false>(grid, st, p, a, m);
+      return k.csi ? go<T, NSLOT, AL, CH_RAYLEIGH, true>(grid, st, p, a, m, x)
+                   : go<T, NSLOT, AL, CH_RAYLEIGH, false>(grid, st, p, a, m, x);
     case CH_LOS:
-      return k.csi ? go<T, NSLOT, AL, CH_LOS, true>(grid, st, p, a, m)
-                   : go<T, NSLOT, AL, CH_LOS, false>(grid, st, p, a, m);
+      return k.csi ? go<T, NSLOT, AL, CH_LOS, true>(grid, st, p, a, m, x)
+                   : go<T, NSLOT, AL, CH_LOS, false>(grid, st, p, a, m, x);
     case CH_TWOPATH:
-      return k.csi ? go<T, NSLOT, AL, CH_TWOPATH, true>(grid, st, p, a, m)
-                   : go<T, NSLOT, AL, CH_TWOPATH, false>(grid, st, p, a, m);
+      return k.csi ? go<T, NSLOT, AL, CH_TWOPATH, true>(grid, st, p, a, m, x)
+                   : go<T, NSLOT, AL, CH_TWOPATH, false>(grid, st, p, a, m, x);
     case CH_TABLE:
-      return k.csi ? go<T, NSLOT, AL, CH_TABLE, true>(grid, st, p, a, m)
-                   : go<T, NSLOT, AL, CH_TABLE, false>(grid, st, p, a, m);
+      return k.csi ? go<T, NSLOT, AL, CH_TABLE, true>(grid, st, p, a, m, x)
+                   : go<T, NSLOT, AL, CH_TABLE, false>(grid, st, p, a, m, x);
     default:
       *found = false;
       return hipSuccess;
@@ -109,34 +117,34 @@ hipError_t by_channel(const InstanceKey& k, dim3 grid, hipStream_t st, const Tri
 
 template <int T>
 hipError_t by_team(const InstanceKey& k, dim3 grid, hipStream_t st, const TrialParams<Real>& p, bool* found,
-                   hipFuncAttributes* a, double* m) {
+                   hipFuncAttributes* a, double* m, double x) {
   constexpr int P = kF / T;
   if (k.aligned) {
     if constexpr (8 < P) {
-      if (k.nslot == 8) return by_channel<T, 8, true>(k, grid, st, p, found, a, m);
+      if (k.nslot == 8) return by_channel<T, 8, true>(k, grid, st, p, found, a, m, x);
     }
     if constexpr (4 < P) {
-      if (k.nslot == 4) return by_channel<T, 4, true>(k, grid, st, p, found, a, m);
+      if (k.nslot == 4) return by_channel<T, 4, true>(k, grid, st, p, found, a, m, x);
     }
     return hipSuccess;
   }
   if (k.nslot != P) return hipSuccess;
-  return by_channel<T, P, false>(k, grid, st, p, found, a, m);
+  return by_channel<T, P, false>(k, grid, st, p, found, a, m, x);
 }
 
 }  // namespace
 
 template <>
 hipError_t launch_trial<kF, Real, INST_MODE>(const InstanceKey& k, dim3 grid, hipStream_t st, const TrialParams<Real>& p,
-                                             bool* found, hipFuncAttributes* attr, double* out) {
+                                             bool* found, hipFuncAttributes* attr, double* out, double aux) {
   *found = false;
   if (k.F != kF || k.f64 != kF64) return hipSuccess;
   if constexpr (kF64) {
-    if (k.T == team_size64(kF)) return by_team<team_size64(kF)>(k, grid, st, p, found, attr, out);
+    if (k.T == team_size64(kF)) return by_team<team_size64(kF)>(k, grid, st, p, found, attr, out, aux);
   } else {
-    if (k.T == team_size(kF)) return by_team<team_size(kF)>(k, grid, st, p, found, attr, out);
+    if (k.T == team_size(kF)) return by_team<team_size(kF)>(k, grid, st, p, found, attr, out, aux);
     if constexpr (alt_team_size(kF) != team_size(kF)) {
-      if (k.T == alt_team_size(kF)) return by_team<alt_team_size(kF)>(k, grid, st, p, found, attr, out);
+      if (k.T == alt_team_size(kF)) return by_team<alt_team_size(kF)>(k, grid, st, p, found, attr, out, aux);
     }
   }
   return hipSuccess;

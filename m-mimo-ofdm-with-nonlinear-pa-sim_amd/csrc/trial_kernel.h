@@ -44,11 +44,12 @@ enum ChanKind : int { CH_RAYLEIGH = 1, CH_LOS = 2, CH_TWOPATH = 3, CH_TABLE = 4 
 enum RxKind : int { RX_CNC = 1, RX_MCNC = 2 };
 
 // The run mode of the instances a translation unit builds (trial_inst.hip -DINST_MODE=<mode>): one
-// kernel per unit, named and shaped by the mode.  The three row modes are float64 only.
+// kernel per unit, named and shaped by the mode.  The four row modes are float64 only.
 #define MIMO_MODE_PLAIN 0  // trial_kernel: the counts alone
 #define MIMO_MODE_MEAS 1   // trial_kernel_meas
 #define MIMO_MODE_SPEC 2   // trial_kernel_spec
 #define MIMO_MODE_BEAM 3   // trial_kernel_beam
+#define MIMO_MODE_ENV 4    // trial_kernel_env
 #ifndef MIMO_INST_MODE
 #define MIMO_INST_MODE MIMO_MODE_PLAIN
 #endif
@@ -84,6 +85,29 @@ constexpr int kSpecFixed = 3;  // MIMO_SPEC_FIXED
 // band).  Register m of frequency thread tf is bin tf + T m before the inverse and after the
 // forward transform (the spectrum instances' statement).  Plain 16-byte stores, every cell
 // written once per launch; the buffer pointer is an extra argument of that kernel alone.
+
+// Envelope instances (MIMO_MODE_ENV): the same trial, the same
+// counts, and per trial a row of 2 kEnvBins + kEnvFixed doubles from the main array pass alone
+// (include/mimo_engine.h mimo_engine_envelope_points): the histograms of |x_a[n]|^2 and |y_a[n]|^2
+// over every antenna's F time samples -- d between the inverse transform and pa_block is x_a (the
+// precoder input carries 1 / sqrt(F), so the unnormalised inverse is the ortho one), d after it
+// y_a -- then Pin = sum |x|^2, Pout = sum |y|^2 and Re / Im of sum y conj(x).  Bins (env_bin):
+// eight linear sub-bins per octave read off the bits of pw scale.  Counters: uint32 in a per-team
+// LDS histogram, zeroed before the pass, one ds_add_u32 per sample and side, stored to the row as
+// doubles once after the pass (plain stores, no global atomics).  MIMO_ENV_SUBH (tuning.h) copies of
+// the histogram, one per lane residue, spread the lanes that meet in the few bins around the mean.
+// x is held across pa_block in a copy of d (4 P VGPRs; the instances up to F 2048 are therefore
+// built for 2 waves / SIMD, tuning.h MIMO_ENV_W64_2048: at the plain instances' 168 VGPRs the copy
+// spills and costs more than the resident team).  The row pointer and the bin scale are extra
+// arguments of that kernel alone.
+constexpr int kEnvBins = 128;   // MIMO_ENV_BINS
+constexpr int kEnvFixed = 4;    // MIMO_ENV_FIXED
+// bin of a sample power: clamp((bits(pw scale) >> 49) - 8088, 0, 127), 8088 = (1023 - 12) << 3
+// (pw scale >= 0: bits >> 49 is the high word >> 17; 0 lands in bin 0, +inf in bin 127)
+__device__ __forceinline__ int env_bin(double pw, double scale) {
+  const int b = (__double2hiint(pw * scale) >> 17) - 8088;
+  return b < 0 ? 0 : (b > kEnvBins - 1 ? kEnvBins - 1 : b);
+}
 
 constexpr int kMaxCsiAnt = 512;  // CSI-error runs: antennas (dynamic LDS per team, A doubles; engine.hip checks)
 constexpr uint32_t kFixedCsiTrial = 0xFFFFFFFFu;  // CSI stream counter of fixed-channel runs (oracle/sim.py draws)
@@ -854,6 +878,12 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
                                                                                                   double* beam_cells) {
   constexpr double* meas_rows = nullptr;
   constexpr double* spec_rows = nullptr;
+#elif MIMO_INST_MODE == MIMO_MODE_ENV
+__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel_env(TrialParams<R> p0,
+                                                                                                 double* env_rows,
+                                                                                                 double env_scale) {
+  constexpr double* meas_rows = nullptr;
+  constexpr double* spec_rows = nullptr;
 #else
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel(TrialParams<R> p0) {
   constexpr double* meas_rows = nullptr;
@@ -862,10 +892,15 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
 #if MIMO_INST_MODE != MIMO_MODE_BEAM
   constexpr double* beam_cells = nullptr;
 #endif
+#if MIMO_INST_MODE != MIMO_MODE_ENV
+  constexpr double* env_rows = nullptr;
+  constexpr double env_scale = 0.0;
+#endif
   using C = cx<R>;
   constexpr bool MEAS = MIMO_INST_MODE == MIMO_MODE_MEAS && sizeof(R) == 8;
   constexpr bool SPEC = MIMO_INST_MODE == MIMO_MODE_SPEC && sizeof(R) == 8;
   constexpr bool BEAM = MIMO_INST_MODE == MIMO_MODE_BEAM && sizeof(R) == 8;
+  constexpr bool ENV = MIMO_INST_MODE == MIMO_MODE_ENV && sizeof(R) == 8;
   // ---- which point and trial this block runs (uniform binary search over point_start)
   uint32_t pi = 0;
   if (p0.n_points > 1) {
@@ -1278,6 +1313,12 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
   R wsc[WSC ? NSLOT : 1];
   // spectrum instances: the thread's in-band sums over the main pass (|x|^2, Re / Im of y conj(x))
   R sp_ex = R(0), sp_cre = R(0), sp_cim = R(0);
+  // envelope instances: the team's histograms (cell (side, bin) of copy c at (side kEnvBins + bin)
+  // SUBH + c: the copies of a bin in neighbouring banks) and the thread's sums over the main pass
+  constexpr int SUBH = MIMO_ENV_SUBH;
+  static_assert(SUBH >= 1 && (SUBH & (SUBH - 1)) == 0 && SUBH <= 64, "a power of two of lane residues");
+  __shared__ uint32_t env_hist[ENV ? 2 * kEnvBins * SUBH : 1];
+  R en_pin = R(0), en_pout = R(0), en_cre = R(0), en_cim = R(0);
   auto array_pass = [&](bool main_pass, C (&acc)[NSLOT]) __attribute__((always_inline)) {
 #pragma unroll
     for (int s = 0; s < NSLOT; ++s) acc[s] = czero<R>();
@@ -1418,7 +1459,35 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
       if (!MIMO_ABL(p, ABL_FFT))
         FFT::template run<+1, 0, SL::zero_mask()>(d, lds, WAVEFFT ? p.tw_wave : p.tw, tfft, MIMO_ABL(p, ABL_XCHG), hfill_ifft,
                                                   tw1);
+      C xin[ENV ? P : 1];  // envelope instances: the PA input, held across pa_block
+      if constexpr (ENV) {
+        if (main_pass) {
+#pragma unroll
+          for (int m = 0; m < P; ++m) {
+            xin[m] = d[m];
+            const R pw = fmar(d[m].x, d[m].x, d[m].y * d[m].y);
+            en_pin += pw;
+#ifndef MIMO_DIAG_ENV_NOHIST  // cost breakdowns only: the sums and the held x without the histograms
+            atomicAdd(&env_hist[env_bin((double)pw, env_scale) * SUBH + (lane & (SUBH - 1))], 1u);
+#endif
+          }
+        }
+      }
       if (!MIMO_ABL(p, ABL_PA)) pa_block<COLD_OUT>(p.pa_kind, d, p.sat_tx, p.sqrt_sat_tx, p.inv_sat_tx, p.rapp_p, p.toi_tx);
+      if constexpr (ENV) {
+        if (main_pass) {
+#pragma unroll
+          for (int m = 0; m < P; ++m) {
+            const R pw = fmar(d[m].x, d[m].x, d[m].y * d[m].y);
+            en_pout += pw;
+#ifndef MIMO_DIAG_ENV_NOHIST
+            atomicAdd(&env_hist[(kEnvBins + env_bin((double)pw, env_scale)) * SUBH + (lane & (SUBH - 1))], 1u);
+#endif
+            en_cre = fmar(d[m].x, xin[m].x, fmar(d[m].y, xin[m].y, en_cre));
+            en_cim = fmar(d[m].y, xin[m].x, fmar(-d[m].x, xin[m].y, en_cim));
+          }
+        }
+      }
       // alpha_a (Bussgang gain of antenna a's PA from its precoding power, main pass only)
       auto alpha_of_vk = [&]() __attribute__((always_inline)) -> R {
         R vks;
@@ -1574,7 +1643,30 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
 #pragma unroll
     for (int s = 0; s < NSLOT; ++s) wsc[s] = inv_nrm[s] * inv_sqrt_f;
   }
+  if constexpr (ENV) {
+    for (int i = t; i < 2 * kEnvBins * SUBH; i += T) env_hist[i] = 0u;
+    __syncthreads();
+  }
   array_pass(true, r);
+  if constexpr (ENV) {
+    // the fixed sums in team_sum's order; the barrier puts every wave's ds_adds ahead of the reads
+    const R pin = team_sum<T>(en_pin, red), pout = team_sum<T>(en_pout, red);
+    const R cre = team_sum<T>(en_cre, red), cim = team_sum<T>(en_cim, red);
+    __syncthreads();
+    double* row = env_rows + (size_t)blockIdx.x * (size_t)(2 * kEnvBins + kEnvFixed);
+    for (int i = t; i < 2 * kEnvBins; i += T) {
+      uint32_t n = 0;
+#pragma unroll
+      for (int c = 0; c < SUBH; ++c) n += env_hist[i * SUBH + c];
+      row[i] = (double)n;
+    }
+    if (t0) {
+      row[2 * kEnvBins] = (double)pin;
+      row[2 * kEnvBins + 1] = (double)pout;
+      row[2 * kEnvBins + 2] = (double)cre;
+      row[2 * kEnvBins + 3] = (double)cim;
+    }
+  }
   if constexpr (SPEC) {
     // Ex = F sum |x|^2 (x carries 1 / sqrt(F)); Y conj(X) = (d / sqrt(F)) conj(x sqrt(F)) = d conj(x)
     const R ex = team_sum<T>(sp_ex, red), cre = team_sum<T>(sp_cre, red), cim = team_sum<T>(sp_cim, red);

@@ -36,21 +36,24 @@ struct InstanceKey {
 // attr != null: return the instance's attributes (static LDS ...) instead of launching it.
 // out: the kernel's extra argument -- the measure instances' per-trial rows [grid.x][kMeasFixed +
 // n_idx], the spectrum instances' [grid.x][F + kSpecFixed], the beam instances' cells
-// [2][grid.x][A][F] complex128 (Y sqrt(F), X / sqrt(F)); the plain instances ignore it.
+// [2][grid.x][A][F] complex128 (Y sqrt(F), X / sqrt(F)), the envelope instances' rows [grid.x][2 kEnvBins +
+// kEnvFixed]; the plain instances ignore it.  aux: the envelope instances' bin scale 1.0625 / ref_pow; the
+// others ignore it.
 template <int F, typename R, int MODE>
 hipError_t launch_trial(const InstanceKey& k, dim3 grid, hipStream_t st, const TrialParams<R>& p, bool* found,
-                        hipFuncAttributes* attr, double* out) = delete;
+                        hipFuncAttributes* attr, double* out, double aux) = delete;
 // the combinations that are built: float32 is plain only
 #define MIMO_DECLARE_LAUNCH_AS(FV, R, MODE)                                                                  \
   template <>                                                                                                \
   hipError_t launch_trial<FV, R, MODE>(const InstanceKey&, dim3, hipStream_t, const TrialParams<R>&, bool*, \
-                                       hipFuncAttributes*, double*);
+                                       hipFuncAttributes*, double*, double);
 #define MIMO_DECLARE_LAUNCH(FV)                           \
   MIMO_DECLARE_LAUNCH_AS(FV, float, MIMO_MODE_PLAIN)      \
   MIMO_DECLARE_LAUNCH_AS(FV, double, MIMO_MODE_PLAIN)     \
   MIMO_DECLARE_LAUNCH_AS(FV, double, MIMO_MODE_MEAS)      \
   MIMO_DECLARE_LAUNCH_AS(FV, double, MIMO_MODE_SPEC)      \
-  MIMO_DECLARE_LAUNCH_AS(FV, double, MIMO_MODE_BEAM)
+  MIMO_DECLARE_LAUNCH_AS(FV, double, MIMO_MODE_BEAM)      \
+  MIMO_DECLARE_LAUNCH_AS(FV, double, MIMO_MODE_ENV)
 MIMO_DECLARE_LAUNCH(128)
 MIMO_DECLARE_LAUNCH(256)
 MIMO_DECLARE_LAUNCH(512)

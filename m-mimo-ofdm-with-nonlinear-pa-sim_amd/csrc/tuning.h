@@ -130,3 +130,24 @@
 #ifndef MIMO_CT_PF
 #define MIMO_CT_PF 0
 #endif
+
+// ---- envelope instances (trial_kernel.h ENV; tools/envelope_bench.py, profiles/r12/envelope/)
+// fp64 F <= 2048: waves / SIMD the register allocation of the envelope instances targets.  They
+// hold the PA input x across pa_block (4 P VGPRs) next to what the plain instance holds.  At 3
+// (168 VGPRs, the plain instances' target) that copy spills -- scratch 144 -> 384 B / lane at
+// config 2 -- and the kernel takes 1.991 ms per 1,024 trials against the plain 0.711 (+180 %); at 2
+// (256 VGPRs, two 4-wave teams per CU instead of three) 0.844 ms (+20 %).  Measured at F 2048 only.
+#ifndef MIMO_ENV_W64_2048
+#define MIMO_ENV_W64_2048 2
+#endif
+// Copies of the team's LDS histogram, one per lane residue (lane mod SUBH), summed when the row is
+// stored.  The samples are near-Gaussian, so most of a wave's lanes meet in the few bins around
+// the mean and their ds_add_u32 to one cell queue up; SUBH copies of a cell in neighbouring banks
+// split that queue.  1: the plain form, 1 KiB of LDS per team; 4: 4 KiB.  Config 2 at 2 waves / SIMD:
+// 0.835 ms per 1,024 trials with 4 copies against 0.844 with 1 (-1.1 %, the spread between rounds
+// is 1.3 %), both histograms together cost 0.064 ms of it; the paper geometry (F 4096) +10 % with
+// 4 copies (82,544 B of LDS: one team per CU instead of two), +0.8 % with 2; at F 8192 4 copies
+// do not fit the CU's LDS.  So 1.
+#ifndef MIMO_ENV_SUBH
+#define MIMO_ENV_SUBH 1
+#endif

@@ -624,6 +624,44 @@ class Link:
                                                         lambda eng, *args: eng.beam_points(*args, [0], probes))
         return [_engine.BeamStats(beam[i], int(n[i])) for i in range(len(n))]
 
+    # ------------------------------------------------------------------ envelope mode
+    def nominal_sample_power(self, point_params: dict = None) -> float:
+        """The array's nominal mean sample power at a PA input, the power ``sat_pow`` is formed from:
+        ``sat_pow / 10^(ibo_db / 10)`` as ``AntennaArray.update_distortion`` sets it; for a TOI or
+        no-PA point the modem's ``avg_sample_power`` times the precoding gain, the same way."""
+        pp = self.point_params() if point_params is None else point_params
+        if pp["pa_kind"] in ("softlim", "rapp"):
+            return float(pp["sat_pow"] / 10 ** (pp["ibo_db"] / 10))
+        n_sc = self.my_mod.n_sub_carr
+        tot = 0.0
+        for t in self.my_array.array_elements:
+            p = t.modem.precoding_mat
+            tot += float(n_sc) if p is None else float(np.vdot(p, p).real)
+        return float(self.my_mod.avg_sample_power * tot / (len(self.my_array.array_elements) * n_sc))
+
+    def envelope(self, reroll_chan: bool, seed_arr, n_trials: int, ref_pow: float = None):
+        """Envelope of the current grid point over trials [0, n_trials) of ``simulate``'s trial
+        sequence: an ``_engine.EnvelopeStats`` -- the distribution (CCDF) of the instantaneous power
+        at every antenna's PA input and output in dB over ``ref_pow``, the efficiency and the
+        Bussgang gain.  ``ref_pow=None``: ``nominal_sample_power()``, so that 0 dB is the mean and a
+        limiter's clip level reads as the IBO.  A fixed number of trials, no stopping rule."""
+        return self.envelope_points(reroll_chan, [seed_arr], [self.point_params()], n_trials, ref_pow)[0]
+
+    def envelope_points(self, reroll_chan: bool, seed_arrs, point_params, n_trials, ref_pow: float = None) -> list:
+        """``envelope`` for many grid points of this system in one engine call
+        (mimo_engine_envelope_points), all over the bins of one ``ref_pow`` (``None``: the first
+        point's ``nominal_sample_power``; the points of an IBO sweep share it up to rounding);
+        ``point_params`` as for ``simulate_points``, ``n_trials`` one number or one per point.  The
+        envelope is taken before the channel and the noise, so a point whose SNR was never set runs
+        at 0 dB.  -> a list of ``_engine.EnvelopeStats``.  Single GPU."""
+        if ref_pow is None:
+            ref_pow = self.nominal_sample_power(point_params[0]) if len(point_params) else 1.0
+        ref_pow = float(ref_pow)
+        (_, _, env, _, _), n = self._fixed_trials_call(reroll_chan, seed_arrs, point_params, n_trials,
+                                                       lambda eng, *args: eng.envelope_points(*args, [0], ref_pow))
+        m = self.my_mod
+        return [_engine.EnvelopeStats(env[i], self.n_ant_val, m.n_fft, int(n[i]), ref_pow) for i in range(len(n))]
+
     def update_distortion(self, ibo_val_db: float) -> None:
         """(mp_model.py:230-241)"""
         self.my_array.update_distortion(ibo_db=ibo_val_db, avg_sample_pow=self.my_mod.avg_sample_power)

@@ -280,6 +280,33 @@ def psd_vs_ibo_rows(stats):
     return list(np.concatenate([stats[0].freq_index[:, None].astype(np.float64), rel], axis=1))
 
 
+def envelope_vs_ibo(link, ibo_arr, n_trials, seed=2137, reroll_chan=True, ref_pow=None):
+    """Envelope of the array's PA inputs and outputs for every IBO of ``ibo_arr``: ``n_trials``
+    trials per point, all points in one ``Link.envelope_points`` call over the bins of one
+    ``ref_pow`` (``None``: the array's nominal mean sample power; one GPU; point i is seeded by
+    ``point_seed(seed, i)``).  -> a list of ``_engine.EnvelopeStats``."""
+    params, seeds = [], []
+    for i, ibo in enumerate(np.asarray(ibo_arr, dtype=np.float64)):
+        link.update_distortion(ibo_val_db=float(ibo))
+        params.append(dict(link.point_params()))
+        seeds.append(point_seed(seed, i))
+    return link.envelope_points(reroll_chan, seeds, params, n_trials, ref_pow)
+
+
+def ccdf_vs_ibo_rows(ibo_arr, stats):
+    """CSV rows of the envelope sweep.  Three header rows, each led by NaN in the edge column and
+    then two columns per IBO: the IBO [dB] twice; the efficiency Pout / Pin twice; |Bussgang gain|
+    twice.  Then one row per bin edge: the edge [dB over ref_pow], and per IBO the CCDF of the
+    instantaneous power at the PA inputs and at the PA outputs, P(u >= edge)."""
+    ibo = np.asarray(ibo_arr, dtype=np.float64).reshape(-1)
+    head = [np.concatenate([[np.nan], np.repeat(v, 2)])
+            for v in (ibo, [st.efficiency for st in stats], [abs(st.gain) for st in stats])]
+    cols = [stats[0].edges_db]
+    for st in stats:
+        cols += [st.ccdf_in, st.ccdf_out]
+    return head + list(np.stack(cols, axis=1))
+
+
 def beam_vs_angle(link, angles_deg, ibo_arr, n_trials, seed=2137, reroll_chan=True, radius=None, z=None):
     """Beampattern of the array over ``angles_deg`` for every IBO of ``ibo_arr``: probes on the
     horizontal circle around the origin through the user (``radius``, ``z``: the link's nominal
@@ -383,14 +410,18 @@ def _build_link(args, device):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--grid", choices=["ber_vs_ebn0", "fixed_ber", "sdr_vs_ibo", "psd_vs_ibo", "beam_vs_angle"],
+    ap.add_argument("--grid", choices=["ber_vs_ebn0", "fixed_ber", "sdr_vs_ibo", "psd_vs_ibo", "beam_vs_angle",
+                                       "ccdf_vs_ibo"],
                     default="fixed_ber",
                     help="sdr_vs_ibo: measured in-band SDR and per-iteration signal-to-error ratio per IBO "
                          "(--n-trials trials per point at the first --ebn0 value; one GPU).  psd_vs_ibo: the "
                          "array's radiated PSD per FFT bin, out-of-band share, Bussgang gain and efficiency per "
                          "IBO (--n-trials trials per point; one GPU).  beam_vs_angle: signal, uncorrelated "
                          "distortion and out-of-band power radiated towards --angles on the circle through the "
-                         "user, per IBO (--n-trials trials per point; one GPU)")
+                         "user, per IBO (--n-trials trials per point; one GPU).  ccdf_vs_ibo: the CCDF of the "
+                         "instantaneous power at the PA inputs and outputs over the array's nominal mean "
+                         "power, with efficiency and Bussgang gain, per IBO (--n-trials trials per point; "
+                         "one GPU)")
     ap.add_argument("--angles", type=str, default="0:180.1:1", help="beam_vs_angle: start:stop:step [deg]")
     ap.add_argument("--n-ant", type=int, default=64)
     ap.add_argument("--n-sc", type=int, default=2048)
@@ -410,7 +441,7 @@ def main():
     ap.add_argument("--n-err-min", type=int, default=int(1e5))
     ap.add_argument("--seed", type=int, default=2137)
     ap.add_argument("--n-trials", type=int, default=4096,
-                    help="sdr_vs_ibo, psd_vs_ibo, beam_vs_angle: trials per IBO point")
+                    help="sdr_vs_ibo, psd_vs_ibo, beam_vs_angle, ccdf_vs_ibo: trials per IBO point")
     ap.add_argument("--out", type=str, default="figs/csv_results")
     ap.add_argument("--split", choices=["points", "trials", "auto"], default="auto",
                     help="ranks deal whole points by cost (one all-reduce at the end), or share every point's "
@@ -470,6 +501,18 @@ def main():
             ibo_arr[1] - ibo_arr[0] if len(ibo_arr) > 1 else 0.0, len(angles), args.n_trials)
         save_to_csv(beam_vs_angle_rows(angles, stats), name, directory=args.out)
         print(f"beam sweep done: {len(ibo_arr)} IBO points x {len(angles)} angles x {args.n_trials} trials in "
+              f"{time.perf_counter() - t0:.1f} s -> {args.out}")
+        return
+    if args.grid == "ccdf_vs_ibo":
+        if world > 1:
+            raise SystemExit("--grid ccdf_vs_ibo runs on one GPU")
+        t0 = time.perf_counter()
+        stats = envelope_vs_ibo(link, ibo_arr, args.n_trials, args.seed)
+        name = "ccdf_vs_ibo_%s_%s_nant%d_nfft%d_nsc%d_ibo_min%d_max%d_step%1.2f_ntrials%d" % (
+            args.pa, args.channel, args.n_ant, args.n_fft, args.n_sc, min(ibo_arr), max(ibo_arr),
+            ibo_arr[1] - ibo_arr[0] if len(ibo_arr) > 1 else 0.0, args.n_trials)
+        save_to_csv(ccdf_vs_ibo_rows(ibo_arr, stats), name, directory=args.out)
+        print(f"ccdf sweep done: {len(ibo_arr)} IBO points x {args.n_trials} trials in "
               f"{time.perf_counter() - t0:.1f} s -> {args.out}")
         return
     t0 = time.perf_counter()
