@@ -109,15 +109,19 @@ __device__ __forceinline__ double bm_c<double>(double scale2) {
   return -scale2;
 }
 
+// DEG: the fp64 form's series degree (real.h ln_unit; 6 unless the caller names another); the
+// fp32 form is one instruction and has none.
+template <int DEG = 6>
 __device__ __forceinline__ float bm_log(uint32_t w0, float) {
   return __builtin_amdgcn_logf(fmaf((float)w0, 2.3283064365386963e-10f, 1.1641532182693481e-10f));
 }
 // fp64: LDS-table ln (real.h ln_unit; the trial kernel loads lut64 first).  The series
 // forms (ln_pos, sincos_rev) measured 1.4-3.9 % slower.
+template <int DEG = 6>
 __device__ __forceinline__ double bm_log(uint32_t w0, double) {
   // ln of u1 = (w0 + 0.5) 2^-32 from the bits of w0 + 0.5 (exact) with the 2^-32 taken into
   // ln_unit's exponent: no scaling instruction
-  return ln_unit<-32>((double)w0 + 0.5);
+  return ln_unit<-32, DEG>((double)w0 + 0.5);
 }
 
 __device__ __forceinline__ float2 box_muller(uint32_t w0, uint32_t w1, float c = kNegLn2) {

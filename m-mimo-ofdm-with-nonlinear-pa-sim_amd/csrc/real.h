@@ -105,14 +105,22 @@ __device__ __forceinline__ uint32_t lut_idx(uint32_t i) { return i; }
 // The series run in the integer residual f itself (coefficients scaled by powers of
 // h = 2 pi 2^-32): sin = f (h - h^3 f^2 / 6 + ...), cos = 1 - h^2 f^2 / 2 + ... -- one
 // multiply fewer than forming phi = h f first.
+// DEG: the sine's last term, 7 or 5.  The phi^7 term is below (pi/256)^7 / 5040 = 8e-18 before the
+// angle sum with an O(1) table entry, so DEG 5 shows only at table index 0, by at most 6 units of
+// the sine's last place there, and stays within 2 of the larger of |sin| and |cos|
+// (tests/test_draw_series_cpu.py); the cosine's phi^6 term is 4.7e-15 and stays.  Callers that do
+// not name a degree get the full series (tuning.h MIMO_BM_SIN_DEG).
+template <int DEG = 7>
 __device__ __forceinline__ void sincos_lut(uint32_t w, double& sn, double& cs) {
+  static_assert(DEG == 7 || DEG == 5, "sine series to phi^7 or phi^5");
   const uint32_t i = (w + 0x800000u) >> 24;  // wraps to 0 near a full revolution
   // w - i 2^24 = the low 24 bits of w sign-extended (one v_bfe_i32), in [-2^23, 2^23)
   const double f = (double)(((int)(w << 8)) >> 8);
   constexpr double h = 1.4629180792671596e-09;    // 2 pi 2^-32
   constexpr double h2 = h * h;
   const double z = f * f;                         // exact (< 2^46)
-  double ps = fma(z, -(h2 * h2 * h2 * h) / 5040, (h2 * h2 * h) / 120);
+  double ps = (h2 * h2 * h) / 120;
+  if constexpr (DEG == 7) ps = fma(z, -(h2 * h2 * h2 * h) / 5040, ps);
   ps = fma(ps, z, -(h2 * h) / 6);
   ps = fma(ps, z, h);
   const double s = f * ps;
@@ -149,7 +157,28 @@ __device__ __forceinline__ void sincos_rev_lut(double r, double& sn, double& cs)
 // log1p(t) to t^6 (truncation < 2^-60 relative).  <= 1.3 ulp (1.24 measured on the device,
 // tests/test_gpu_probe_math.py).
 // ESC: ln(x 2^ESC) -- the scale enters the exponent only (Box-Muller: x = w0 + 0.5, ESC = -32).
-template <int ESC = 0>
+// DEG: the last power of log1p's series, 6, 5 or 4 (|t| < 1.11 2^-10: the t^6 and t^5 terms are
+// each below 2e-16 absolute).  To t^5 a single log stays within 1.7 units of the last place
+// (1.0 at t^6); to t^4 it is off by up to 1,600 near u -> 1 and serves weighted sums of logs of
+// size ~64 only (tuning.h MIMO_BM_LN_DEG, MIMO_P1_LN_DEG; tests/test_draw_series_cpu.py).  Callers
+// that do not name a degree get the full series.
+template <int DEG>
+__device__ __forceinline__ double log1p_series(double t) {
+  static_assert(DEG >= 4 && DEG <= 6, "log1p series to t^4, t^5 or t^6");
+  if constexpr (DEG == 4) {
+    // t + t^2 ((-1/2 + t/3) - t^2 / 4): every FMA has one constant that is no inline operand (a
+    // Horner step between two such constants costs a v_mov_b64 of one of them per draw here)
+    const double u = t * t;
+    return fma(u, fma(u, -0.25, fma(t, 1.0 / 3, -0.5)), t);
+  }
+  double q = DEG == 6 ? -1.0 / 6 : 1.0 / 5;
+  if constexpr (DEG >= 6) q = fma(q, t, 1.0 / 5);
+  if constexpr (DEG >= 5) q = fma(q, t, -1.0 / 4);
+  q = fma(q, t, 1.0 / 3);
+  q = fma(q, t, -0.5);
+  return fma(t * t, q, t);
+}
+template <int ESC = 0, int DEG = 6>
 __device__ __forceinline__ double ln_unit(double x) {
   // m and e by v_frexp_mant / v_frexp_exp (x normal, > 0): two instructions instead of the
   // bit surgery (shift, add; and, or and a register copy); the bucket from x's top mantissa bits
@@ -158,12 +187,7 @@ __device__ __forceinline__ double ln_unit(double x) {
   const uint32_t hi = (uint32_t)__double2hiint(x);
   const double2 cl = lut64[lut_idx((hi >> 11) & 511u)];
   const double t = fma(m, cl.x, -1.0);
-  double q = -1.0 / 6;
-  q = fma(q, t, 1.0 / 5);
-  q = fma(q, t, -1.0 / 4);
-  q = fma(q, t, 1.0 / 3);
-  q = fma(q, t, -0.5);
-  const double p = fma(t * t, q, t);
+  const double p = log1p_series<DEG>(t);
   constexpr double kLn2Hi = 6.93147180369123816490e-01;
   constexpr double kLn2Lo = 1.90821492927058770002e-10;
   const double de = (double)e;
@@ -174,19 +198,14 @@ __device__ __forceinline__ double ln_unit(double x) {
 // (the trial kernel's pass 1): sum_a c_a ln u_a = sum c_a tab_a + sum c_a poly_a +
 // ln 2 sum c_a de_a, three FMAs per term and ln_sum() once, instead of ln_unit's two FMAs and
 // an add and then the weighted add.
-template <int ESC = 0>
+template <int ESC = 0, int DEG = 6>
 __device__ __forceinline__ void ln_unit_parts(double x, double& tab, double& poly, double& de) {
   const double m = __builtin_amdgcn_frexp_mant(x);
   const int e = __builtin_amdgcn_frexp_exp(x) + ESC;
   const uint32_t hi = (uint32_t)__double2hiint(x);
   const double2 cl = lut64[lut_idx((hi >> 11) & 511u)];
   const double t = fma(m, cl.x, -1.0);
-  double q = -1.0 / 6;
-  q = fma(q, t, 1.0 / 5);
-  q = fma(q, t, -1.0 / 4);
-  q = fma(q, t, 1.0 / 3);
-  q = fma(q, t, -0.5);
-  poly = fma(t * t, q, t);
+  poly = log1p_series<DEG>(t);
   tab = cl.y;
   de = (double)e;
 }

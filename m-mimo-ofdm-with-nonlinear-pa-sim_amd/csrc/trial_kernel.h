@@ -618,7 +618,8 @@ struct Channel {
   // SWAP = false: no pair swap, and q0 is the first call's counter for j = 0, formed by the caller
   // once per trial (S/2 - 1 for thread 0, else S/4 - 1 + t): thread 0's sums of slots 0 and Q
   // then sit in each other's place, which the caller puts right once after the loop.
-  template <bool SUMS3, bool SWAP, class PP>
+  // LN_DEG: the degree of the logs' series (real.h ln_unit; tuning.h MIMO_P1_LN_DEG).
+  template <bool SUMS3, bool SWAP, int LN_DEG, class PP>
   static __device__ __forceinline__ void power_acc(const PP& p, Key key, uint32_t trial, int a, int t, uint32_t q0,
                                                    R (&acc)[SUMS3 ? 3 : 1][NSLOT]) {
     static_assert(ALIGNED && sizeof(R) == 8, "aligned fp64 instances");
@@ -631,12 +632,12 @@ struct Channel {
     auto add = [&](int s, uint32_t w0) __attribute__((always_inline)) {
       if constexpr (SUMS3) {
         R tab, poly, de;
-        ln_unit_parts<-32>((double)w0 + 0.5, tab, poly, de);
+        ln_unit_parts<-32, LN_DEG>((double)w0 + 0.5, tab, poly, de);
         acc[0][s] = fmar(c, tab, acc[0][s]);
         acc[1][s] = fmar(c, poly, acc[1][s]);
         acc[2][s] = fmar(c, de, acc[2][s]);
       } else {
-        acc[0][s] += c * bm_log(w0, R(0));
+        acc[0][s] += c * bm_log<LN_DEG>(w0, R(0));
       }
     };
 #pragma unroll
@@ -678,6 +679,9 @@ struct Channel {
 
   // normals() with a per-slot scale folded into the Box-Muller radius: z = (rho w_s) e^{j phi}
   // and rw = rho w_s (aligned instances) -- one multiply per draw instead of two.
+  // LN_DEG, SIN_DEG: the degrees of the draws' series (real.h ln_unit, sincos_lut; tuning.h
+  // MIMO_BM_LN_DEG, MIMO_BM_SIN_DEG).
+  template <int LN_DEG = 6, int SIN_DEG = 7>
   static __device__ __forceinline__ void normals_w(Key key, uint32_t trial, uint32_t stream, uint32_t aux, int t, int S,
                                                    R c, const R (&w)[NSLOT], C (&z)[NSLOT], R (&rw)[NSLOT]) {
     static_assert(ALIGNED, "aligned slot map");
@@ -685,9 +689,9 @@ struct Channel {
     const bool t0 = (t == 0);
     const int qp = (S >> 2) - 1 + t;
     auto draw = [&](int s, uint32_t w0, uint32_t w1) __attribute__((always_inline)) {
-      rw[s] = sqrt_n1(c * bm_log(w0, R(0))) * w[s];
+      rw[s] = sqrt_n1(c * bm_log<LN_DEG>(w0, R(0))) * w[s];
       R sn, cs;
-      sincos_lut(w1, sn, cs);
+      sincos_lut<SIN_DEG>(w1, sn, cs);
       z[s] = mkc(rw[s] * cs, rw[s] * sn);
     };
 #pragma unroll
@@ -955,13 +959,24 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
   // VK_LDS (tuning.h; fp64 wave-split instances without CSI): the waves hand their vk partials
   // over per thread, one ds_write_b64 each in place of the DPP tree, and the alpha wave of the
   // antenna adds them per lane to its own (kept in registers) and runs the one tree.  W - 1
-  // regions of 64 partials, rotated with the alpha wave: wave w writes region (w - a - 1) mod W.
+  // regions of 64 partials.  With a fixed alpha wave k (ALPHA_WAVE below) wave w's region is a
+  // compile-time function of w, w - (w > k), and the alpha wave adds the W partials in wave order
+  // 0, 1, ..., its own in its place, so alpha does not depend on the antenna's index.  With the
+  // alpha wave rotating (a mod W) the regions rotate with it: wave w writes region
+  // (w - a - 1) mod W.
   // (1.5 KiB at T 256: the F 2048 instance's LDS 51,824 -> 53,296 B, and three teams per CU are
   // admitted up to 54,613 B; the alpha wave needs no store.)  One buffer, as vk_part with ALPHA1:
   // written before the inverse transform's barrier, read by the alpha wave between that barrier
-  // and the forward transform's, which the next antenna's writes follow.
+  // and the forward transform's, which the next antenna's writes follow.  alpha_s likewise:
+  // written before the forward transform's barrier, read at the combine after it, and rewritten
+  // after the next antenna's inverse barrier.  Both orders rest on the two barriers alone, not on
+  // which wave forms alpha.
   constexpr bool VK_LDS = MIMO_VK_LDS != 0 && ALPHA1 && sizeof(R) == 8 && wave_fft_used(F, T, true) && !CSI && T > 64;
   __shared__ R vk_thr[VK_LDS ? (T / 64 - 1) * 64 : 1];
+  // The wave that forms alpha (tuning.h MIMO_ALPHA_WAVE): fixed in the fp64 wave-split instances
+  // without CSI, whose wave 0 skips the inter-step twiddles; -1: wave a mod W of antenna a, as
+  // every other instance has it.
+  constexpr int ALPHA_WAVE = (MIMO_ALPHA_WAVE >= 0 && ALPHA1 && WAVEFFT && !CSI) ? (MIMO_ALPHA_WAVE & (W - 1)) : -1;
   // per-antenna mean |H|^2 (CSI model): dynamic LDS of A doubles (the launch sizes it), not
   // a static kMaxCsiAnt table -- the static 4 KiB cost F 4096 its second team per CU and F
   // 2048 its stage-2 twiddle rows (and with them the cot-tan FFT stages)
@@ -1087,7 +1102,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
     const int tl = P1_HOIST ? tl_p1 : opaque(tf);
     if constexpr (P1_ACC) {
       if (!MIMO_ABL(p, ABL_RNG)) {
-        CHN::template power_acc<P1_SUMS3, !P1_HOIST>(p, key, ch_trial, a, tl, q0_p1, p1_acc);
+        CHN::template power_acc<P1_SUMS3, !P1_HOIST, MIMO_P1_LN_DEG>(p, key, ch_trial, a, tl, q0_p1, p1_acc);
         continue;
       }
     }
@@ -1310,6 +1325,10 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
   // ... and for the Rayleigh channel the weight is folded into the Box-Muller radius
   // (CHN::normals_w): one multiply per draw instead of three, |h w|^2 from the radius
   constexpr bool WSC_RAY = MIMO_WSC_RAY != 0 && WSC && CH == CH_RAYLEIGH && ALIGNED;  // (fp64: no pipelined draws)
+  // the draws' series cut to what their use needs in the wave-split instances only (tuning.h);
+  // the team-FFT sizes keep the full series
+  constexpr int BM_LN_DEG = WAVEFFT ? MIMO_BM_LN_DEG : 6;
+  constexpr int BM_SIN_DEG = WAVEFFT ? MIMO_BM_SIN_DEG : 7;
   R wsc[WSC ? NSLOT : 1];
   // spectrum instances: the thread's in-band sums over the main pass (|x|^2, Re / Im of y conj(x))
   R sp_ex = R(0), sp_cre = R(0), sp_cim = R(0);
@@ -1353,7 +1372,8 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
           }
         } else {
           const R sa = p.ant_rel[a];
-          CHN::normals_w(key, ch_trial, ST_CHAN, (uint32_t)a, tl, S, bm_c<R>(sa * sa), wsc, h, rw);
+          CHN::template normals_w<BM_LN_DEG, BM_SIN_DEG>(key, ch_trial, ST_CHAN, (uint32_t)a, tl, S, bm_c<R>(sa * sa), wsc,
+                                                         h, rw);
         }
       } else {
         CHN::template gen<FREL>(p, key, ch_trial, a, tl, rx, h);
@@ -1436,8 +1456,13 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
       }
       if (main_pass) {
         if constexpr (VK_LDS) {
-          const int aw = a & (W - 1);
-          if (wid != aw) vk_thr[((wid - aw - 1) & (W - 1)) * 64 + lane] = vk;  // read after the IFFT's first barrier
+          // (read after the IFFT's first barrier)
+          if constexpr (ALPHA_WAVE >= 0) {
+            if (wid != ALPHA_WAVE) vk_thr[(wid - (wid > ALPHA_WAVE ? 1 : 0)) * 64 + lane] = vk;
+          } else {
+            const int aw = a & (W - 1);
+            if (wid != aw) vk_thr[((wid - aw - 1) & (W - 1)) * 64 + lane] = vk;
+          }
         } else {
           vk = wave_sum_lane63(vk);
           if (lane == 63) vk_part[vkb][wid] = vk;  // read after the IFFT's first barrier
@@ -1494,9 +1519,16 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
         if constexpr (VK_LDS) {
           // the alpha wave: its own partials and the other waves', region by region, then the
           // one tree; lane 63's sum to every lane, so that the branches below stay uniform
-          vks = vk;
+          if constexpr (ALPHA_WAVE >= 0) {  // in wave order, the alpha wave's own in its place
+            vks = ALPHA_WAVE == 0 ? vk : vk_thr[lane];
 #pragma unroll
-          for (int i = 0; i < W - 1; ++i) vks += vk_thr[i * 64 + lane];
+            for (int i = 1; i < W; ++i)
+              vks += i == ALPHA_WAVE ? vk : vk_thr[(i - (i > ALPHA_WAVE ? 1 : 0)) * 64 + lane];
+          } else {
+            vks = vk;
+#pragma unroll
+            for (int i = 0; i < W - 1; ++i) vks += vk_thr[i * 64 + lane];
+          }
           const uint64_t u = __builtin_bit_cast(uint64_t, (double)wave_sum_lane63(vks));
           const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, 63);
           const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), 63);
@@ -1534,14 +1566,14 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
           else return alpha_of_gamma2(g2);
         }
       };
-      // ALPHA1: one wave per antenna (a mod W) forms it from the vk partials (visible since the
-      // IFFT's first barrier) and hands it over in LDS; the forward FFT's cross-wave barrier
-      // orders the hand-off (alpha_s double-buffered like vk_part).  The other waves skip the
-      // partial sum and the 18-FMA polynomial.
+      // ALPHA1: one wave per antenna (ALPHA_WAVE, else a mod W) forms it from the vk partials
+      // (visible since the IFFT's first barrier) and hands it over in LDS; the forward FFT's
+      // cross-wave barrier orders the hand-off (alpha_s double-buffered like vk_part).  The other
+      // waves skip the partial sum and the 18-FMA polynomial.
       if constexpr (ALPHA1) {
         // (ablation builds without the transforms' barriers: order the vk_part hand-off)
         if (MIMO_ABL(p, ABL_FFT) || MIMO_ABL(p, ABL_XCHG)) __syncthreads();
-        if (main_pass && wid == (a & (W - 1))) {
+        if (main_pass && wid == (ALPHA_WAVE >= 0 ? ALPHA_WAVE : (a & (W - 1)))) {
           const R al = alpha_of_vk();
           if (lane == 0) alpha_s[vkb] = al;
         }

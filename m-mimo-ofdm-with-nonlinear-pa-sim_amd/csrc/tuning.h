@@ -61,6 +61,44 @@
 #define MIMO_VK_LDS 1
 #endif
 
+// ---- the wave that forms alpha in the fp64 wave-split instances without CSI (trial_kernel.h
+// ALPHA_WAVE).  -1: wave a mod W of antenna a, so the ~47 VALU of the partial sum and the 18-FMA
+// polynomial rotate over the team.  k >= 0: wave k mod W for every antenna.  Wave 0 of a team is
+// the one that skips the inter-step twiddle multiply of wave_fft.h run_second (50 VALU per
+// antenna fewer than waves 1..3), so 0 puts alpha on the lightest wave and 1 is the control that
+// puts it on a full one.  Config 2, 100 interleaved rounds, A/A spread 0.03 ms
+// (profiles/r17/balance/ab_switches.json): 0 -0.16 ms (-0.35 %), 1 +0.06 ms against -1; static
+// VALU of the slowest wave per antenna 1,051 -> 999, SQ_WAIT_ANY 0.159 -> 0.149 of wave cycles
+// with the series below.  The CSI instances (no VK_LDS) keep a mod W.
+#ifndef MIMO_ALPHA_WAVE
+#define MIMO_ALPHA_WAVE 0
+#endif
+
+// ---- the series of the Rayleigh channel draws in the fp64 wave-split instances (real.h
+// ln_unit / sincos_lut DEG; every other caller -- noise, CSI, the team-FFT sizes, the probe --
+// keeps the full series).  Bounds: tests/test_draw_series_cpu.py.
+// P1_LN_DEG (6 | 4): log1p's last power in pass 1's weighted log sum (Channel::power_acc).  The
+// t^5 and t^6 terms are below 2e-16 each where the sum of ~64 has a spacing of 1.4e-14: against
+// the long-double sum 4.14 units of the last place at most with either degree.  -8 VALU per
+// antenna-wave.
+// BM_LN_DEG (6 | 5): the same in the array pass's radius (Channel::normals_w), under sqrt_n1's
+// own 2^-47.8: per draw 1.69 units of the last place at most to t^5, 1.00 to t^6 (t^4: 1,617, so
+// not there).  -4 VALU.
+// BM_SIN_DEG (7 | 5): the sine's last term in normals_w's sincos_lut.  -4 VALU.
+// The same run, each alone against all off: P1_LN_DEG 4 -0.30 ms (-0.7 %), BM_LN_DEG 5 -0.16 ms
+// (-0.4 %), BM_SIN_DEG 5 -0.19 ms (-0.4 %); all four switches -0.77 ms (-1.7 %, 44.97 -> 44.19 ms),
+// SQ_INSTS_VALU 1,175.3 -> 1,154.3 per antenna-wave, error totals and the bench's outputs equal
+// (profiles/r17/balance/).
+#ifndef MIMO_P1_LN_DEG
+#define MIMO_P1_LN_DEG 4
+#endif
+#ifndef MIMO_BM_LN_DEG
+#define MIMO_BM_LN_DEG 5
+#endif
+#ifndef MIMO_BM_SIN_DEG
+#define MIMO_BM_SIN_DEG 5
+#endif
+
 // ---- Philox rounds whose words are uniform across the team on the SALU (philox.h kUni)
 // Always in the fp64 wave-split instances (F <= 2048).  F 4096: with CSI only (-2.4 % on the
 // paper-CSI line, +1.1 % without CSI, profiles/r06/k4096/).  F 8192: with the folded weight
