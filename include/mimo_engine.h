@@ -16,12 +16,15 @@
  *                                  the array radiates towards a list of probe positions (beampattern)
  *     mimo_engine_envelope_points  the same trials with the distribution of the instantaneous power at
  *                                  every antenna's PA input and output (CCDF / PAPR, compression)
+ *     mimo_engine_soft_points      the same trials with the histogram of the demapper's bit reliabilities
+ *                                  per counter index (BICM GMI / achievable rate per CNC / MCNC iteration)
  *     mimo_engine_run_points    <- the drivers' grid loops over (IBO, Eb/N0), one launch
  *                                  for many points   main_mp_miso_cnc_constant_ber_req_ebn0_vs_ibo.py:100-215
  *   fine seams (float64 stage kernels, caller-owned host arrays)
  *     mimo_qam_map              <- modulation.modulate                 modulation.py:13-25
  *     mimo_qam_slice            <- demodulate / symbol_detection       modulation.py:63-88,138-146
  *     mimo_qam_llr              <- soft_decoding                       modulation.py:29-59
+ *     mimo_qam_softbits            the soft mode's max-log soft bit lambda (no reference entry point)
  *     mimo_ofdm_tx / _rx        <- _tx_ofdm_symbol / _rx_ofdm_symbol   modulation.py:248-293
  *     mimo_fft                  <- utilities.to_freq/time_domain       utilities.py:311-339
  *     mimo_pa                   <- SoftLimiter/Rapp/ThirdOrderNonLin.process  distortion.py
@@ -298,6 +301,45 @@ int32_t mimo_engine_envelope_points(mimo_engine* e, int32_t n_points, const mimo
                                     const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters,
                                     int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
                                     uint32_t* per_trial, double ref_pow, double* env_out, double* per_trial_env);
+/* Soft mode (float64 engines): the trials, arguments, launch splitting and point rules of
+ * mimo_engine_run_points and the same counts, plus per point and per counter index the histogram of
+ * the demapper's bit reliabilities, from which the bit-wise mutual information of a coded link (the
+ * BICM generalised mutual information, GMI) follows after every recorded CNC / MCNC iteration.
+ *  Lattice and labels: the constellation in its own units (mimo_qam_map): levels are the odd integers
+ *   -(L - 1) ... L - 1, L = sqrt(constel_size), hb = log2 L; a label is (gray(i_I) << hb) | gray(i_Q).
+ *  Max-log soft bit: for a real coordinate x and Gray bit j of its axis, d0 = min |x - a| over the
+ *   levels a whose Gray bit j is 0, d1 the same over those whose bit is 1, and
+ *     lambda_j(x) = (d0 - d1) * (d0 + d1) * 0.25,
+ *   each one IEEE double operation, no fused multiply-add anywhere.  Ties between levels do not
+ *   change d0 or d1, so any method that finds the nearest level of each kind gives the same bits.
+ *   lambda > 0 favours bit 1 (the sign of mimo_qam_llr); 4 lambda / noise_var is that seam's max-log
+ *   approximation.
+ *  Reliability and bin: for transmitted bit b, rho = lambda if b = 1, else -lambda; rho < 0 is a
+ *   hard-decision error.  With scale = 128.0 / rho_max formed once on the host in double,
+ *     bin = clamp(floor(rho * scale), -128, 127) + 128,
+ *   the clamp in double before the integer conversion: 256 linear bins of width rho_max / 128, bin
+ *   128 opens at exactly 0, bins 0 and 255 take everything beyond the range.
+ *  Row of a trial: n_idx * MIMO_SOFT_BINS doubles, n_idx as in the counts layout ([clean if
+ *   incl_clean] + one entry per recorded iteration).  Cell [i][b] is the number of the
+ *   n_sub_carr log2(constel_size) bit reliabilities of counter index i that fall in bin b: both axes
+ *   and every Gray bit of every data sub-carrier, pooled, taken on the value that index slices (the
+ *   clean run's z_c, or an iteration's z - dist).  Only recorded iterations are binned; off-band
+ *   slots contribute nothing.
+ * soft_out: [n_points][n_idx * 256] totals (ADDED to; the cells are integers held exactly in doubles,
+ * so totals are bit-identical whatever the order or split).  per_trial_soft: optional
+ * [sum n_trials][n_idx * 256] rows in point order, NULL to skip.  The per-trial rows of one launch
+ * live in a device buffer of at most MIMO_SOFT_BUFFER_BYTES (256 MiB, a design figure), so a soft
+ * launch holds floor(2^28 / (8 * 256 * n_idx)) trials, or fewer (MIMO_MAX_LAUNCH_TRIALS).
+ * MIMO_EINVAL, before any HIP call: a float32 engine, a null soft_out, a rho_max that is not finite
+ * and > 0, or whose 128 / rho_max is not finite and > 0.  (Added within ABI 8: a library without it
+ * is reported by name.) */
+enum { MIMO_SOFT_BINS = 256 };
+#define MIMO_SOFT_BUFFER_BYTES (256u << 20)
+int32_t mimo_soft_width(int32_t n_iters, int32_t incl_clean); /* MIMO_SOFT_BINS * n_idx; host only */
+int32_t mimo_engine_soft_points(mimo_engine* e, int32_t n_points, const mimo_point* points, const uint64_t* seeds,
+                                const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters,
+                                int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
+                                uint32_t* per_trial, double rho_max, double* soft_out, double* per_trial_soft);
 /* Device time of the trial kernels of the last run, in ms (HIP events on the engine stream). */
 double mimo_engine_last_kernel_ms(const mimo_engine* e);
 /* ... and of the beamforming kernels of the last beam call (0 after any other call). */
@@ -322,6 +364,8 @@ void mimo_engine_destroy(mimo_engine* e);
  *   iters         n_iters >= 1 values, ascending, unique, >= 0
  * mimo_qam_map: labels in [0, constel_size).  mimo_qam_llr: noise_var holds n values; out is
  * [n][log2 constel_size], MSB first, +inf where the zero-bit sum underflows to 0.
+ * mimo_qam_softbits: out is [n][log2 constel_size] values of the soft mode's lambda (see
+ * mimo_engine_soft_points), the I-axis bits MSB first and then the Q-axis bits: mimo_qam_llr's layout.
  * mimo_ofdm_tx: sym_iq [batch][n_sub_carr] -> td_iq [batch][n_fft + cp_len]; mimo_ofdm_rx the
  * reverse.  mimo_awgn: out = in + sqrt(-ln u1) exp(j 2 pi u2) noise_std / sqrt(2) with
  * (w0, w1, ., .) = Philox4x32-10 of counter (i_lo, counter_lo, 6, counter_hi ^ i_hi) under the
@@ -329,6 +373,7 @@ void mimo_engine_destroy(mimo_engine* e);
 int32_t mimo_qam_map(int32_t constel_size, const int32_t* labels, int64_t n, double* out_iq);
 int32_t mimo_qam_slice(int32_t constel_size, const double* in_iq, int64_t n, int32_t* labels_out);
 int32_t mimo_qam_llr(int32_t constel_size, const double* in_iq, int64_t n, const double* noise_var, double* llr_out);
+int32_t mimo_qam_softbits(int32_t constel_size, const double* in_iq, int64_t n, double* out);
 int32_t mimo_fft(int32_t n_fft, int64_t batch, int32_t inverse, const double* in_iq, double* out_iq);
 int32_t mimo_ofdm_tx(int32_t n_fft, int32_t n_sub_carr, int32_t cp_len, int64_t batch, const double* sym_iq,
                      double* td_iq);

@@ -80,6 +80,10 @@ SYMBOLS = {
     "mimo_engine_envelope_points": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(MimoPoint), _u64p,
                                                      _u64p, _u64p, _i32p, ctypes.c_int32, ctypes.c_int32, _u64p, _u64p,
                                                      _u32p, ctypes.c_double, _dp, _dp]),
+    "mimo_soft_width": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32]),
+    "mimo_engine_soft_points": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(MimoPoint), _u64p,
+                                                 _u64p, _u64p, _i32p, ctypes.c_int32, ctypes.c_int32, _u64p, _u64p,
+                                                 _u32p, ctypes.c_double, _dp, _dp]),
     "mimo_engine_last_kernel_ms": (ctypes.c_double, [ctypes.c_void_p]),
     "mimo_engine_last_beam_ms": (ctypes.c_double, [ctypes.c_void_p]),
     "mimo_engine_describe": (ctypes.c_char_p, [ctypes.c_void_p]),
@@ -87,6 +91,7 @@ SYMBOLS = {
     "mimo_qam_map": (ctypes.c_int32, [ctypes.c_int32, _i32p, ctypes.c_int64, _dp]),
     "mimo_qam_slice": (ctypes.c_int32, [ctypes.c_int32, _dp, ctypes.c_int64, _i32p]),
     "mimo_qam_llr": (ctypes.c_int32, [ctypes.c_int32, _dp, ctypes.c_int64, _dp, _dp]),
+    "mimo_qam_softbits": (ctypes.c_int32, [ctypes.c_int32, _dp, ctypes.c_int64, _dp]),
     "mimo_fft": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, _dp, _dp]),
     "mimo_ofdm_tx": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _dp, _dp]),
     "mimo_ofdm_rx": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _dp, _dp]),
@@ -119,6 +124,7 @@ BEAM_FIXED = 5   # include/mimo_engine.h MIMO_BEAM_FIXED
 ENV_BINS = 128   # include/mimo_engine.h MIMO_ENV_BINS
 ENV_FIXED = 4    # include/mimo_engine.h MIMO_ENV_FIXED
 ENV_WIDTH = 2 * ENV_BINS + ENV_FIXED
+SOFT_BINS = 256  # include/mimo_engine.h MIMO_SOFT_BINS
 
 
 def lib():
@@ -502,6 +508,108 @@ class EnvelopeStats:
                 f"gain={abs(self.gain):.4f})")
 
 
+class SoftStats:
+    """Bit reliabilities of a soft call (mimo_engine_soft_points): ``hist[n_idx][256]``, per counter
+    index ([clean] + one per recorded iteration) the number of bit reliabilities
+    ``rho = +-lambda`` (the max-log soft bit signed by the transmitted bit; ``rho < 0`` is a
+    hard-decision error) in each of 256 linear bins of width ``rho_max / 128``; bin 128 opens at 0,
+    bins 0 and 255 take everything beyond ``-+rho_max``.  From it the bit-wise mutual information of
+    the demapper's outputs, the BICM generalised mutual information (GMI), which predicts what a
+    coded link gets from the same trials: with the decoder's LLR ``scale * rho``,
+    ``gmi(scale) = 1 - mean log2(1 + exp(-scale rho))``, evaluated on the bin midpoints.
+    ``a + b`` (``a.pool(b)``) pools two measurements of one system taken with the same ``rho_max``."""
+
+    def __init__(self, hist, rho_max, constel_size, n_trials):
+        self.hist = np.array(hist, np.float64).reshape(-1, SOFT_BINS)
+        self.rho_max, self.constel_size, self.n_trials = float(rho_max), int(constel_size), int(n_trials)
+        if not (self.rho_max > 0 and np.isfinite(self.rho_max)) or self.constel_size < 4 or self.n_trials < 0:
+            raise ValueError("rho_max is finite and > 0, constel_size >= 4 and n_trials >= 0")
+
+    @property
+    def n_idx(self):
+        return self.hist.shape[0]
+
+    @property
+    def width(self):
+        """The bin width rho_max / 128."""
+        return self.rho_max / 128.0
+
+    @property
+    def centres(self):
+        """The bin midpoints (bins 0 and 255 stand for everything beyond them)."""
+        return (np.arange(SOFT_BINS) - 128 + 0.5) * self.width
+
+    @property
+    def n_bits(self):
+        """Reliabilities per counter index (exact: the cells are integers below 2^53)."""
+        return self.hist.sum(axis=1)
+
+    def _share(self, cells):
+        n = self.n_bits
+        out = np.zeros(self.n_idx)
+        np.divide(cells, n, out=out, where=n > 0)
+        return out
+
+    def ber(self):
+        """The share of reliabilities below 0 (bins 0 ... 127): the hard-decision BER, per index."""
+        return self._share(self.hist[:, :128].sum(axis=1))
+
+    def clamped(self):
+        """The share in bins 0 and 255, beyond the range: choose a larger rho_max if it matters."""
+        return self._share(self.hist[:, 0] + self.hist[:, -1])
+
+    def nominal_scale(self, noise_var):
+        """4 / noise_var: the scale that turns rho into the max-log LLR of a Gaussian channel whose
+        complex noise has variance ``noise_var`` in lattice units (``mimo_qam_llr``'s argument)."""
+        return 4.0 / float(noise_var)
+
+    def gmi(self, scale=None):
+        """Per index, ``1 - sum_b h_b log2(1 + exp(-scale c_b)) / N`` in bits per coded bit (0 where
+        nothing was measured); ``scale`` one number or one per index; None: the maximum over
+        ``scale > 0`` (at ``best_scale()``)."""
+        if scale is None:
+            return self.gmi(self.best_scale())
+        s = np.broadcast_to(np.asarray(scale, np.float64), (self.n_idx,))
+        loss = (self.hist * np.logaddexp(0.0, -s[:, None] * self.centres[None, :])).sum(axis=1) / np.log(2.0)
+        return np.where(self.n_bits > 0, 1.0 - self._share(loss), 0.0)
+
+    def best_scale(self, iters=120):
+        """Per index the scale that maximises ``gmi(scale)``: a golden-section search on
+        ``log scale`` (the function is concave in ``scale``, so it has one maximum there too) between
+        ``1e-3 / rho_max`` and ``2e3 / width``, where every LLR is negligible / saturated.  A histogram
+        without errors keeps growing with the scale and returns the upper end."""
+        lo = np.full(self.n_idx, np.log(1e-3 / self.rho_max))
+        hi = np.full(self.n_idx, np.log(2e3 / self.width))
+        g = (np.sqrt(5.0) - 1.0) / 2.0
+        f = lambda t: self.gmi(np.exp(t))
+        a, b = hi - g * (hi - lo), lo + g * (hi - lo)
+        fa, fb = f(a), f(b)
+        for _ in range(int(iters)):
+            left = fa > fb   # the maximum lies in [lo, b]
+            hi = np.where(left, b, hi)
+            lo = np.where(left, lo, a)
+            a, b = hi - g * (hi - lo), lo + g * (hi - lo)
+            fa, fb = f(a), f(b)
+        return np.exp(0.5 * (lo + hi))
+
+    def rate(self):
+        """``log2(constel_size) gmi()``: achievable bits per data sub-carrier, per index."""
+        return np.log2(self.constel_size) * self.gmi()
+
+    def pool(self, other):
+        if not isinstance(other, SoftStats):
+            return NotImplemented
+        if (other.constel_size, other.rho_max, other.n_idx) != (self.constel_size, self.rho_max, self.n_idx):
+            raise ValueError("reliabilities of different systems or ranges cannot be pooled")
+        return SoftStats(self.hist + other.hist, self.rho_max, self.constel_size, self.n_trials + other.n_trials)
+
+    __add__ = pool
+
+    def __repr__(self):
+        return (f"SoftStats(n_idx={self.n_idx}, n_trials={self.n_trials}, rho_max={self.rho_max:g}, "
+                f"ber={np.array2string(self.ber(), precision=3)}, gmi={np.array2string(self.gmi(), precision=4)})")
+
+
 class Engine:
     """One configured system (the deep-copied objects of a ``Link``) on one GPU."""
 
@@ -687,6 +795,23 @@ class Engine:
                                                       iters, ref_pow, incl_clean, per_trial)
         return err[0], bits[0], env[0], pt, pe
 
+    def soft_points(self, points, seeds, first_trials, n_trials, iters, rho_max, incl_clean=False, per_trial=False):
+        """run_points in soft mode (mimo_engine_soft_points; float64 engines): the same trials and
+        counts, and per point and counter index the histogram of the bit reliabilities over 256 bins
+        of width ``rho_max / 128``.
+        -> (err[P, n_idx], bits[P, n_idx], soft[P, n_idx, 256], per-trial counts [sum n_trials, n_idx] or
+        None, per-trial rows [sum n_trials, n_idx, 256] or None);
+        SoftStats(soft[i], rho_max, constel_size, n_trials[i])."""
+        return self._points_call("mimo_engine_soft_points", points, seeds, first_trials, n_trials, iters, incl_clean,
+                                 per_trial, lambda n_idx: ((n_idx, SOFT_BINS), (ctypes.c_double(float(rho_max)),)))
+
+    def soft(self, seed, first_trial, n_trials, iters, rho_max, incl_clean=False, per_trial=False, point=None):
+        """One point (the last set_point's, or ``point``: make_point keywords / MimoPoint).
+        -> (err[n_idx], bits[n_idx], soft[n_idx, 256], per-trial counts or None, per-trial rows or None)."""
+        err, bits, soft, pt, ps = self.soft_points([self._one_point(point)], [seed], [first_trial], [n_trials],
+                                                   iters, rho_max, incl_clean, per_trial)
+        return err[0], bits[0], soft[0], pt, ps
+
     @property
     def kernel_ms(self):
         return self._L.mimo_engine_last_kernel_ms(self._h)
@@ -736,6 +861,17 @@ def qam_llr(constel_size, symbols, noise_var):
     _check(lib().mimo_qam_llr(int(constel_size), _ptr(z, ctypes.c_double), n, _ptr(nv, ctypes.c_double),
                               _ptr(out, ctypes.c_double)))
     return out
+
+
+def qam_softbits(constel_size, symbols):
+    """The soft mode's max-log soft bits ``lambda`` (mimo_qam_softbits): [n][log2 M], the I-axis bits
+    MSB first and then the Q-axis bits (``qam_llr``'s layout); ``4 lambda / noise_var`` approximates it."""
+    z = as_iq(np.asarray(symbols).reshape(-1))
+    n = z.size // 2
+    nb = int(np.log2(constel_size))
+    out = np.empty(n * nb, np.float64)
+    _check(lib().mimo_qam_softbits(int(constel_size), _ptr(z, ctypes.c_double), n, _ptr(out, ctypes.c_double)))
+    return out.reshape(n, nb)
 
 
 def fft(x, inverse=False):

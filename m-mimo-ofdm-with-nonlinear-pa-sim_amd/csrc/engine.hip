@@ -169,10 +169,10 @@ struct mimo_engine {
   Buf<double> ant_rel64, f_rel64, f_over_c, tx_pos_dev;
   Buf<uint32_t> counts;
   Buf<unsigned long long> tot;            // [points][n_idx] totals of one run
-  // row-mode calls (measure, spectrum, beam, envelope: one mode per call, so one pair): the per-trial
-  // rows of one launch and their per-slice partials.  Spectrum, beam and envelope rows hold at most
-  // MIMO_SPEC_BUFFER_BYTES / MIMO_BEAM_ROWS_BYTES / MIMO_ENV_BUFFER_BYTES (that bounds the trials of
-  // their launches).
+  // row-mode calls (measure, spectrum, beam, envelope, soft: one mode per call, so one pair): the
+  // per-trial rows of one launch and their per-slice partials.  Spectrum, beam, envelope and soft rows
+  // hold at most MIMO_SPEC_BUFFER_BYTES / MIMO_BEAM_ROWS_BYTES / MIMO_ENV_BUFFER_BYTES /
+  // MIMO_SOFT_BUFFER_BYTES (that bounds the trials of their launches).
   Buf<double> rows;                       // [launch blocks][row width]
   Buf<double> part;                       // [launch slices][row width]
   // beam calls: the beam instances' cells of one launch (at most the beam buffer's bytes: it bounds
@@ -279,6 +279,7 @@ hipError_t launch(int mode, const mimo::InstanceKey& k, dim3 grid, hipStream_t s
     case MIMO_MODE_SPEC: return launch_sized<R, MIMO_MODE_SPEC>(k, grid, st, p, found, attr, out, aux);
     case MIMO_MODE_BEAM: return launch_sized<R, MIMO_MODE_BEAM>(k, grid, st, p, found, attr, out, aux);
     case MIMO_MODE_ENV: return launch_sized<R, MIMO_MODE_ENV>(k, grid, st, p, found, attr, out, aux);
+    case MIMO_MODE_SOFT: return launch_sized<R, MIMO_MODE_SOFT>(k, grid, st, p, found, attr, out, aux);
     default: return launch_sized<R, MIMO_MODE_PLAIN>(k, grid, st, p, found, attr, out, aux);
   }
 }
@@ -303,7 +304,11 @@ struct BeamCall {
 //  envelope (mimo_engine_envelope_points): rows of 2 MIMO_ENV_BINS + MIMO_ENV_FIXED sums (the two
 //   histograms' cells are integers in doubles); the envelope instance runs with the bin scale
 //   1.0625 / ref_pow as its second extra argument, reduce_spec forms the slice partials, and a
-//   launch holds no more trials than its rows fit MIMO_ENV_BUFFER_BYTES.
+//   launch holds no more trials than its rows fit MIMO_ENV_BUFFER_BYTES;
+//  soft (mimo_engine_soft_points): rows of n_idx MIMO_SOFT_BINS histogram cells (integers in
+//   doubles); the soft instance runs with the bin scale 128 / rho_max as its second extra
+//   argument, reduce_spec forms the slice partials, and a launch holds no more trials than its
+//   rows fit MIMO_SOFT_BUFFER_BYTES.
 struct RowMode {
   int mode = MIMO_MODE_PLAIN;
   int width = 0;                        // doubles of one trial's row, and of one point's in out
@@ -311,7 +316,7 @@ struct RowMode {
   double* out = nullptr;                // [points][width], added into
   double* per_trial_out = nullptr;      // [trials of the call][width], or null
   const BeamCall* beam = nullptr;       // beam only
-  double aux = 0.0;                     // envelope only: the kernel's bin scale
+  double aux = 0.0;                     // envelope, soft: the kernel's bin scale
   bool rows() const { return mode != MIMO_MODE_PLAIN; }
 };
 
@@ -627,8 +632,8 @@ int validate_points(const mimo_engine* e, int n_points, const mimo_point* pts, c
 // The CSI instances add n_ant reals of dynamic LDS (the per-antenna power table) to their
 // static LDS: check the sum against the CU's LDS before launching (F 8192 holds
 // ~157 KiB statically, so A = 512 (4 KiB) is the edge).  mode: the instance the call launches --
-// the envelope instances hold their histogram on top of the plain instance's static LDS (the
-// measure, spectrum and beam instances hold what the plain one holds).
+// the envelope and soft instances hold their histogram on top of the plain instance's static LDS
+// (the measure, spectrum and beam instances hold what the plain one holds).
 int check_csi_lds(const mimo_engine* e, const mimo::InstanceKey& key, int mode) {
   hipFuncAttributes fa{};
   bool found = false;
@@ -1135,6 +1140,36 @@ int32_t mimo_engine_envelope_points(mimo_engine* e, int32_t n_points, const mimo
   rm.max_trials = MIMO_ENV_BUFFER_BYTES / (sizeof(double) * (size_t)rm.width);
   rm.out = env_out;
   rm.per_trial_out = per_trial_env;
+  rm.aux = scale;
+  return run_points(e, n_points, points, seeds, first_trial, n_trials, iters, n_iters, incl_clean, err_out, bits_out,
+                    per_trial, rm);
+}
+
+int32_t mimo_soft_width(int32_t n_iters, int32_t incl_clean) {
+  if (n_iters < 1 || n_iters > 32) return fail(MIMO_EINVAL, "n_iters must be in [1, 32]");
+  return MIMO_SOFT_BINS * (n_iters + (incl_clean ? 1 : 0));
+}
+
+int32_t mimo_engine_soft_points(mimo_engine* e, int32_t n_points, const mimo_point* points, const uint64_t* seeds,
+                                const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters,
+                                int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
+                                uint32_t* per_trial, double rho_max, double* soft_out, double* per_trial_soft) {
+  if (!e) return fail(MIMO_EINVAL, "null engine");
+  if (e->cfg.precision != MIMO_PREC_F64)
+    return fail(MIMO_EINVAL, "soft needs a float64 engine (no float32 soft instances are built)");
+  if (!soft_out) return fail(MIMO_EINVAL, "null soft_out");
+  if (!(rho_max > 0) || !std::isfinite(rho_max)) return fail(MIMO_EINVAL, "rho_max must be finite and > 0");
+  const double scale = 128.0 / rho_max;
+  if (!(scale > 0) || !std::isfinite(scale))
+    return fail(MIMO_EINVAL, "rho_max leaves no finite bin scale 128 / rho_max > 0");
+  // (run_points checks n_iters before it reads the width; a list it refuses gets one index here)
+  const int n_idx = (n_iters >= 1 && n_iters <= 32 ? n_iters : 1) + (incl_clean ? 1 : 0);
+  RowMode rm;
+  rm.mode = MIMO_MODE_SOFT;
+  rm.width = MIMO_SOFT_BINS * n_idx;
+  rm.max_trials = MIMO_SOFT_BUFFER_BYTES / (sizeof(double) * (size_t)rm.width);
+  rm.out = soft_out;
+  rm.per_trial_out = per_trial_soft;
   rm.aux = scale;
   return run_points(e, n_points, points, seeds, first_trial, n_trials, iters, n_iters, incl_clean, err_out, bits_out,
                     per_trial, rm);

@@ -12,6 +12,7 @@
 #include "../../include/mimo_engine.h"
 #include "alpha_fit.h"
 #include "philox.h"
+#include "softbits.h"
 
 namespace {
 
@@ -96,6 +97,17 @@ __global__ void k_qam_llr(int M, int L, int hb, int nb, const double2* in, int64
       }
       out[i * nb + nb - 1 - b] = den == 0 ? INFINITY : log(fabs(num) / fabs(den));
     }
+  }
+}
+
+// max-log soft bits lambda (softbits.h soft_axis): [n][2 hb], I-axis bits MSB first, then Q -- the
+// layout of k_qam_llr
+__global__ void k_qam_softbits(int L, int hb, const double2* in, int64_t n, double* out) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const double2 z = in[i];
+    double* o = out + i * (2 * hb);
+    mimo::soft_axis(z.x, L, hb, [&](int j, double lam) { o[hb - 1 - j] = lam; });
+    mimo::soft_axis(z.y, L, hb, [&](int j, double lam) { o[2 * hb - 1 - j] = lam; });
   }
 }
 
@@ -318,6 +330,24 @@ int32_t mimo_qam_llr(int32_t M, const double* in_iq, int64_t n, const double* no
                      dout.as<double>());
   S_TRY(hipGetLastError());
   S_TRY(hipMemcpy(llr_out, dout.p, n * nb * sizeof(double), hipMemcpyDeviceToHost));
+  return MIMO_OK;
+}
+
+int32_t mimo_qam_softbits(int32_t M, const double* in_iq, int64_t n, double* out) {
+  const int L = qam_l(M);
+  if (!L) return sfail(MIMO_EINVAL, kBadQam);
+  if (n < 0) return sfail(MIMO_EINVAL, "n must be >= 0");
+  if (n == 0) return MIMO_OK;
+  int hb = 0;
+  while ((1 << hb) < L) ++hb;
+  const int nb = 2 * hb;
+  DBuf din, dout;
+  S_TRY(din.alloc(n * sizeof(double2)));
+  S_TRY(dout.alloc(n * nb * sizeof(double)));
+  S_TRY(hipMemcpy(din.p, in_iq, n * sizeof(double2), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_qam_softbits, grid_for(n), dim3(256), 0, 0, L, hb, din.as<double2>(), n, dout.as<double>());
+  S_TRY(hipGetLastError());
+  S_TRY(hipMemcpy(out, dout.p, n * nb * sizeof(double), hipMemcpyDeviceToHost));
   return MIMO_OK;
 }
 

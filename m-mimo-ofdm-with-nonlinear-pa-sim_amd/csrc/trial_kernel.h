@@ -33,6 +33,7 @@
 #include "tuning.h"
 #include "alpha_fit.h"
 #include "philox.h"
+#include "softbits.h"
 #include "team_fft.h"
 #include "wave_fft.h"
 #include "split_fft.h"
@@ -44,12 +45,13 @@ enum ChanKind : int { CH_RAYLEIGH = 1, CH_LOS = 2, CH_TWOPATH = 3, CH_TABLE = 4 
 enum RxKind : int { RX_CNC = 1, RX_MCNC = 2 };
 
 // The run mode of the instances a translation unit builds (trial_inst.hip -DINST_MODE=<mode>): one
-// kernel per unit, named and shaped by the mode.  The four row modes are float64 only.
+// kernel per unit, named and shaped by the mode.  The five row modes are float64 only.
 #define MIMO_MODE_PLAIN 0  // trial_kernel: the counts alone
 #define MIMO_MODE_MEAS 1   // trial_kernel_meas
 #define MIMO_MODE_SPEC 2   // trial_kernel_spec
 #define MIMO_MODE_BEAM 3   // trial_kernel_beam
 #define MIMO_MODE_ENV 4    // trial_kernel_env
+#define MIMO_MODE_SOFT 5   // trial_kernel_soft
 #ifndef MIMO_INST_MODE
 #define MIMO_INST_MODE MIMO_MODE_PLAIN
 #endif
@@ -108,6 +110,18 @@ __device__ __forceinline__ int env_bin(double pw, double scale) {
   const int b = (__double2hiint(pw * scale) >> 17) - 8088;
   return b < 0 ? 0 : (b > kEnvBins - 1 ? kEnvBins - 1 : b);
 }
+
+// Soft instances (MIMO_MODE_SOFT): the same trial, the same
+// counts, and per trial a row of n_idx kSoftBins doubles (include/mimo_engine.h
+// mimo_engine_soft_points): for every counter index the histogram of the 2 hb bit reliabilities of
+// every valid slot, taken on the value that index slices -- the clean run's z_c, an iteration's
+// z - dist -- by softbits.h soft_axis / soft_bin (max-log soft bit of each Gray bit of each axis,
+// signed by the transmitted bit, 256 linear bins over +-rho_max).  Only where the index is recorded
+// (a uniform branch): one ds_add_u32 per reliability into a per-team LDS histogram of kSoftBins
+// uint32 (1 KiB), which the team stores as doubles to row[idx kSoftBins + ...] after `record` and
+// zeroes again (plain stores, every cell written once, no global atomics).  All of it sits in the
+// receiver phase, outside the antenna loop.  The row pointer and the bin scale 128 / rho_max are
+// extra arguments of that kernel alone.
 
 constexpr int kMaxCsiAnt = 512;  // CSI-error runs: antennas (dynamic LDS per team, A doubles; engine.hip checks)
 constexpr uint32_t kFixedCsiTrial = 0xFFFFFFFFu;  // CSI stream counter of fixed-channel runs (oracle/sim.py draws)
@@ -888,6 +902,12 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
                                                                                                  double env_scale) {
   constexpr double* meas_rows = nullptr;
   constexpr double* spec_rows = nullptr;
+#elif MIMO_INST_MODE == MIMO_MODE_SOFT
+__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel_soft(TrialParams<R> p0,
+                                                                                                  double* soft_rows,
+                                                                                                  double soft_scale) {
+  constexpr double* meas_rows = nullptr;
+  constexpr double* spec_rows = nullptr;
 #else
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel(TrialParams<R> p0) {
   constexpr double* meas_rows = nullptr;
@@ -900,11 +920,16 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
   constexpr double* env_rows = nullptr;
   constexpr double env_scale = 0.0;
 #endif
+#if MIMO_INST_MODE != MIMO_MODE_SOFT
+  constexpr double* soft_rows = nullptr;
+  constexpr double soft_scale = 0.0;
+#endif
   using C = cx<R>;
   constexpr bool MEAS = MIMO_INST_MODE == MIMO_MODE_MEAS && sizeof(R) == 8;
   constexpr bool SPEC = MIMO_INST_MODE == MIMO_MODE_SPEC && sizeof(R) == 8;
   constexpr bool BEAM = MIMO_INST_MODE == MIMO_MODE_BEAM && sizeof(R) == 8;
   constexpr bool ENV = MIMO_INST_MODE == MIMO_MODE_ENV && sizeof(R) == 8;
+  constexpr bool SOFT = MIMO_INST_MODE == MIMO_MODE_SOFT && sizeof(R) == 8;
   // ---- which point and trial this block runs (uniform binary search over point_start)
   uint32_t pi = 0;
   if (p0.n_points > 1) {
@@ -1745,6 +1770,48 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
       if (t0) meas_rows[(size_t)blockIdx.x * (size_t)(kMeasFixed + p0.n_idx) + col] = (double)tot;
     }
   };
+  // soft instances: the team's reliability histogram of the counter index being recorded.  Zeroed
+  // here; every flush leaves it zeroed for the next index.
+  __shared__ uint32_t soft_hist[SOFT ? kSoftBins : 1];
+  if constexpr (SOFT) {
+    for (int i = t; i < kSoftBins; i += T) soft_hist[i] = 0u;
+    __syncthreads();
+  }
+  // the 2 hb reliabilities of slot s, whose slicer input is v, into the histogram (valid slots only)
+  auto soft_add = [&](int s, C v) __attribute__((always_inline)) {
+    if constexpr (SOFT) {
+      if ((valid_mask >> s) & 1u) {
+        const uint32_t li = lab[s] >> hb, lq = lab[s] & ((1u << hb) - 1u);
+#ifndef MIMO_DIAG_SOFT_NOHIST  // cost breakdowns only: the metric without the LDS adds
+        soft_axis((double)v.x, L, hb, [&](int j, double lam) {
+          atomicAdd(&soft_hist[soft_bin(lam, (li >> j) & 1u, soft_scale)], 1u);
+        });
+        soft_axis((double)v.y, L, hb, [&](int j, double lam) {
+          atomicAdd(&soft_hist[soft_bin(lam, (lq >> j) & 1u, soft_scale)], 1u);
+        });
+#else
+        double keep = 0.0;
+        soft_axis((double)v.x, L, hb, [&](int j, double lam) { keep += (double)soft_bin(lam, (li >> j) & 1u, soft_scale); });
+        soft_axis((double)v.y, L, hb, [&](int j, double lam) { keep += (double)soft_bin(lam, (lq >> j) & 1u, soft_scale); });
+        if (keep < 0.0) atomicAdd(&soft_hist[0], 1u);  // never taken: keeps the metric alive
+#endif
+      }
+    }
+  };
+  // after `record`: the histogram of counter index idx to the trial's row, and zeroed for the next.
+  // The first barrier puts every wave's ds_adds ahead of the reads, the second the zeroes ahead of
+  // the next index's adds; a thread zeroes the cells it read.
+  auto soft_flush = [&](int idx) __attribute__((always_inline)) {
+    if constexpr (SOFT) {
+      __syncthreads();
+      double* row = soft_rows + ((size_t)blockIdx.x * (size_t)p0.n_idx + (size_t)idx) * (size_t)kSoftBins;
+      for (int i = t; i < kSoftBins; i += T) {
+        row[i] = (double)soft_hist[i];
+        soft_hist[i] = 0u;
+      }
+      __syncthreads();
+    }
+  };
   // |a - b|^2 on a valid slot, 0 off band
   auto err2 = [&](int s, C a, C b) __attribute__((always_inline)) -> R {
     const C e = csub(a, b);
@@ -1768,9 +1835,11 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
       const uint32_t lh = slice(zc, L, hb);
       errs += ((valid_mask >> s) & 1u) ? __popc(lh ^ lab[s]) : 0u;
       if constexpr (MEAS) ee += err2(s, zc, sym);
+      soft_add(s, zc);
     }
     measure(kMeasFixed, ee);
     record(0, errs);
+    soft_flush(0);
   }
 
   const R sig = sqrt_ieee(p.es_over_snr * eta);
@@ -1820,8 +1889,13 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
       if constexpr (MEAS) ee += err2(s, csub(z[s], dist[s]), qam_point<R>(lab[s], L, hb));
     }
     if ((p.rec_mask >> it) & 1u) {
+      if constexpr (SOFT) {
+#pragma unroll
+        for (int s = 0; s < NSLOT; ++s) soft_add(s, csub(z[s], dist[s]));
+      }
       measure(kMeasFixed + idx, ee);
       record(idx++, errs);
+      soft_flush(idx - 1);
     }
     return it < p.max_iter;
   };

@@ -189,3 +189,17 @@
 #ifndef MIMO_ENV_SUBH
 #define MIMO_ENV_SUBH 1
 #endif
+
+// ---- soft instances (trial_kernel.h SOFT; tools/soft_bench.py, profiles/r18/soft/)
+// fp64 F 2048: waves / SIMD the register allocation of the soft instances targets.  Their additions
+// sit in the receiver phase, outside the antenna loop, but at 3 (168 VGPRs, the plain instances'
+// target) they spill more than the plain instance does -- config 2's instance: 30 -> 49 spilled
+// VGPRs, scratch 144 -> 224 B / lane (profiles/r18/soft/resources.txt) -- and the kernel takes
+// 0.875 ms per 1,024 trials (CNC iterations 0-4 recorded) against the plain 0.737 (+18.8 %); at 2
+// (217 VGPRs, none spilled, scratch 32 B / lane; two 4-wave teams per CU instead of three) 0.839 ms
+// (+14.4 %), outside the 1 % spread of either.  Measured at F 2048, and applied there only: the
+// soft instances below keep the plain instances' target (F 128 and F 512 spill nothing more there;
+// F 256 and F 1024 do, 12 -> 32 and 32 -> 51 VGPRs at their Rayleigh instances, unmeasured).
+#ifndef MIMO_SOFT_W64_2048
+#define MIMO_SOFT_W64_2048 2
+#endif

@@ -662,6 +662,45 @@ class Link:
         m = self.my_mod
         return [_engine.EnvelopeStats(env[i], self.n_ant_val, m.n_fft, int(n[i]), ref_pow) for i in range(len(n))]
 
+    # ------------------------------------------------------------------ soft mode
+    def nominal_llr_scale(self, point_params: dict = None) -> float:
+        """``4 / noise_var`` with ``noise_var = avg_symbol_power / 10^(snr_db / 10)``: after the AGC
+        the received points are back on the lattice, so this is the point's noise power per
+        sub-carrier in lattice units and the scale that turns a reliability into a max-log LLR."""
+        pp = self.point_params() if point_params is None else point_params
+        if pp["snr_db"] is None:
+            raise ValueError("set_snr() must be called before soft()")
+        return 4.0 * 10 ** (pp["snr_db"] / 10) / float(pp["avg_symbol_power"])
+
+    def soft(self, incl_clean_run: bool, reroll_chan: bool, cnc_n_iter_lst, seed_arr, n_trials: int,
+             rho_max: float = None):
+        """Bit reliabilities of the current grid point over trials [0, n_trials) of ``simulate``'s
+        trial sequence: an ``_engine.SoftStats`` -- per counter ([clean] + one per sorted, unique
+        iteration) the histogram of the demapper's soft outputs, its BER, GMI and achievable rate.
+        ``rho_max=None``: ``32 / nominal_llr_scale()``, so that the 256 bins cover LLRs to about
+        +-32 at the nominal scale -- beyond that a bit costs or earns less than 2e-14 bit of GMI,
+        and a bin is a quarter of an LLR unit wide.  A fixed number of trials, no stopping rule."""
+        return self.soft_points(incl_clean_run, reroll_chan, cnc_n_iter_lst, [seed_arr], [self.point_params()],
+                                n_trials, rho_max)[0]
+
+    def soft_points(self, incl_clean_run: bool, reroll_chan: bool, cnc_n_iter_lst, seed_arrs, point_params, n_trials,
+                    rho_max: float = None) -> list:
+        """``soft`` for many grid points of this system in one engine call (mimo_engine_soft_points),
+        all over the bins of one ``rho_max`` (``None``: ``32 / nominal_llr_scale`` of the point with
+        the most noise, whose reliabilities reach furthest); ``point_params`` as for
+        ``simulate_points``, ``n_trials`` one number or one per point.  -> a list of
+        ``_engine.SoftStats``.  Single GPU."""
+        if any(pp["snr_db"] is None for pp in point_params):
+            raise ValueError("set_snr() must be called before soft()")
+        if rho_max is None:
+            rho_max = max([32.0 / self.nominal_llr_scale(pp) for pp in point_params], default=1.0)
+        rho_max = float(rho_max)
+        uniq = sorted(set(int(i) for i in np.asarray(cnc_n_iter_lst, dtype=np.int64).reshape(-1)))
+        (_, _, soft, _, _), n = self._fixed_trials_call(
+            reroll_chan, seed_arrs, point_params, n_trials,
+            lambda eng, *args: eng.soft_points(*args, uniq, rho_max, incl_clean_run), need_snr="soft")
+        return [_engine.SoftStats(soft[i], rho_max, self.my_mod.constel_size, int(n[i])) for i in range(len(n))]
+
     def update_distortion(self, ibo_val_db: float) -> None:
         """(mp_model.py:230-241)"""
         self.my_array.update_distortion(ibo_db=ibo_val_db, avg_sample_pow=self.my_mod.avg_sample_power)

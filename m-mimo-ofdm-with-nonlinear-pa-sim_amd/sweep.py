@@ -307,6 +307,43 @@ def ccdf_vs_ibo_rows(ibo_arr, stats):
     return head + list(np.stack(cols, axis=1))
 
 
+def gmi_vs_ebn0(link, ibo_arr, ebn0_arr, iters, n_trials, seed=2137, incl_clean=False, reroll_chan=True, rho_max=None):
+    """Bit reliabilities for every IBO of ``ibo_arr`` and every Eb/N0 of ``ebn0_arr``: ``n_trials``
+    trials per point, the IBOs of one Eb/N0 in one ``Link.soft_points`` call over the bins of one
+    ``rho_max`` (``None``: that Eb/N0's ``32 / nominal_llr_scale``, so every noise level keeps the
+    full resolution; one GPU; point ``i_ibo len(ebn0_arr) + i_ebn0`` is seeded by ``point_seed`` of
+    that number, run_grid's order).  -> ``stats[i_ibo][i_ebn0]``, ``_engine.SoftStats``."""
+    m = link.my_mod
+    ibo_arr = np.asarray(ibo_arr, dtype=np.float64)
+    ebn0_arr = np.asarray(ebn0_arr, dtype=np.float64)
+    snr_arr = np.asarray(ebn0_to_snr(ebn0_arr, m.n_sub_carr, m.n_sub_carr, m.constel_size), dtype=np.float64)
+    out = [[None] * len(ebn0_arr) for _ in ibo_arr]
+    for j, snr in enumerate(snr_arr):
+        link.set_snr(float(snr))
+        params, seeds = [], []
+        for i, ibo in enumerate(ibo_arr):
+            link.update_distortion(ibo_val_db=float(ibo))
+            params.append(dict(link.point_params()))
+            seeds.append(point_seed(seed, i * len(ebn0_arr) + j))
+        for i, st in enumerate(link.soft_points(incl_clean, reroll_chan, iters, seeds, params, n_trials, rho_max)):
+            out[i][j] = st
+    return out
+
+
+def gmi_vs_ebn0_rows(ebn0_arr, stats):
+    """CSV rows of one IBO of the soft sweep (``stats``: its SoftStats per Eb/N0): the Eb/N0 axis,
+    then per counter index four rows -- the BER, the GMI at the best scale [bit per coded bit], the
+    best scale, and the rate log2(M) GMI [bit per sub-carrier]."""
+    rows = [np.asarray(ebn0_arr, dtype=np.float64)]
+    ber = np.asarray([st.ber() for st in stats])
+    scale = np.asarray([st.best_scale() for st in stats])
+    gmi = np.asarray([st.gmi(s) for st, s in zip(stats, scale)])
+    bits = np.asarray([np.log2(st.constel_size) for st in stats])
+    for k in range(ber.shape[1]):
+        rows += [ber[:, k], gmi[:, k], scale[:, k], bits * gmi[:, k]]
+    return rows
+
+
 def beam_vs_angle(link, angles_deg, ibo_arr, n_trials, seed=2137, reroll_chan=True, radius=None, z=None):
     """Beampattern of the array over ``angles_deg`` for every IBO of ``ibo_arr``: probes on the
     horizontal circle around the origin through the user (``radius``, ``z``: the link's nominal
@@ -411,7 +448,7 @@ def _build_link(args, device):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--grid", choices=["ber_vs_ebn0", "fixed_ber", "sdr_vs_ibo", "psd_vs_ibo", "beam_vs_angle",
-                                       "ccdf_vs_ibo"],
+                                       "ccdf_vs_ibo", "gmi_vs_ebn0"],
                     default="fixed_ber",
                     help="sdr_vs_ibo: measured in-band SDR and per-iteration signal-to-error ratio per IBO "
                          "(--n-trials trials per point at the first --ebn0 value; one GPU).  psd_vs_ibo: the "
@@ -421,7 +458,10 @@ def main():
                          "user, per IBO (--n-trials trials per point; one GPU).  ccdf_vs_ibo: the CCDF of the "
                          "instantaneous power at the PA inputs and outputs over the array's nominal mean "
                          "power, with efficiency and Bussgang gain, per IBO (--n-trials trials per point; "
-                         "one GPU)")
+                         "one GPU).  gmi_vs_ebn0: per IBO and Eb/N0 the BER, the bit-wise mutual information "
+                         "(GMI) of the demapper's soft outputs at its best LLR scale, that scale and the "
+                         "achievable rate, per recorded iteration (--n-trials trials per point; one GPU; like the "
+                         "other row grids without the clean index, which sweep.gmi_vs_ebn0(incl_clean=True) adds)")
     ap.add_argument("--angles", type=str, default="0:180.1:1", help="beam_vs_angle: start:stop:step [deg]")
     ap.add_argument("--n-ant", type=int, default=64)
     ap.add_argument("--n-sc", type=int, default=2048)
@@ -441,7 +481,7 @@ def main():
     ap.add_argument("--n-err-min", type=int, default=int(1e5))
     ap.add_argument("--seed", type=int, default=2137)
     ap.add_argument("--n-trials", type=int, default=4096,
-                    help="sdr_vs_ibo, psd_vs_ibo, beam_vs_angle, ccdf_vs_ibo: trials per IBO point")
+                    help="sdr_vs_ibo, psd_vs_ibo, beam_vs_angle, ccdf_vs_ibo, gmi_vs_ebn0: trials per point")
     ap.add_argument("--out", type=str, default="figs/csv_results")
     ap.add_argument("--split", choices=["points", "trials", "auto"], default="auto",
                     help="ranks deal whole points by cost (one all-reduce at the end), or share every point's "
@@ -513,6 +553,20 @@ def main():
             ibo_arr[1] - ibo_arr[0] if len(ibo_arr) > 1 else 0.0, args.n_trials)
         save_to_csv(ccdf_vs_ibo_rows(ibo_arr, stats), name, directory=args.out)
         print(f"ccdf sweep done: {len(ibo_arr)} IBO points x {args.n_trials} trials in "
+              f"{time.perf_counter() - t0:.1f} s -> {args.out}")
+        return
+    if args.grid == "gmi_vs_ebn0":
+        if world > 1:
+            raise SystemExit("--grid gmi_vs_ebn0 runs on one GPU")
+        t0 = time.perf_counter()
+        stats = gmi_vs_ebn0(link, ibo_arr, ebn0_arr, iters, args.n_trials, args.seed)
+        for i, ibo in enumerate(ibo_arr):
+            name = "gmi_vs_ebn0_%s_%s_nant%d_ibo%1.2f_ebn0_min%d_max%d_step%1.2f_ntrials%d_niter%s" % (
+                args.receiver, args.channel, args.n_ant, ibo, min(ebn0_arr), max(ebn0_arr),
+                ebn0_arr[1] - ebn0_arr[0] if len(ebn0_arr) > 1 else 0.0, args.n_trials,
+                "_".join(str(v) for v in iters))
+            save_to_csv(gmi_vs_ebn0_rows(ebn0_arr, stats[i]), name, directory=args.out)
+        print(f"gmi sweep done: {len(ibo_arr)} IBO x {len(ebn0_arr)} Eb/N0 points x {args.n_trials} trials in "
               f"{time.perf_counter() - t0:.1f} s -> {args.out}")
         return
     t0 = time.perf_counter()
