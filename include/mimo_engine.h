@@ -18,6 +18,8 @@
  *                                  every antenna's PA input and output (CCDF / PAPR, compression)
  *     mimo_engine_soft_points      the same trials with the histogram of the demapper's bit reliabilities
  *                                  per counter index (BICM GMI / achievable rate per CNC / MCNC iteration)
+ *     mimo_engine_coded_points     the same trials with the bit and frame errors of an LDPC-coded link after
+ *                                  a layered min-sum decoder, per counter index (coded BER / FER per iteration)
  *     mimo_engine_run_points    <- the drivers' grid loops over (IBO, Eb/N0), one launch
  *                                  for many points   main_mp_miso_cnc_constant_ber_req_ebn0_vs_ibo.py:100-215
  *   fine seams (float64 stage kernels, caller-owned host arrays)
@@ -25,6 +27,7 @@
  *     mimo_qam_slice            <- demodulate / symbol_detection       modulation.py:63-88,138-146
  *     mimo_qam_llr              <- soft_decoding                       modulation.py:29-59
  *     mimo_qam_softbits            the soft mode's max-log soft bit lambda (no reference entry point)
+ *     mimo_ldpc_decode             the coded mode's LDPC decoder on caller-given channel values
  *     mimo_ofdm_tx / _rx        <- _tx_ofdm_symbol / _rx_ofdm_symbol   modulation.py:248-293
  *     mimo_fft                  <- utilities.to_freq/time_domain       utilities.py:311-339
  *     mimo_pa                   <- SoftLimiter/Rapp/ThirdOrderNonLin.process  distortion.py
@@ -340,10 +343,79 @@ int32_t mimo_engine_soft_points(mimo_engine* e, int32_t n_points, const mimo_poi
                                 const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters,
                                 int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
                                 uint32_t* per_trial, double rho_max, double* soft_out, double* per_trial_soft);
+/* Coded mode (float64 engines): the trials, arguments, launch splitting and point rules of
+ * mimo_engine_run_points and the same counts, plus per point and per counter index the bit and frame
+ * errors of an LDPC-coded link after a real iterative decoder of finite length with fixed-point
+ * messages, fed by the demapper's reliabilities after every recorded CNC / MCNC iteration.  There is
+ * no encoder: the labels are i.i.d. uniform draws, that is a codeword of any linear code XORed with
+ * a uniform scrambler known to the receiver, and a min-sum decoder is symmetric under the sign flips
+ * of a codeword, so decoding the reliabilities rho (> 0: the transmitted bit is favoured) against
+ * the all-zero codeword has exactly the error events of that scrambled coded link.  Everything is
+ * integer after one floor, so any implementation of this text gives the same numbers.
+ *  Code: a QC-LDPC code given by its base matrix (mimo_ldpc_code below; no table ships here).  z in
+ *   [1, 512], n_rows in [1, 64], n_cols in [2, 128], N = n_cols z code bits; shifts[r][c] is -1 for a
+ *   zero block, else s in [0, z): check i of base row r touches bit c z + (i + s) mod z of base
+ *   column c.  Every base row has weight 2 ... 32, every base column weight >= 1.  n_dec_iters in
+ *   [1, 64] decoder iterations, always run in full (no early stop).
+ *  Channel value: with scale = 32.0 / rho_max formed once on the host in double and rho exactly the
+ *   soft mode's reliability (mimo_engine_soft_points; no fused multiply-add),
+ *     c = 2 * clamp(floor(rho * scale), -32, 31) + 1,
+ *   the clamp in double before the integer conversion: an odd integer in [-63, 63], never 0; c < 0 is
+ *   an uncoded bit error.  The 64 bins' edges are soft-mode edges at the same rho_max.
+ *  Bit stream of one trial and counter index: Gray bit j of data sub-carrier k at p = j S + k, j in
+ *   mimo_qam_llr's layout (the I axis MSB first, then the Q axis), k in the order of the labels,
+ *   S = n_sub_carr.  n_cw = floor(S log2 M / N) codewords, >= 1; bit n of codeword w is stream
+ *   position n n_cw + w (interleaved: every codeword sees every bit level); positions from n_cw N
+ *   upwards are not decoded.
+ *  Decoder: layered normalised min-sum, factor 3/4.  L[n] = c[n] (int16), one message R per edge,
+ *   starting at 0.  n_dec_iters times, the base rows r in ascending order, and for every check i of
+ *   row r (independent within a layer) and each of its edges e:  T_e = L[n_e] - R_e;  m_e = the
+ *   smallest |T| over the other edges of the check;  sg_e = -1 if an odd number of the other edges
+ *   have T < 0 (a T of 0 counts as non-negative), else +1;  R_e = sg_e min(127, (3 m_e) >> 2);
+ *   L[n_e] = T_e + R_e.  No other clamp: L = c + the bit's current R's, |L| <= 63 + 127 n_rows <= 8191.
+ *   Ties in the minimum change no value.  Hard decision: bit = 1 iff L < 0.
+ *  Row of a trial: n_idx * MIMO_CODED_FIXED doubles, all integers; per counter index, over the trial's
+ *   n_cw codewords: [0] the number of c < 0 among the n_cw N decoded positions, [1] the number of
+ *   L < 0 after decoding, [2] codewords with any L < 0, [3] codewords whose hard decision has a
+ *   non-zero syndrome.  (A flagged frame is no codeword, so it is wrong: [2] - [3] counts the frames
+ *   that are wrong and pass every check, the undetected errors.)  Only recorded iterations leave cells.
+ * coded_out: [n_points][n_idx * 4] totals (ADDED to; integers held exactly in doubles, so totals are
+ * bit-identical whatever the order or split).  per_trial_coded: optional [sum n_trials][n_idx * 4]
+ * rows in point order, NULL to skip.  per_trial_chan: optional [sum n_trials][n_idx][S log2 M] int8,
+ * the c values of every stream position (the undecoded tail included), NULL to skip: any decoder of
+ * the caller's can run on them.  The channel values of one launch live in a device buffer of at most
+ * MIMO_CODED_BUFFER_BYTES (256 MiB, a design figure), so a coded launch holds
+ * floor(2^28 / (n_idx S log2 M)) trials, or fewer (MIMO_MAX_LAUNCH_TRIALS).  The decoder keeps its
+ * state in the LDS of one workgroup: 2 B per code bit (rounded up to 8) + 8 B per check + 96 B.
+ * MIMO_EINVAL, before any HIP call, with a message naming the field: a float32 engine; a null code,
+ * code->shifts or coded_out; a range above broken; N > S log2 M; a rho_max that is not finite and
+ * > 0, or whose 32 / rho_max is not finite and > 0; a decoder state above 163,840 B (the message
+ * names the figure).  (Added within ABI 8: a library without it is reported by name.) */
+typedef struct mimo_ldpc_code {
+  int32_t z;             /* lifting size, 1 ... 512 */
+  int32_t n_rows;        /* base rows, 1 ... 64 */
+  int32_t n_cols;        /* base columns, 2 ... 128; N = n_cols z code bits */
+  const int16_t* shifts; /* [n_rows][n_cols]: -1 = zero block, else s in [0, z): check i of base
+                            row r touches bit c z + (i + s) mod z of base column c */
+  int32_t n_dec_iters;   /* 1 ... 64, always run in full: no early stop */
+} mimo_ldpc_code;
+enum { MIMO_CODED_FIXED = 4 };
+#define MIMO_CODED_BUFFER_BYTES (256u << 20)
+int32_t mimo_coded_width(int32_t n_iters, int32_t incl_clean); /* MIMO_CODED_FIXED * n_idx; host only */
+/* n_cw = floor(n_sub_carr log2(constel_size) / N) >= 1, or MIMO_EINVAL (the code's rules, the
+ * constellation, N > n_sub_carr log2 constel_size); host only */
+int32_t mimo_coded_codewords(int32_t n_sub_carr, int32_t constel_size, const mimo_ldpc_code* code);
+int32_t mimo_engine_coded_points(mimo_engine* e, int32_t n_points, const mimo_point* points, const uint64_t* seeds,
+                                 const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters,
+                                 int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
+                                 uint32_t* per_trial, const mimo_ldpc_code* code, double rho_max, double* coded_out,
+                                 double* per_trial_coded, int8_t* per_trial_chan);
 /* Device time of the trial kernels of the last run, in ms (HIP events on the engine stream). */
 double mimo_engine_last_kernel_ms(const mimo_engine* e);
 /* ... and of the beamforming kernels of the last beam call (0 after any other call). */
 double mimo_engine_last_beam_ms(const mimo_engine* e);
+/* ... and of the decoder kernels of the last coded call (0 after any other call). */
+double mimo_engine_last_decode_ms(const mimo_engine* e);
 /* Which kernel instance the current config selects: "F=2048 T=128 slots=8 aligned ..." */
 const char* mimo_engine_describe(const mimo_engine* e);
 void mimo_engine_destroy(mimo_engine* e);
@@ -374,6 +446,11 @@ int32_t mimo_qam_map(int32_t constel_size, const int32_t* labels, int64_t n, dou
 int32_t mimo_qam_slice(int32_t constel_size, const double* in_iq, int64_t n, int32_t* labels_out);
 int32_t mimo_qam_llr(int32_t constel_size, const double* in_iq, int64_t n, const double* noise_var, double* llr_out);
 int32_t mimo_qam_softbits(int32_t constel_size, const double* in_iq, int64_t n, double* out);
+/* The coded mode's decoder on caller-given channel values (see mimo_engine_coded_points): chan is
+ * [n_cw][N] int8, app_out [n_cw][N] int16 the final L of every bit.  chan may hold any integer with
+ * |c| <= 63, 0 and even values included; beyond that, or for a code that breaks its rules,
+ * MIMO_EINVAL before any HIP call.  n_cw = 0 is MIMO_OK with nothing read or written. */
+int32_t mimo_ldpc_decode(const mimo_ldpc_code* code, const int8_t* chan, int64_t n_cw, int16_t* app_out);
 int32_t mimo_fft(int32_t n_fft, int64_t batch, int32_t inverse, const double* in_iq, double* out_iq);
 int32_t mimo_ofdm_tx(int32_t n_fft, int32_t n_sub_carr, int32_t cp_len, int64_t batch, const double* sym_iq,
                      double* td_iq);

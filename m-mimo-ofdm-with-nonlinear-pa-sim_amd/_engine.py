@@ -33,6 +33,8 @@ _i32p = ctypes.POINTER(ctypes.c_int32)
 _i64p = ctypes.POINTER(ctypes.c_int64)
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
+_i8p = ctypes.POINTER(ctypes.c_int8)
+_i16p = ctypes.POINTER(ctypes.c_int16)
 
 
 class MimoConfig(ctypes.Structure):
@@ -50,6 +52,33 @@ class MimoPoint(ctypes.Structure):
                 ("p_hardness", ctypes.c_double), ("toi_coeff", ctypes.c_double), ("cnc_sat_pow", ctypes.c_double),
                 ("cnc_toi_coeff", ctypes.c_double), ("cnc_alpha", ctypes.c_double), ("csi_eps", ctypes.c_double),
                 ("array_alpha", ctypes.c_double)]
+
+
+class LdpcCode(ctypes.Structure):
+    """mimo_ldpc_code: a QC-LDPC code by its base matrix.  ``LdpcCode(z, table, n_dec_iters)`` with
+    ``table`` [n_rows, n_cols] of shifts, -1 for a zero block: check i of base row r touches bit
+    ``c z + (i + s) mod z`` of base column c.  ``table`` (int16, read-only) stays with the object."""
+    _fields_ = [("z", ctypes.c_int32), ("n_rows", ctypes.c_int32), ("n_cols", ctypes.c_int32), ("shifts", _i16p),
+                ("n_dec_iters", ctypes.c_int32)]
+
+    def __init__(self, z, table, n_dec_iters=10):
+        t = np.asarray(table)
+        if t.ndim != 2:
+            raise ValueError("the shift table must be [n_rows, n_cols]")
+        if t.size and (t.min() < -32768 or t.max() > 32767):  # (the rules are the library's to check)
+            raise ValueError("shifts must fit int16")
+        self.table = np.ascontiguousarray(t, dtype=np.int16)
+        self.table.setflags(write=False)
+        super().__init__(z=int(z), n_rows=t.shape[0], n_cols=t.shape[1], shifts=self.table.ctypes.data_as(_i16p),
+                         n_dec_iters=int(n_dec_iters))
+
+    @property
+    def n_bits(self):
+        """N = n_cols z code bits."""
+        return self.n_cols * self.z
+
+    def with_iters(self, n_dec_iters):
+        return LdpcCode(self.z, self.table, n_dec_iters)
 
 
 SYMBOLS = {
@@ -84,6 +113,13 @@ SYMBOLS = {
     "mimo_engine_soft_points": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(MimoPoint), _u64p,
                                                  _u64p, _u64p, _i32p, ctypes.c_int32, ctypes.c_int32, _u64p, _u64p,
                                                  _u32p, ctypes.c_double, _dp, _dp]),
+    "mimo_coded_width": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32]),
+    "mimo_coded_codewords": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(LdpcCode)]),
+    "mimo_engine_coded_points": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(MimoPoint), _u64p,
+                                                  _u64p, _u64p, _i32p, ctypes.c_int32, ctypes.c_int32, _u64p, _u64p,
+                                                  _u32p, ctypes.POINTER(LdpcCode), ctypes.c_double, _dp, _dp, _i8p]),
+    "mimo_engine_last_decode_ms": (ctypes.c_double, [ctypes.c_void_p]),
+    "mimo_ldpc_decode": (ctypes.c_int32, [ctypes.POINTER(LdpcCode), _i8p, ctypes.c_int64, _i16p]),
     "mimo_engine_last_kernel_ms": (ctypes.c_double, [ctypes.c_void_p]),
     "mimo_engine_last_beam_ms": (ctypes.c_double, [ctypes.c_void_p]),
     "mimo_engine_describe": (ctypes.c_char_p, [ctypes.c_void_p]),
@@ -125,6 +161,7 @@ ENV_BINS = 128   # include/mimo_engine.h MIMO_ENV_BINS
 ENV_FIXED = 4    # include/mimo_engine.h MIMO_ENV_FIXED
 ENV_WIDTH = 2 * ENV_BINS + ENV_FIXED
 SOFT_BINS = 256  # include/mimo_engine.h MIMO_SOFT_BINS
+CODED_FIXED = 4  # include/mimo_engine.h MIMO_CODED_FIXED
 
 
 def lib():
@@ -610,6 +647,70 @@ class SoftStats:
                 f"ber={np.array2string(self.ber(), precision=3)}, gmi={np.array2string(self.gmi(), precision=4)})")
 
 
+class CodedStats:
+    """Coded-link errors of a coded call (mimo_engine_coded_points): ``cells[n_idx][4]``, per counter
+    index ([clean] + one per recorded iteration) over all decoded codewords the number of channel
+    values below 0 (uncoded errors at the decoded positions), of wrong bits after the decoder, of
+    wrong frames, and of frames whose hard decision fails a parity check.  ``n_frames`` codewords of
+    ``n_code_bits`` bits each were decoded per index.  A frame the checks flag is no codeword and
+    therefore wrong, so the flagged frames are among the wrong ones and ``undetected()`` =
+    ``fer() - syndrome_rate()`` is the share of frames that converged to a wrong codeword.
+    ``a + b`` (``a.pool(b)``) pools two measurements of one system and code."""
+
+    def __init__(self, cells, n_frames, n_code_bits):
+        self.cells = np.array(cells, np.float64).reshape(-1, CODED_FIXED)
+        self.n_frames, self.n_code_bits = int(n_frames), int(n_code_bits)
+        if self.n_frames < 0 or self.n_code_bits < 1:
+            raise ValueError("n_frames >= 0 and n_code_bits >= 1")
+
+    @property
+    def n_idx(self):
+        return self.cells.shape[0]
+
+    @property
+    def n_bits(self):
+        """Decoded bits per counter index."""
+        return self.n_frames * self.n_code_bits
+
+    def _share(self, col, n):
+        return self.cells[:, col] / n if n > 0 else np.zeros(self.n_idx)
+
+    def raw_ber(self):
+        """Uncoded BER at the decoded positions, per index."""
+        return self._share(0, self.n_bits)
+
+    def ber(self):
+        """BER after the decoder, per index."""
+        return self._share(1, self.n_bits)
+
+    def fer(self):
+        """Share of codewords with any wrong bit, per index."""
+        return self._share(2, self.n_frames)
+
+    def syndrome_rate(self):
+        """Share of codewords whose hard decision is no codeword (a detected failure), per index."""
+        return self._share(3, self.n_frames)
+
+    def undetected(self):
+        """Share of codewords that are wrong and pass every parity check, per index."""
+        n = self.n_frames
+        return (self.cells[:, 2] - self.cells[:, 3]) / n if n > 0 else np.zeros(self.n_idx)
+
+    def pool(self, other):
+        if not isinstance(other, CodedStats):
+            return NotImplemented
+        if (other.n_code_bits, other.n_idx) != (self.n_code_bits, self.n_idx):
+            raise ValueError("coded errors of different codes or iteration lists cannot be pooled")
+        return CodedStats(self.cells + other.cells, self.n_frames + other.n_frames, self.n_code_bits)
+
+    __add__ = pool
+
+    def __repr__(self):
+        return (f"CodedStats(n_idx={self.n_idx}, n_frames={self.n_frames}, n_code_bits={self.n_code_bits}, "
+                f"raw_ber={np.array2string(self.raw_ber(), precision=3)}, "
+                f"ber={np.array2string(self.ber(), precision=3)}, fer={np.array2string(self.fer(), precision=3)})")
+
+
 class Engine:
     """One configured system (the deep-copied objects of a ``Link``) on one GPU."""
 
@@ -663,11 +764,13 @@ class Engine:
         _check(self._L.mimo_engine_set_point(self._h, ctypes.byref(pt)))
         self._point = pt  # the one-point measure() runs it
 
-    def _points_call(self, name, points, seeds, first_trials, n_trials, iters, incl_clean, per_trial, rows=None):
+    def _points_call(self, name, points, seeds, first_trials, n_trials, iters, incl_clean, per_trial, rows=None,
+                     tail=None):
         """Marshals a ``mimo_engine_*_points`` call and makes it (``name``: the C function).
         ``rows``: None for a plain run, else ``n_idx -> (shape of a point's row, the C arguments
         that stand ahead of the row pointers)``.  -> (err, bits, per-trial counts or None), for a
-        row mode (err, bits, rows[P, *shape], per-trial counts, per-trial rows [sum n_trials, *shape])."""
+        row mode (err, bits, rows[P, *shape], per-trial counts, per-trial rows [sum n_trials, *shape]).
+        ``tail``: ``(trials of the call, n_idx) -> the C arguments behind the row pointers``."""
         P = len(points)
         arr = (MimoPoint * max(1, P))()
         for i, pt in enumerate(points):
@@ -695,7 +798,7 @@ class Engine:
             return err, bits, pt
         tot, p_tot = out((P,) + shape, np.float64, ctypes.c_double)
         pr, p_pr = out((int(nt.sum()),) + shape, np.float64, ctypes.c_double, per_trial)
-        _check(getattr(self._L, name)(*args, *lead, p_tot, p_pr))
+        _check(getattr(self._L, name)(*args, *lead, p_tot, p_pr, *(tail(int(nt.sum()), n_idx) if tail else ())))
         return err, bits, tot, pt, pr
 
     def _one_point(self, point):
@@ -812,6 +915,46 @@ class Engine:
                                                    iters, rho_max, incl_clean, per_trial)
         return err[0], bits[0], soft[0], pt, ps
 
+    def coded_codewords(self, code):
+        """n_cw: codewords per trial and counter index (mimo_coded_codewords)."""
+        return coded_codewords(self.n_sub_carr, self.constel_size, code)
+
+    def coded_points(self, points, seeds, first_trials, n_trials, iters, code, rho_max, incl_clean=False,
+                     per_trial=False, chan=False):
+        """run_points in coded mode (mimo_engine_coded_points; float64 engines): the same trials and
+        counts, and per point and counter index the four error counts of the LDPC-coded link
+        (``code``: an ``LdpcCode``; channel values quantised over ``+-rho_max``).
+        -> (err[P, n_idx], bits[P, n_idx], coded[P, n_idx, 4], per-trial counts [sum n_trials, n_idx] or
+        None, per-trial rows [sum n_trials, n_idx, 4] or None), with ``chan=True`` also the channel
+        values [sum n_trials, n_idx, S log2 M] int8;
+        CodedStats(coded[i], n_trials[i] * coded_codewords(code), code.n_bits)."""
+        sb = self.n_sub_carr * int(round(np.log2(self.constel_size)))
+        got = []
+
+        def tail(n, n_idx):
+            got.append(np.zeros((n, n_idx, sb), np.int8) if chan else None)
+            return (_ptr(got[0], ctypes.c_int8) if chan else None,)
+
+        out = self._points_call("mimo_engine_coded_points", points, seeds, first_trials, n_trials, iters, incl_clean,
+                                per_trial, lambda n_idx: ((n_idx, CODED_FIXED), (ctypes.byref(code),
+                                                                                 ctypes.c_double(float(rho_max)))),
+                                tail)
+        return out + (got[0],) if chan else out
+
+    def coded(self, seed, first_trial, n_trials, iters, code, rho_max, incl_clean=False, per_trial=False, point=None,
+              chan=False):
+        """One point (the last set_point's, or ``point``: make_point keywords / MimoPoint).
+        -> (err[n_idx], bits[n_idx], coded[n_idx, 4], per-trial counts or None, per-trial rows or None
+        [, channel values])."""
+        out = self.coded_points([self._one_point(point)], [seed], [first_trial], [n_trials], iters, code, rho_max,
+                                incl_clean, per_trial, chan)
+        return (out[0][0], out[1][0], out[2][0]) + tuple(out[3:])
+
+    @property
+    def decode_kernel_ms(self):
+        """Device time of the decoder kernels of the last coded call (0 after any other call)."""
+        return self._L.mimo_engine_last_decode_ms(self._h)
+
     @property
     def kernel_ms(self):
         return self._L.mimo_engine_last_kernel_ms(self._h)
@@ -872,6 +1015,39 @@ def qam_softbits(constel_size, symbols):
     out = np.empty(n * nb, np.float64)
     _check(lib().mimo_qam_softbits(int(constel_size), _ptr(z, ctypes.c_double), n, _ptr(out, ctypes.c_double)))
     return out.reshape(n, nb)
+
+
+def coded_width(n_iters, incl_clean=False):
+    """Doubles of a coded row (mimo_coded_width): 4 per counter index."""
+    n = lib().mimo_coded_width(int(n_iters), int(bool(incl_clean)))
+    if n < 0:
+        _check(n)
+    return n
+
+
+def coded_codewords(n_sub_carr, constel_size, code):
+    """n_cw = floor(n_sub_carr log2(constel_size) / N): the codewords of one trial and counter index
+    (mimo_coded_codewords; raises for a code that breaks its rules or is longer than a trial)."""
+    n = lib().mimo_coded_codewords(int(n_sub_carr), int(constel_size), ctypes.byref(code) if code is not None else None)
+    if n < 0:
+        _check(n)
+    return n
+
+
+def ldpc_decode(code, chan):
+    """The coded mode's decoder (mimo_ldpc_decode) on channel values ``chan`` [n_cw, N] (integers with
+    ``|c| <= 63``) -> the final L of every bit, [n_cw, N] int16; a bit is decided 1 where L < 0."""
+    c = np.asarray(chan)
+    if c.size and np.abs(c).max() > 127:
+        raise EngineError("chan must be in [-63, 63]")
+    c = _c(c, np.int8).reshape(-1)
+    n = code.n_bits
+    if n > 0 and c.size % n:
+        raise ValueError("chan must hold whole codewords of n_cols z values")
+    n_cw = c.size // n if n > 0 else 0   # (a code without bits is the library's to refuse)
+    out = np.zeros(c.size, np.int16)
+    _check(lib().mimo_ldpc_decode(ctypes.byref(code), _ptr(c, ctypes.c_int8), n_cw, _ptr(out, ctypes.c_int16)))
+    return out.reshape(n_cw, n) if n > 0 else out
 
 
 def fft(x, inverse=False):

@@ -22,6 +22,7 @@
 #ifndef MIMO_ONLY_F  // the single-size diagnostic builds link neither beam instances nor beam.o
 #include "beam.h"
 #endif
+#include "ldpc.h"
 
 namespace {
 
@@ -157,7 +158,7 @@ struct mimo_engine {
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  hipEvent_t ev2 = nullptr;               // after the beamforming kernel of a launch
+  hipEvent_t ev2 = nullptr;               // after the beamforming / decoder kernel of a launch
   Buf<float2> tw[2];                      // fp32 stage twiddles for team_size(F), alt_team_size(F)
   Buf<double2> tw64;                      // fp64 stage twiddles for team_size64(F)
   Buf<double2> twave64;                   // wave-split FFT twiddles (wave_fft.h) where the instance uses it
@@ -180,6 +181,11 @@ struct mimo_engine {
   Buf<double> bcell;                      // [2][launch blocks][A][F] complex128
   Buf<double> bgeo;                       // dist [n_probes][A] | 1 / dist [n_probes][A] | f / c [F]
   double last_beam_ms = 0.0;
+  // coded calls: the coded instances' channel values of one launch (at most MIMO_CODED_BUFFER_BYTES: it
+  // bounds the trials of a coded launch) and the decoder's tables (ldpc.h LdpcHost::tables)
+  Buf<int8_t> cchan;                      // [launch blocks][n_idx][S log2 M]
+  Buf<int32_t> ctab;
+  double last_decode_ms = 0.0;
   // per-launch tables in one device blob, filled by one copy from a pinned host buffer:
   // TrialParams<R>[segments] | uint32 block offsets [segments + 1] |
   // uint32 reduction-slice starts [slices + 1] (<= kSlice trials, one point each) | int32 point of slice [slices]
@@ -280,6 +286,7 @@ hipError_t launch(int mode, const mimo::InstanceKey& k, dim3 grid, hipStream_t s
     case MIMO_MODE_BEAM: return launch_sized<R, MIMO_MODE_BEAM>(k, grid, st, p, found, attr, out, aux);
     case MIMO_MODE_ENV: return launch_sized<R, MIMO_MODE_ENV>(k, grid, st, p, found, attr, out, aux);
     case MIMO_MODE_SOFT: return launch_sized<R, MIMO_MODE_SOFT>(k, grid, st, p, found, attr, out, aux);
+    case MIMO_MODE_CODED: return launch_sized<R, MIMO_MODE_CODED>(k, grid, st, p, found, attr, out, aux);
     default: return launch_sized<R, MIMO_MODE_PLAIN>(k, grid, st, p, found, attr, out, aux);
   }
 }
@@ -289,6 +296,15 @@ hipError_t launch(int mode, const mimo::InstanceKey& k, dim3 grid, hipStream_t s
 struct BeamCall {
   int n_probes;
   std::vector<double> geo;
+};
+
+// A coded call's code, checked and turned into the decoder's tables by the caller
+// (mimo_engine_coded_points).
+struct CodedCall {
+  mimo::LdpcHost code;
+  int n_cw = 0;                    // codewords of one trial and counter index
+  size_t stream = 0;               // S log2 M: channel values of one trial and counter index
+  int8_t* per_trial_chan = nullptr;  // [trials of the call][n_idx][stream], or null
 };
 
 // What a row mode adds to a plain run, filled once by the extern "C" entry point of the mode:
@@ -308,7 +324,11 @@ struct BeamCall {
 //  soft (mimo_engine_soft_points): rows of n_idx MIMO_SOFT_BINS histogram cells (integers in
 //   doubles); the soft instance runs with the bin scale 128 / rho_max as its second extra
 //   argument, reduce_spec forms the slice partials, and a launch holds no more trials than its
-//   rows fit MIMO_SOFT_BUFFER_BYTES.
+//   rows fit MIMO_SOFT_BUFFER_BYTES;
+//  coded (mimo_engine_coded_points): rows of n_idx MIMO_CODED_FIXED counts (integers in doubles); the
+//   coded instance runs with the scale 32 / rho_max as its second extra argument and fills the
+//   launch's channel values, the decoder kernel (ldpc.hip) forms the per-trial rows from them,
+//   reduce_spec the slice partials; the channel values of a launch fit MIMO_CODED_BUFFER_BYTES.
 struct RowMode {
   int mode = MIMO_MODE_PLAIN;
   int width = 0;                        // doubles of one trial's row, and of one point's in out
@@ -316,7 +336,8 @@ struct RowMode {
   double* out = nullptr;                // [points][width], added into
   double* per_trial_out = nullptr;      // [trials of the call][width], or null
   const BeamCall* beam = nullptr;       // beam only
-  double aux = 0.0;                     // envelope, soft: the kernel's bin scale
+  const CodedCall* coded = nullptr;     // coded only
+  double aux = 0.0;                     // envelope, soft, coded: the kernel's bin scale
   bool rows() const { return mode != MIMO_MODE_PLAIN; }
 };
 
@@ -633,7 +654,7 @@ int validate_points(const mimo_engine* e, int n_points, const mimo_point* pts, c
 // static LDS: check the sum against the CU's LDS before launching (F 8192 holds
 // ~157 KiB statically, so A = 512 (4 KiB) is the edge).  mode: the instance the call launches --
 // the envelope and soft instances hold their histogram on top of the plain instance's static LDS
-// (the measure, spectrum and beam instances hold what the plain one holds).
+// (the measure, spectrum, beam and coded instances hold what the plain one holds).
 int check_csi_lds(const mimo_engine* e, const mimo::InstanceKey& key, int mode) {
   hipFuncAttributes fa{};
   bool found = false;
@@ -774,7 +795,7 @@ struct Progress {
   // row modes: the slice partials of every launch, in launch and slice order, and their points
   std::vector<double> part;
   std::vector<int> part_point;
-  double ms = 0.0, beam_ms = 0.0;
+  double ms = 0.0, beam_ms = 0.0, decode_ms = 0.0;
 };
 
 // The tables of one launch, written into the host blob: the segments' parameters and block
@@ -812,7 +833,7 @@ LaunchTables fill_launch_tables(char* h_blob, const BlobLayout& o, const std::ve
 }
 
 // One launch: its tables into the blob, the trial kernel of the mode, for beam the beamforming
-// kernel, the count and row reductions and the copies back; waits for the launch and times it.
+// kernel, for coded the decoder kernel, the count and row reductions and the copies back; waits for the launch and times it.
 template <typename R>
 int run_launch(mimo_engine* e, const mimo::InstanceKey& key, const mimo::TrialParams<R>& base,
                const std::vector<mimo::TrialParams<R>>& ptab, const BlobLayout& o, const std::vector<Seg>& segs,
@@ -833,9 +854,11 @@ int run_launch(mimo_engine* e, const mimo::InstanceKey& key, const mimo::TrialPa
   HIP_TRY(hipMemcpyAsync(e->blob.p, e->h_blob.p, o.point_of + nsl * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipEventRecord(e->ev0, e->stream));
   bool found = false;
-  // (the beam instances fill the launch's cells; the beamforming kernel forms the rows from them)
-  const hipError_t le =
-      launch(rm.mode, key, dim3(nb), e->stream, kp, &found, nullptr, rm.beam ? e->bcell.p : e->rows.p, rm.aux);
+  // (the beam instances fill the launch's cells; the beamforming kernel forms the rows from them.
+  // The coded instances fill the launch's channel values, int8 behind the same pointer; the decoder
+  // kernel forms the rows from them)
+  double* const inst_out = rm.beam ? e->bcell.p : rm.coded ? reinterpret_cast<double*>(e->cchan.p) : e->rows.p;
+  const hipError_t le = launch(rm.mode, key, dim3(nb), e->stream, kp, &found, nullptr, inst_out, rm.aux);
   if (!found) return fail(MIMO_ENOKERNEL, "no kernel instance for " + e->desc);
   if (le != hipSuccess) return fail(MIMO_EHIP, std::string("trial kernel launch: ") + hipGetErrorString(le));
   HIP_TRY(hipEventRecord(e->ev1, e->stream));
@@ -849,6 +872,16 @@ int run_launch(mimo_engine* e, const mimo::InstanceKey& key, const mimo::TrialPa
     HIP_TRY(hipEventRecord(e->ev2, e->stream));
   }
 #endif
+  if (rm.coded) {
+    const CodedCall& cc = *rm.coded;
+    const hipError_t de = mimo::launch_ldpc(e->stream, cc.code, e->ctab.p, e->cchan.p, (int64_t)nb * n_idx,
+                                            (int64_t)cc.stream, cc.n_cw, cc.n_cw, e->rows.p, nullptr);
+    if (de != hipSuccess) return fail(MIMO_EHIP, std::string("decoder kernel launch: ") + hipGetErrorString(de));
+    HIP_TRY(hipEventRecord(e->ev2, e->stream));
+    if (cc.per_trial_chan)
+      HIP_TRY(hipMemcpyAsync(cc.per_trial_chan + pg->trials_done * (size_t)n_idx * cc.stream, e->cchan.p,
+                             (size_t)nb * n_idx * cc.stream, hipMemcpyDeviceToHost, e->stream));
+  }
   hipLaunchKernelGGL(reduce_counts, dim3((unsigned)nsl, n_idx), dim3(256), 0, e->stream, e->counts.p, d_slice_first,
                      reinterpret_cast<const int32_t*>(e->blob.p + o.point_of), n_idx, e->tot.p);
   HIP_TRY(hipGetLastError());
@@ -881,6 +914,11 @@ int run_launch(mimo_engine* e, const mimo::InstanceKey& key, const mimo::TrialPa
     HIP_TRY(hipEventSynchronize(e->ev2));
     HIP_TRY(hipEventElapsedTime(&ms, e->ev1, e->ev2));
     pg->beam_ms += ms;
+  }
+  if (rm.coded) {
+    HIP_TRY(hipEventSynchronize(e->ev2));
+    HIP_TRY(hipEventElapsedTime(&ms, e->ev1, e->ev2));
+    pg->decode_ms += ms;
   }
   return MIMO_OK;
 }
@@ -943,6 +981,12 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
     HIP_TRY(hipMemcpyAsync(e->bgeo.p, rm.beam->geo.data(), sizeof(double) * rm.beam->geo.size(), hipMemcpyHostToDevice,
                            e->stream));
   }
+  if (rm.coded) {
+    if (int rc = e->cchan.ensure(std::max<size_t>(1, plan.max_blocks * (size_t)n_idx * rm.coded->stream))) return rc;
+    if (int rc = e->ctab.ensure(rm.coded->code.tables.size())) return rc;
+    HIP_TRY(hipMemcpyAsync(e->ctab.p, rm.coded->code.tables.data(), sizeof(int32_t) * rm.coded->code.tables.size(),
+                           hipMemcpyHostToDevice, e->stream));
+  }
   if (int rc = e->counts.ensure((size_t)(1ull << 20) * n_idx)) return rc;
   if (int rc = e->tot.ensure((size_t)n_points * n_idx)) return rc;
   HIP_TRY(hipMemsetAsync(e->tot.p, 0, sizeof(unsigned long long) * n_points * n_idx, e->stream));
@@ -973,6 +1017,7 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
   }
   e->last_ms = pg.ms;
   e->last_beam_ms = pg.beam_ms;
+  e->last_decode_ms = pg.decode_ms;
   return MIMO_OK;
 }
 
@@ -1175,7 +1220,63 @@ int32_t mimo_engine_soft_points(mimo_engine* e, int32_t n_points, const mimo_poi
                     per_trial, rm);
 }
 
+int32_t mimo_coded_width(int32_t n_iters, int32_t incl_clean) {
+  if (n_iters < 1 || n_iters > 32) return fail(MIMO_EINVAL, "n_iters must be in [1, 32]");
+  return MIMO_CODED_FIXED * (n_iters + (incl_clean ? 1 : 0));
+}
+
+int32_t mimo_coded_codewords(int32_t n_sub_carr, int32_t constel_size, const mimo_ldpc_code* code) {
+  mimo::LdpcHost h;
+  std::string err;
+  if (!mimo::ldpc_prepare(code, &h, &err)) return fail(MIMO_EINVAL, err);
+  const int L = (int)std::lround(std::sqrt((double)constel_size));
+  if (L * L != constel_size || !is_pow2(constel_size) || constel_size < 4 || constel_size > 4096)
+    return fail(MIMO_EINVAL, "Constellation size must be a power of some number, only square QAM supported.");
+  if (n_sub_carr < 1) return fail(MIMO_EINVAL, "n_sub_carr must be >= 1");
+  const int64_t stream = (int64_t)n_sub_carr * (int64_t)std::lround(std::log2((double)constel_size));
+  if ((int64_t)h.n_bits() > stream)
+    return fail(MIMO_EINVAL, "code: N = n_cols z = " + std::to_string(h.n_bits()) + " code bits exceed the " +
+                                 std::to_string(stream) + " bits (n_sub_carr log2 constel_size) of one trial");
+  return (int32_t)(stream / h.n_bits());
+}
+
+int32_t mimo_engine_coded_points(mimo_engine* e, int32_t n_points, const mimo_point* points, const uint64_t* seeds,
+                                 const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters,
+                                 int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
+                                 uint32_t* per_trial, const mimo_ldpc_code* code, double rho_max, double* coded_out,
+                                 double* per_trial_coded, int8_t* per_trial_chan) {
+  if (!e) return fail(MIMO_EINVAL, "null engine");
+  if (e->cfg.precision != MIMO_PREC_F64)
+    return fail(MIMO_EINVAL, "coded needs a float64 engine (no float32 coded instances are built)");
+  if (!coded_out) return fail(MIMO_EINVAL, "null coded_out");
+  const int n_cw = mimo_coded_codewords(e->cfg.n_sub_carr, e->cfg.constel_size, code);
+  if (n_cw < 0) return MIMO_EINVAL;
+  if (!(rho_max > 0) || !std::isfinite(rho_max)) return fail(MIMO_EINVAL, "rho_max must be finite and > 0");
+  const double scale = 32.0 / rho_max;
+  if (!(scale > 0) || !std::isfinite(scale))
+    return fail(MIMO_EINVAL, "rho_max leaves no finite scale 32 / rho_max > 0");
+  CodedCall cc;
+  std::string err;
+  if (!mimo::ldpc_prepare(code, &cc.code, &err)) return fail(MIMO_EINVAL, err);
+  cc.n_cw = n_cw;
+  cc.stream = (size_t)e->cfg.n_sub_carr * (size_t)std::lround(std::log2((double)e->cfg.constel_size));
+  cc.per_trial_chan = per_trial_chan;
+  // (run_points checks n_iters before it reads the width; a list it refuses gets one index here)
+  const int n_idx = (n_iters >= 1 && n_iters <= 32 ? n_iters : 1) + (incl_clean ? 1 : 0);
+  RowMode rm;
+  rm.mode = MIMO_MODE_CODED;
+  rm.width = MIMO_CODED_FIXED * n_idx;
+  rm.max_trials = MIMO_CODED_BUFFER_BYTES / (cc.stream * (size_t)n_idx);
+  rm.out = coded_out;
+  rm.per_trial_out = per_trial_coded;
+  rm.coded = &cc;
+  rm.aux = scale;
+  return run_points(e, n_points, points, seeds, first_trial, n_trials, iters, n_iters, incl_clean, err_out, bits_out,
+                    per_trial, rm);
+}
+
 double mimo_engine_last_kernel_ms(const mimo_engine* e) { return e ? e->last_ms : 0.0; }
+double mimo_engine_last_decode_ms(const mimo_engine* e) { return e ? e->last_decode_ms : 0.0; }
 double mimo_engine_last_beam_ms(const mimo_engine* e) { return e ? e->last_beam_ms : 0.0; }
 
 const char* mimo_engine_describe(const mimo_engine* e) {

@@ -53,4 +53,15 @@ __device__ __forceinline__ int soft_bin(double lambda, bool bit, double scale) {
   return (int)fmin(fmax(f, -128.0), 127.0) + 128;
 }
 
+// channel value of the coded mode from the same reliability: c = 2 clamp(floor(rho scale), -32, 31) + 1,
+// the clamp in double before the conversion (scale = 32 / rho_max, formed on the host): an odd
+// integer in [-63, 63], c < 0 a hard-decision error.  Its 64 bins' edges are soft_bin's at the same
+// rho_max.
+__device__ __forceinline__ int coded_value(double lambda, bool bit, double scale) {
+#pragma clang fp contract(off)
+  const double rho = bit ? lambda : -lambda;
+  const double f = floor(rho * scale);
+  return 2 * (int)fmin(fmax(f, -32.0), 31.0) + 1;
+}
+
 }  // namespace mimo

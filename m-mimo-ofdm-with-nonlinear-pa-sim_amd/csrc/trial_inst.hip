@@ -1,7 +1,7 @@
 // Instantiates the fused trial kernel for one FFT size, arithmetic type and run mode: compiled
 // once per -DINST_F=<size> -DINST_F64=<0|1>, and once more per size with -DINST_F64=1
-// -DINST_MODE=<1 measure | 2 spectrum | 3 beam | 4 envelope | 5 soft> (trial_kernel.h MIMO_MODE_*; 0,
-// plain, by default).
+// -DINST_MODE=<1 measure | 2 spectrum | 3 beam | 4 envelope | 5 soft | 6 coded> (trial_kernel.h
+// MIMO_MODE_*; 0, plain, by default).
 #include <type_traits>
 
 #ifndef INST_F
@@ -14,7 +14,7 @@
 #define INST_MODE 0
 #endif
 #if INST_MODE && !INST_F64
-#error "the measure, spectrum, beam, envelope and soft instances are float64 only"
+#error "the measure, spectrum, beam, envelope, soft and coded instances are float64 only"
 #endif
 #define MIMO_INST_MODE INST_MODE
 
@@ -31,6 +31,8 @@
 #define MIMO_TRIAL_KERNEL trial_kernel_env
 #elif INST_MODE == MIMO_MODE_SOFT
 #define MIMO_TRIAL_KERNEL trial_kernel_soft
+#elif INST_MODE == MIMO_MODE_CODED
+#define MIMO_TRIAL_KERNEL trial_kernel_coded
 #else
 #define MIMO_TRIAL_KERNEL trial_kernel
 #endif
@@ -66,9 +68,11 @@ constexpr Profile profile_for(int T, bool aligned, int ch) {
   // (the F 2048 soft instances: 2 waves/SIMD as well, tuning.h MIMO_SOFT_W64_2048: no spilled VGPR, -4 % at
   // config 2; the smaller soft instances keep the plain target -- at 2 the F 512 generic ones, which need up to
   // 326 VGPRs and run at one wave/SIMD, would be capped at 256 and spill, profiles/r18/soft/resources.txt)
+  // (the F 2048 coded instances: tuning.h MIMO_CODED_W64_2048, profiles/r19/coded/)
   if (kF64 && kF <= 2048)
     return Profile{INST_MODE == MIMO_MODE_ENV    ? MIMO_ENV_W64_2048
                    : INST_MODE == MIMO_MODE_SOFT && kF == 2048 ? MIMO_SOFT_W64_2048
+                   : INST_MODE == MIMO_MODE_CODED && kF == 2048 ? MIMO_CODED_W64_2048
                                                  : MIMO_W64_2048,
                    1, false};
   if (kF64 && kF == 4096) return Profile{2, 1, false};  // 16-point team, symbols from levels: 2 teams/CU
@@ -82,7 +86,7 @@ constexpr Profile profile_for(int T, bool aligned, int ch) {
 // attr != null: no launch, the instance's attributes instead (its static LDS, which the
 // engine checks with the CSI table's dynamic LDS against the device limit before a launch).
 // out, aux: the kernel's extra arguments (trial_launch.h launch_trial; the plain kernel has none,
-// the envelope and soft kernels alone take aux).
+// the envelope, soft and coded kernels alone take aux; the coded kernel's buffer holds int8).
 template <int T, int NSLOT, bool AL, int CH, bool CSI>
 hipError_t go(dim3 grid, hipStream_t st, const TrialParams<Real>& p, hipFuncAttributes* attr, double* out,
               double aux) {
@@ -91,7 +95,9 @@ hipError_t go(dim3 grid, hipStream_t st, const TrialParams<Real>& p, hipFuncAttr
   if (attr) return hipFuncGetAttributes(attr, reinterpret_cast<const void*>(kern));
   // CSI: the per-antenna power table is dynamic LDS, A reals (trial_kernel pw_csi)
   const size_t dyn = CSI ? sizeof(Real) * (size_t)p.n_ant : 0;
-#if INST_MODE == MIMO_MODE_ENV || INST_MODE == MIMO_MODE_SOFT
+#if INST_MODE == MIMO_MODE_CODED
+  hipLaunchKernelGGL(kern, grid, dim3(T), dyn, st, p, reinterpret_cast<int8_t*>(out), aux);
+#elif INST_MODE == MIMO_MODE_ENV || INST_MODE == MIMO_MODE_SOFT
   hipLaunchKernelGGL(kern, grid, dim3(T), dyn, st, p, out, aux);
 #elif INST_MODE
   hipLaunchKernelGGL(kern, grid, dim3(T), dyn, st, p, out);

@@ -45,13 +45,14 @@ enum ChanKind : int { CH_RAYLEIGH = 1, CH_LOS = 2, CH_TWOPATH = 3, CH_TABLE = 4 
 enum RxKind : int { RX_CNC = 1, RX_MCNC = 2 };
 
 // The run mode of the instances a translation unit builds (trial_inst.hip -DINST_MODE=<mode>): one
-// kernel per unit, named and shaped by the mode.  The five row modes are float64 only.
+// kernel per unit, named and shaped by the mode.  The six row modes are float64 only.
 #define MIMO_MODE_PLAIN 0  // trial_kernel: the counts alone
 #define MIMO_MODE_MEAS 1   // trial_kernel_meas
 #define MIMO_MODE_SPEC 2   // trial_kernel_spec
 #define MIMO_MODE_BEAM 3   // trial_kernel_beam
 #define MIMO_MODE_ENV 4    // trial_kernel_env
 #define MIMO_MODE_SOFT 5   // trial_kernel_soft
+#define MIMO_MODE_CODED 6  // trial_kernel_coded
 #ifndef MIMO_INST_MODE
 #define MIMO_INST_MODE MIMO_MODE_PLAIN
 #endif
@@ -122,6 +123,15 @@ __device__ __forceinline__ int env_bin(double pw, double scale) {
 // zeroes again (plain stores, every cell written once, no global atomics).  All of it sits in the
 // receiver phase, outside the antenna loop.  The row pointer and the bin scale 128 / rho_max are
 // extra arguments of that kernel alone.
+
+// Coded instances (MIMO_MODE_CODED): the same trial, the same counts, and per trial and recorded
+// counter index the quantised reliability c (softbits.h coded_value: an odd integer in [-63, 63],
+// include/mimo_engine.h mimo_engine_coded_points) of every Gray bit of every valid slot, taken on the
+// value that index slices, as one int8 at chan[(block n_idx + idx) S 2 hb + j S + k]: bit j of
+// sub-carrier k, the I axis MSB first, then Q.  Plain byte stores from the receiver phase, every cell
+// written once, no LDS and no barrier on top of the plain instance's.  The LDPC decoder (ldpc.hip)
+// reads the buffer after the launch.  The buffer and the scale 32 / rho_max are extra arguments of
+// that kernel alone.
 
 constexpr int kMaxCsiAnt = 512;  // CSI-error runs: antennas (dynamic LDS per team, A doubles; engine.hip checks)
 constexpr uint32_t kFixedCsiTrial = 0xFFFFFFFFu;  // CSI stream counter of fixed-channel runs (oracle/sim.py draws)
@@ -908,6 +918,12 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
                                                                                                   double soft_scale) {
   constexpr double* meas_rows = nullptr;
   constexpr double* spec_rows = nullptr;
+#elif MIMO_INST_MODE == MIMO_MODE_CODED
+__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel_coded(TrialParams<R> p0,
+                                                                                                   int8_t* coded_chan,
+                                                                                                   double coded_scale) {
+  constexpr double* meas_rows = nullptr;
+  constexpr double* spec_rows = nullptr;
 #else
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel(TrialParams<R> p0) {
   constexpr double* meas_rows = nullptr;
@@ -924,12 +940,17 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
   constexpr double* soft_rows = nullptr;
   constexpr double soft_scale = 0.0;
 #endif
+#if MIMO_INST_MODE != MIMO_MODE_CODED
+  constexpr int8_t* coded_chan = nullptr;
+  constexpr double coded_scale = 0.0;
+#endif
   using C = cx<R>;
   constexpr bool MEAS = MIMO_INST_MODE == MIMO_MODE_MEAS && sizeof(R) == 8;
   constexpr bool SPEC = MIMO_INST_MODE == MIMO_MODE_SPEC && sizeof(R) == 8;
   constexpr bool BEAM = MIMO_INST_MODE == MIMO_MODE_BEAM && sizeof(R) == 8;
   constexpr bool ENV = MIMO_INST_MODE == MIMO_MODE_ENV && sizeof(R) == 8;
   constexpr bool SOFT = MIMO_INST_MODE == MIMO_MODE_SOFT && sizeof(R) == 8;
+  constexpr bool CODED = MIMO_INST_MODE == MIMO_MODE_CODED && sizeof(R) == 8;
   // ---- which point and trial this block runs (uniform binary search over point_start)
   uint32_t pi = 0;
   if (p0.n_points > 1) {
@@ -1812,6 +1833,24 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
       __syncthreads();
     }
   };
+  // coded instances: the 2 hb channel values of slot s, whose slicer input is v, to the stream of
+  // counter index idx (valid slots only; only where the index is recorded)
+  auto coded_put = [&](int idx, int s, C v) __attribute__((always_inline)) {
+    if constexpr (CODED) {
+      bool ok;
+      const int k = SL::k_of(s, opaque(tf), S, ok);
+      if (ok) {
+        const uint32_t li = lab[s] >> hb, lq = lab[s] & ((1u << hb) - 1u);
+        int8_t* o = coded_chan + ((size_t)blockIdx.x * (size_t)p0.n_idx + (size_t)idx) * ((size_t)S * (size_t)(2 * hb)) + k;
+        soft_axis((double)v.x, L, hb, [&](int j, double lam) {
+          o[(size_t)(hb - 1 - j) * (size_t)S] = (int8_t)coded_value(lam, (li >> j) & 1u, coded_scale);
+        });
+        soft_axis((double)v.y, L, hb, [&](int j, double lam) {
+          o[(size_t)(2 * hb - 1 - j) * (size_t)S] = (int8_t)coded_value(lam, (lq >> j) & 1u, coded_scale);
+        });
+      }
+    }
+  };
   // |a - b|^2 on a valid slot, 0 off band
   auto err2 = [&](int s, C a, C b) __attribute__((always_inline)) -> R {
     const C e = csub(a, b);
@@ -1836,6 +1875,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
       errs += ((valid_mask >> s) & 1u) ? __popc(lh ^ lab[s]) : 0u;
       if constexpr (MEAS) ee += err2(s, zc, sym);
       soft_add(s, zc);
+      coded_put(0, s, zc);
     }
     measure(kMeasFixed, ee);
     record(0, errs);
@@ -1892,6 +1932,10 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
       if constexpr (SOFT) {
 #pragma unroll
         for (int s = 0; s < NSLOT; ++s) soft_add(s, csub(z[s], dist[s]));
+      }
+      if constexpr (CODED) {
+#pragma unroll
+        for (int s = 0; s < NSLOT; ++s) coded_put(idx, s, csub(z[s], dist[s]));
       }
       measure(kMeasFixed + idx, ee);
       record(idx++, errs);

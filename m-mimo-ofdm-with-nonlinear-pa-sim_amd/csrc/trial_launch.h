@@ -37,8 +37,10 @@ struct InstanceKey {
 // out: the kernel's extra argument -- the measure instances' per-trial rows [grid.x][kMeasFixed +
 // n_idx], the spectrum instances' [grid.x][F + kSpecFixed], the beam instances' cells
 // [2][grid.x][A][F] complex128 (Y sqrt(F), X / sqrt(F)), the envelope instances' rows [grid.x][2 kEnvBins +
-// kEnvFixed], the soft instances' rows [grid.x][n_idx kSoftBins]; the plain instances ignore it.  aux: the
-// envelope instances' bin scale 1.0625 / ref_pow, the soft instances' 128 / rho_max; the others ignore it.
+// kEnvFixed], the soft instances' rows [grid.x][n_idx kSoftBins], the coded instances' channel values [grid.x][n_idx]
+// [S log2 M] int8 (passed through the same pointer); the plain instances ignore it.  aux: the envelope
+// instances' bin scale 1.0625 / ref_pow, the soft instances' 128 / rho_max, the coded instances' 32 / rho_max;
+// the others ignore it.
 template <int F, typename R, int MODE>
 hipError_t launch_trial(const InstanceKey& k, dim3 grid, hipStream_t st, const TrialParams<R>& p, bool* found,
                         hipFuncAttributes* attr, double* out, double aux) = delete;
@@ -54,7 +56,8 @@ hipError_t launch_trial(const InstanceKey& k, dim3 grid, hipStream_t st, const T
   MIMO_DECLARE_LAUNCH_AS(FV, double, MIMO_MODE_SPEC)      \
   MIMO_DECLARE_LAUNCH_AS(FV, double, MIMO_MODE_BEAM)      \
   MIMO_DECLARE_LAUNCH_AS(FV, double, MIMO_MODE_ENV)       \
-  MIMO_DECLARE_LAUNCH_AS(FV, double, MIMO_MODE_SOFT)
+  MIMO_DECLARE_LAUNCH_AS(FV, double, MIMO_MODE_SOFT)      \
+  MIMO_DECLARE_LAUNCH_AS(FV, double, MIMO_MODE_CODED)
 MIMO_DECLARE_LAUNCH(128)
 MIMO_DECLARE_LAUNCH(256)
 MIMO_DECLARE_LAUNCH(512)

@@ -203,3 +203,14 @@
 #ifndef MIMO_SOFT_W64_2048
 #define MIMO_SOFT_W64_2048 2
 #endif
+
+// ---- coded instances (trial_kernel.h CODED; tools/coded_bench.py, profiles/r19/coded/)
+// fp64 F 2048: waves / SIMD the register allocation of the coded instances targets.  Unlike the
+// soft and envelope instances they keep the plain instances' 3: there config 2's instance spills
+// 122 VGPRs against the plain 30 (scratch 144 -> 496 B / lane, profiles/r19/coded/resources.txt)
+// and the kernel takes 0.888 ms per 1,024 trials (CNC iterations 0-4 recorded) against the plain
+// 0.775 (+14.5 %); at 2 (237 VGPRs, none spilled; two 4-wave teams per CU instead of three)
+// 0.929 ms (+19.9 %), medians of alternating rounds (ab_waves.json).
+#ifndef MIMO_CODED_W64_2048
+#define MIMO_CODED_W64_2048 MIMO_W64_2048
+#endif

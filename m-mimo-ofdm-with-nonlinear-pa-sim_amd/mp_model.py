@@ -701,6 +701,38 @@ class Link:
             lambda eng, *args: eng.soft_points(*args, uniq, rho_max, incl_clean_run), need_snr="soft")
         return [_engine.SoftStats(soft[i], rho_max, self.my_mod.constel_size, int(n[i])) for i in range(len(n))]
 
+    # ------------------------------------------------------------------ coded mode
+    def coded(self, incl_clean_run: bool, reroll_chan: bool, cnc_n_iter_lst, seed_arr, n_trials: int, code,
+              rho_max: float = None):
+        """Coded-link errors of the current grid point over trials [0, n_trials) of ``simulate``'s
+        trial sequence: an ``_engine.CodedStats`` -- per counter ([clean] + one per sorted, unique
+        iteration) the uncoded BER at the decoded positions and the BER and frame error rate after
+        the layered min-sum decoder of ``code`` (an ``_engine.LdpcCode``, e.g.
+        ``utilities.qc_ldpc_code``).  ``rho_max=None``: ``32 / nominal_llr_scale()`` as for ``soft``,
+        so that the decoder's 64 input levels cover LLRs to about +-32 at the nominal scale, one
+        LLR unit per level.  A fixed number of trials, no stopping rule."""
+        return self.coded_points(incl_clean_run, reroll_chan, cnc_n_iter_lst, [seed_arr], [self.point_params()],
+                                 n_trials, code, rho_max)[0]
+
+    def coded_points(self, incl_clean_run: bool, reroll_chan: bool, cnc_n_iter_lst, seed_arrs, point_params, n_trials,
+                     code, rho_max: float = None) -> list:
+        """``coded`` for many grid points of this system in one engine call
+        (mimo_engine_coded_points), all quantised over one ``rho_max`` (``None``:
+        ``32 / nominal_llr_scale`` of the point with the most noise, as ``soft_points`` picks it);
+        ``point_params`` as for ``simulate_points``, ``n_trials`` one number or one per point.
+        -> a list of ``_engine.CodedStats``.  Single GPU."""
+        if any(pp["snr_db"] is None for pp in point_params):
+            raise ValueError("set_snr() must be called before coded()")
+        if rho_max is None:
+            rho_max = max([32.0 / self.nominal_llr_scale(pp) for pp in point_params], default=1.0)
+        rho_max = float(rho_max)
+        uniq = sorted(set(int(i) for i in np.asarray(cnc_n_iter_lst, dtype=np.int64).reshape(-1)))
+        n_cw = _engine.coded_codewords(self.my_mod.n_sub_carr, self.my_mod.constel_size, code)
+        (_, _, coded, _, _), n = self._fixed_trials_call(
+            reroll_chan, seed_arrs, point_params, n_trials,
+            lambda eng, *args: eng.coded_points(*args, uniq, code, rho_max, incl_clean_run), need_snr="coded")
+        return [_engine.CodedStats(coded[i], int(n[i]) * n_cw, code.n_bits) for i in range(len(n))]
+
     def update_distortion(self, ibo_val_db: float) -> None:
         """(mp_model.py:230-241)"""
         self.my_array.update_distortion(ibo_db=ibo_val_db, avg_sample_pow=self.my_mod.avg_sample_power)

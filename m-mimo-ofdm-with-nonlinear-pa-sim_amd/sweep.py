@@ -344,6 +344,44 @@ def gmi_vs_ebn0_rows(ebn0_arr, stats):
     return rows
 
 
+def coded_ber_vs_ebn0(link, ibo_arr, ebn0_arr, iters, n_trials, code, seed=2137, incl_clean=False, reroll_chan=True,
+                      rho_max=None):
+    """Coded-link errors for every IBO of ``ibo_arr`` and every Eb/N0 of ``ebn0_arr``: ``n_trials``
+    trials per point decoded with ``code`` (an ``_engine.LdpcCode``), the IBOs of one Eb/N0 in one
+    ``Link.coded_points`` call quantised over one ``rho_max`` (``None``: that Eb/N0's
+    ``32 / nominal_llr_scale``; one GPU; point ``i_ibo len(ebn0_arr) + i_ebn0`` is seeded by
+    ``point_seed`` of that number, run_grid's order).  Eb/N0 counts the transmitted bits: the code's
+    rate is not taken out of it.  -> ``stats[i_ibo][i_ebn0]``, ``_engine.CodedStats``."""
+    m = link.my_mod
+    ibo_arr = np.asarray(ibo_arr, dtype=np.float64)
+    ebn0_arr = np.asarray(ebn0_arr, dtype=np.float64)
+    snr_arr = np.asarray(ebn0_to_snr(ebn0_arr, m.n_sub_carr, m.n_sub_carr, m.constel_size), dtype=np.float64)
+    out = [[None] * len(ebn0_arr) for _ in ibo_arr]
+    for j, snr in enumerate(snr_arr):
+        link.set_snr(float(snr))
+        params, seeds = [], []
+        for i, ibo in enumerate(ibo_arr):
+            link.update_distortion(ibo_val_db=float(ibo))
+            params.append(dict(link.point_params()))
+            seeds.append(point_seed(seed, i * len(ebn0_arr) + j))
+        for i, st in enumerate(link.coded_points(incl_clean, reroll_chan, iters, seeds, params, n_trials, code,
+                                                 rho_max)):
+            out[i][j] = st
+    return out
+
+
+def coded_ber_vs_ebn0_rows(ebn0_arr, stats):
+    """CSV rows of one IBO of the coded sweep (``stats``: its CodedStats per Eb/N0): the Eb/N0 axis,
+    then per counter index four rows -- the uncoded BER at the decoded positions, the BER after the
+    decoder, the frame error rate and the share of frames the parity checks flag."""
+    rows = [np.asarray(ebn0_arr, dtype=np.float64)]
+    cols = [np.asarray([f(st) for st in stats]) for f in (lambda st: st.raw_ber(), lambda st: st.ber(),
+                                                         lambda st: st.fer(), lambda st: st.syndrome_rate())]
+    for k in range(cols[0].shape[1]):
+        rows += [c[:, k] for c in cols]
+    return rows
+
+
 def beam_vs_angle(link, angles_deg, ibo_arr, n_trials, seed=2137, reroll_chan=True, radius=None, z=None):
     """Beampattern of the array over ``angles_deg`` for every IBO of ``ibo_arr``: probes on the
     horizontal circle around the origin through the user (``radius``, ``z``: the link's nominal
@@ -448,7 +486,7 @@ def _build_link(args, device):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--grid", choices=["ber_vs_ebn0", "fixed_ber", "sdr_vs_ibo", "psd_vs_ibo", "beam_vs_angle",
-                                       "ccdf_vs_ibo", "gmi_vs_ebn0"],
+                                       "ccdf_vs_ibo", "gmi_vs_ebn0", "coded_ber_vs_ebn0"],
                     default="fixed_ber",
                     help="sdr_vs_ibo: measured in-band SDR and per-iteration signal-to-error ratio per IBO "
                          "(--n-trials trials per point at the first --ebn0 value; one GPU).  psd_vs_ibo: the "
@@ -461,7 +499,12 @@ def main():
                          "one GPU).  gmi_vs_ebn0: per IBO and Eb/N0 the BER, the bit-wise mutual information "
                          "(GMI) of the demapper's soft outputs at its best LLR scale, that scale and the "
                          "achievable rate, per recorded iteration (--n-trials trials per point; one GPU; like the "
-                         "other row grids without the clean index, which sweep.gmi_vs_ebn0(incl_clean=True) adds)")
+                         "other row grids without the clean index, which sweep.gmi_vs_ebn0(incl_clean=True) adds).  "
+                         "coded_ber_vs_ebn0: per IBO and Eb/N0 the uncoded BER, the BER and frame error rate after a "
+                         "layered min-sum LDPC decoder and the share of flagged frames, per recorded iteration, "
+                         "with the stand-in code of --ldpc (--n-trials trials per point; one GPU)")
+    ap.add_argument("--ldpc", type=str, default="128,4,8,10",
+                    help="coded_ber_vs_ebn0: z,n_rows,n_cols,n_dec_iters of utilities.qc_ldpc_code (seed 0)")
     ap.add_argument("--angles", type=str, default="0:180.1:1", help="beam_vs_angle: start:stop:step [deg]")
     ap.add_argument("--n-ant", type=int, default=64)
     ap.add_argument("--n-sc", type=int, default=2048)
@@ -481,7 +524,8 @@ def main():
     ap.add_argument("--n-err-min", type=int, default=int(1e5))
     ap.add_argument("--seed", type=int, default=2137)
     ap.add_argument("--n-trials", type=int, default=4096,
-                    help="sdr_vs_ibo, psd_vs_ibo, beam_vs_angle, ccdf_vs_ibo, gmi_vs_ebn0: trials per point")
+                    help="sdr_vs_ibo, psd_vs_ibo, beam_vs_angle, ccdf_vs_ibo, gmi_vs_ebn0, coded_ber_vs_ebn0: trials "
+                         "per point")
     ap.add_argument("--out", type=str, default="figs/csv_results")
     ap.add_argument("--split", choices=["points", "trials", "auto"], default="auto",
                     help="ranks deal whole points by cost (one all-reduce at the end), or share every point's "
@@ -567,6 +611,23 @@ def main():
                 "_".join(str(v) for v in iters))
             save_to_csv(gmi_vs_ebn0_rows(ebn0_arr, stats[i]), name, directory=args.out)
         print(f"gmi sweep done: {len(ibo_arr)} IBO x {len(ebn0_arr)} Eb/N0 points x {args.n_trials} trials in "
+              f"{time.perf_counter() - t0:.1f} s -> {args.out}")
+        return
+    if args.grid == "coded_ber_vs_ebn0":
+        if world > 1:
+            raise SystemExit("--grid coded_ber_vs_ebn0 runs on one GPU")
+        from utilities import qc_ldpc_code
+        z, n_rows, n_cols, n_dec = (int(v) for v in args.ldpc.split(","))
+        code = qc_ldpc_code(z, n_rows, n_cols, n_dec)
+        t0 = time.perf_counter()
+        stats = coded_ber_vs_ebn0(link, ibo_arr, ebn0_arr, iters, args.n_trials, code, args.seed)
+        for i, ibo in enumerate(ibo_arr):
+            name = "coded_ber_vs_ebn0_%s_%s_nant%d_ibo%1.2f_ebn0_min%d_max%d_step%1.2f_ntrials%d_z%d_%dx%d_dec%d_niter%s" % (
+                args.receiver, args.channel, args.n_ant, ibo, min(ebn0_arr), max(ebn0_arr),
+                ebn0_arr[1] - ebn0_arr[0] if len(ebn0_arr) > 1 else 0.0, args.n_trials, z, n_rows, n_cols, n_dec,
+                "_".join(str(v) for v in iters))
+            save_to_csv(coded_ber_vs_ebn0_rows(ebn0_arr, stats[i]), name, directory=args.out)
+        print(f"coded sweep done: {len(ibo_arr)} IBO x {len(ebn0_arr)} Eb/N0 points x {args.n_trials} trials in "
               f"{time.perf_counter() - t0:.1f} s -> {args.out}")
         return
     t0 = time.perf_counter()

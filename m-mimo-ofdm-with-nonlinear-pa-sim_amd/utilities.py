@@ -111,6 +111,30 @@ def to_time_domain(in_sig_mat_fd: ndarray) -> ndarray:
     return _engine.fft(np.asarray(in_sig_mat_fd), inverse=True)
 
 
+def qc_ldpc_code(z: int, n_rows: int, n_cols: int, n_dec_iters: int = 10, seed: int = 0):
+    """A deterministic QC-LDPC code for the coded mode (``_engine.LdpcCode``): lifting size ``z``, a
+    base matrix of ``n_rows`` x ``n_cols`` blocks, every block a shifted identity (none empty), and no
+    4-cycles.  With ``g = np.random.default_rng(seed)``, column by column ``g.integers(0, z, n_rows)``
+    is drawn up to 1,000 times and the first draw is kept for which
+    ``(s[r1, c0] - col[r1] + col[r2] - s[r2, c0]) % z != 0`` for every earlier column ``c0`` and every
+    pair of rows ``r1 < r2``; ``ValueError`` if none is.  No standard's table: a stand-in of the same
+    structure for anyone who has none at hand."""
+    z, n_rows, n_cols = int(z), int(n_rows), int(n_cols)
+    g = np.random.default_rng(seed)
+    s = np.zeros((n_rows, n_cols), dtype=np.int64)
+    r1, r2 = np.triu_indices(n_rows, 1)
+    for c in range(n_cols):
+        for _ in range(1000):
+            col = g.integers(0, z, n_rows)
+            d = (s[r1, :c] - col[r1, None] + col[r2, None] - s[r2, :c]) % z
+            if np.all(d != 0):
+                s[:, c] = col
+                break
+        else:
+            raise ValueError(f"no 4-cycle-free column {c} for z {z}, {n_rows} x {n_cols} within 1,000 draws")
+    return _engine.LdpcCode(z, s, n_dec_iters)
+
+
 def save_to_csv(data_lst: list, filename: str, directory: str = "figs/csv_results") -> None:
     """One row per vector, ``csv.writer.writerows`` (utilities.py:342-352); the reference
     writes to ``figs/csv_results`` relative to the working directory."""
