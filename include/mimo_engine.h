@@ -20,6 +20,9 @@
  *                                  per counter index (BICM GMI / achievable rate per CNC / MCNC iteration)
  *     mimo_engine_coded_points     the same trials with the bit and frame errors of an LDPC-coded link after
  *                                  a layered min-sum decoder, per counter index (coded BER / FER per iteration)
+ *     mimo_engine_set_channel_bank  a table engine's bank of channel matrices, one per trial (snapshots)
+ *     mimo_engine_set_tdl           the power-delay profile of a tapped-delay-line Rayleigh channel, drawn
+ *                                   per trial on the device (frequency-selective fading)
  *     mimo_engine_run_points    <- the drivers' grid loops over (IBO, Eb/N0), one launch
  *                                  for many points   main_mp_miso_cnc_constant_ber_req_ebn0_vs_ibo.py:100-215
  *   fine seams (float64 stage kernels, caller-owned host arrays)
@@ -35,6 +38,7 @@
  *     mimo_mrt_precode          <- AntennaArray.set_precoding_matrix   antenna_array.py:162-185
  *     mimo_combine              <- Miso*Fd.propagate                   channel.py:74-89,277-292
  *     mimo_awgn                 <- Awgn.process                        noise.py:45-83
+ *     mimo_tdl_channels            the TDL engine's channel realisations (no reference entry point)
  *     mimo_count_bit_errors     <- utilities.count_mismatched_bits     utilities.py:94-104
  *     mimo_cnc_receive          <- CncReceiver.receive                 corrector.py:52-112
  *     mimo_cnc_receive_ex       <- CncReceiver.receive(return_bits=False) corrector.py:80-84
@@ -58,7 +62,7 @@ extern "C" {
 
 enum { MIMO_OK = 0, MIMO_EINVAL = -1, MIMO_EHIP = -2, MIMO_ENOKERNEL = -3, MIMO_ENOMEM = -4 };
 enum { MIMO_PA_NONE = 0, MIMO_PA_SOFTLIM = 1, MIMO_PA_RAPP = 2, MIMO_PA_TOI = 3 };
-enum { MIMO_CH_RAYLEIGH = 1, MIMO_CH_LOS = 2, MIMO_CH_TWOPATH = 3, MIMO_CH_TABLE = 4 };
+enum { MIMO_CH_RAYLEIGH = 1, MIMO_CH_LOS = 2, MIMO_CH_TWOPATH = 3, MIMO_CH_TABLE = 4, MIMO_CH_TDL = 5 };
 enum { MIMO_RX_CNC = 1, MIMO_RX_MCNC = 2 };
 enum { MIMO_PREC_F64 = 0, MIMO_PREC_F32 = 1 };
 
@@ -87,7 +91,10 @@ typedef struct mimo_config {
   int32_t n_fft;            /* FFT size F: power of two, 128 ... 8192               */
   int32_t constel_size;     /* square QAM order M (4 ... 4096)                      */
   int32_t cp_len;           /* cyclic prefix (BER-neutral: memoryless PA, circular channel) */
-  int32_t channel_kind;     /* MIMO_CH_* (TABLE: a fixed matrix, see chan_table)     */
+  int32_t channel_kind;     /* MIMO_CH_* (TABLE: a fixed matrix, see chan_table, or a bank of them,
+                               mimo_engine_set_channel_bank; TDL: a tapped-delay-line Rayleigh channel
+                               per trial, mimo_engine_set_tdl -- reroll_chan must be 1 and chan_table
+                               is not read)                                           */
   int32_t receiver_kind;    /* MIMO_RX_*                                            */
   int32_t device;           /* HIP device ordinal, -1 = current                      */
   double rx_pos[3];         /* nominal RX position [m]                               */
@@ -410,12 +417,71 @@ int32_t mimo_engine_coded_points(mimo_engine* e, int32_t n_points, const mimo_po
                                  int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
                                  uint32_t* per_trial, const mimo_ldpc_code* code, double rho_max, double* coded_out,
                                  double* per_trial_coded, int8_t* per_trial_chan);
+/* Channel bank (MIMO_CH_TABLE engines): many channel matrices on the device, one per trial.
+ * tables is [n_bank][n_ant][n_fft] complex, each entry in chan_table's layout.  From then on trial i
+ * (the absolute index, first_trial + offset) of mimo_engine_run and of every *_points call uses
+ * table i mod n_bank.  n_bank = 0: back to the create-time table.  The tables are copied, their
+ * in-band columns only (as mimo_engine_create keeps chan_table's), and uploaded at the next run: no
+ * HIP call happens here.  A float32 engine stores float2, rounded to nearest.  The bank lives in a
+ * device buffer of at most MIMO_BANK_BUFFER_BYTES (a design figure), so it holds
+ * mimo_bank_capacity entries: 1,024 at n_ant 64, n_sub_carr 1024 in float64.  MIMO_EINVAL, with a
+ * message naming the field: an engine that is not MIMO_CH_TABLE; null tables with n_bank > 0; a value
+ * that is not finite (the message names the entry and the antenna); n_bank < 0 or above
+ * mimo_bank_capacity.  One shared estimate per table is the table engine's CSI-error rule, and
+ * per-entry estimates are not built: any run on an engine with n_bank > 1 whose points have
+ * csi_eps >= 0 is MIMO_EINVAL, before any HIP call.  (Added within ABI 8: a library without it is
+ * reported by name.) */
+#define MIMO_BANK_BUFFER_BYTES (1ull << 30)
+/* entries that fit: floor(MIMO_BANK_BUFFER_BYTES / (n_ant n_sub_carr (16 | 8 bytes))); host only,
+ * MIMO_EINVAL for n_ant < 1, n_sub_carr < 1 or an unknown precision */
+int64_t mimo_bank_capacity(int32_t n_ant, int32_t n_sub_carr, int32_t precision);
+int32_t mimo_engine_set_channel_bank(mimo_engine* e, int32_t n_bank, const double* tables);
+/* Tapped-delay-line (TDL) Rayleigh channel (MIMO_CH_TDL engines): a frequency-selective channel
+ * drawn per trial and antenna from a caller-given power-delay profile.
+ *  Taps: tap l < L of antenna a in trial i under the key seed:
+ *   (w0, w1, ., .) = Philox4x32-10 of counter (l, i mod 2^32, 7, a) (stream 7; stream 6 is mimo_awgn's),
+ *   u1 = (w0 + 0.5) 2^-32, u2 = w1 2^-32,
+ *   g[a][l] = ant_amp[a] sqrt(powers[l]) sqrt(-ln u1) exp(j 2 pi u2)         (mimo_awgn's formula)
+ *   -- a CN(0, ant_amp[a]^2 powers[l]) draw; the powers are used as given, not normalised.
+ *  Frequency response at FFT bin n (numpy.fft order, bin 0 = the centre frequency):
+ *   H[a][n] = sum_l g[a][l] W[(n delays[l]) mod n_fft],  summed in ascending l from 0,
+ *   W[m] = exp(-j 2 pi m / n_fft) from a table the host builds once in double, W[0] = (1, -0.0 or
+ *   0.0) exactly: a single tap at delay 0 gives H[a][n] = g[a][0] bit for bit.
+ *  Engine: it selects the table instances of the trial kernel and needs a profile before its first
+ *   run (MIMO_EINVAL without one); reroll_chan = 0 is refused by mimo_engine_create (a fixed channel
+ *   is a table).  Before every trial-kernel launch of every call a generator kernel fills bank entry
+ *   b with the realisation of the (point seed, trial) of the launch's block b, in-band columns only,
+ *   in device memory; a float32 engine stores the values rounded to nearest.  A launch therefore
+ *   holds at most mimo_bank_capacity trials and longer calls split; per-trial rows and counts do not
+ *   depend on where.  Points with csi_eps >= 0 are MIMO_EINVAL, before any HIP call.
+ *  mimo_engine_set_tdl copies the profile (no HIP call).  MIMO_EINVAL, with a message naming the
+ *   field: an engine that is not MIMO_CH_TDL, a null profile, delays or powers, n_taps outside
+ *   [1, 64], delays that are not strictly ascending in [0, n_fft), a power or an amplitude that is
+ *   not finite and > 0.
+ *  mimo_tdl_channels is the fine seam: the same realisations, by the same device function, on host
+ *   arrays.  h_out is [n][n_ant][n_fft] complex, trial first_trial + j at h_out[j]; taps_out, optional,
+ *   [n][n_ant][L] complex.  n_fft a power of two in [2, 8192], n_ant >= 1, n >= 0 (n = 0: MIMO_OK,
+ *   nothing written); a null h_out is MIMO_EINVAL.
+ * (Added within ABI 8: a library without them is reported by name.) */
+typedef struct mimo_tdl {
+  int32_t n_taps;          /* L, 1 ... 64 */
+  const int32_t* delays;   /* [L] whole samples, strictly ascending, 0 <= d < n_fft */
+  const double* powers;    /* [L] linear, finite and > 0 (used as given, not normalised) */
+  const double* ant_amp;   /* [n_ant] amplitude per antenna, finite and > 0; NULL = 1 */
+} mimo_tdl;
+enum { MIMO_TDL_MAX_TAPS = 64 };
+int32_t mimo_engine_set_tdl(mimo_engine* e, const mimo_tdl* prof);
+int32_t mimo_tdl_channels(const mimo_tdl* prof, int32_t n_ant, int32_t n_fft, uint64_t seed, uint64_t first_trial,
+                          int64_t n, double* h_out, double* taps_out);
 /* Device time of the trial kernels of the last run, in ms (HIP events on the engine stream). */
 double mimo_engine_last_kernel_ms(const mimo_engine* e);
 /* ... and of the beamforming kernels of the last beam call (0 after any other call). */
 double mimo_engine_last_beam_ms(const mimo_engine* e);
 /* ... and of the decoder kernels of the last coded call (0 after any other call). */
 double mimo_engine_last_decode_ms(const mimo_engine* e);
+/* ... and of the TDL generator kernels of the last call on a MIMO_CH_TDL engine (0 on any other);
+ * an event pair of its own: mimo_engine_last_kernel_ms does not include it. */
+double mimo_engine_last_chan_ms(const mimo_engine* e);
 /* Which kernel instance the current config selects: "F=2048 T=128 slots=8 aligned ..." */
 const char* mimo_engine_describe(const mimo_engine* e);
 void mimo_engine_destroy(mimo_engine* e);

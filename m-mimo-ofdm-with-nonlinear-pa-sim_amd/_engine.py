@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MIMO_LIB") or os.path.join(_HERE, "libmimo_engine.so")
 
 PA_KINDS = {"none": 0, "softlim": 1, "rapp": 2, "toi": 3}
-CH_KINDS = {"rayleigh": 1, "los": 2, "two_path": 3, "table": 4}
+CH_KINDS = {"rayleigh": 1, "los": 2, "two_path": 3, "table": 4, "tdl": 5}
 RX_KINDS = {"cnc": 1, "mcnc": 2}
 # Arithmetic type of the fused kernel: "f64" is the reference's own precision (complex128 /
 # float64, the default); "f32" is the fast variant.  MIMO_PRECISION overrides the default.
@@ -81,6 +81,26 @@ class LdpcCode(ctypes.Structure):
         return LdpcCode(self.z, self.table, n_dec_iters)
 
 
+class TdlProfile(ctypes.Structure):
+    """mimo_tdl: a power-delay profile.  ``TdlProfile(delays, powers, ant_amp=None)``: whole-sample
+    delays (strictly ascending), linear powers (used as given) and, optionally, one amplitude per
+    antenna (None: 1).  The arrays stay with the object; the rules are the library's to check."""
+    _fields_ = [("n_taps", ctypes.c_int32), ("delays", _i32p), ("powers", _dp), ("ant_amp", _dp)]
+
+    def __init__(self, delays, powers, ant_amp=None):
+        d = np.asarray(delays)
+        if d.ndim != 1 or np.asarray(powers).shape != d.shape:
+            raise ValueError("delays and powers must be one-dimensional and of equal length")
+        if d.size and (np.any(d != np.floor(d)) or d.min() < -2 ** 31 or d.max() >= 2 ** 31):
+            raise ValueError("delays must be whole samples that fit int32")
+        self.delays_arr = np.ascontiguousarray(d, dtype=np.int32)
+        self.powers_arr = np.ascontiguousarray(powers, dtype=np.float64)
+        self.amp_arr = None if ant_amp is None else np.ascontiguousarray(ant_amp, dtype=np.float64).reshape(-1)
+        super().__init__(n_taps=int(d.size), delays=self.delays_arr.ctypes.data_as(_i32p),
+                         powers=self.powers_arr.ctypes.data_as(_dp),
+                         ant_amp=self.amp_arr.ctypes.data_as(_dp) if self.amp_arr is not None else None)
+
+
 SYMBOLS = {
     "mimo_abi_version": (ctypes.c_int32, []),
     "mimo_last_error": (ctypes.c_char_p, []),
@@ -119,6 +139,12 @@ SYMBOLS = {
                                                   _u64p, _u64p, _i32p, ctypes.c_int32, ctypes.c_int32, _u64p, _u64p,
                                                   _u32p, ctypes.POINTER(LdpcCode), ctypes.c_double, _dp, _dp, _i8p]),
     "mimo_engine_last_decode_ms": (ctypes.c_double, [ctypes.c_void_p]),
+    "mimo_bank_capacity": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "mimo_engine_set_channel_bank": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, _dp]),
+    "mimo_engine_set_tdl": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(TdlProfile)]),
+    "mimo_tdl_channels": (ctypes.c_int32, [ctypes.POINTER(TdlProfile), ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
+                                           ctypes.c_uint64, ctypes.c_int64, _dp, _dp]),
+    "mimo_engine_last_chan_ms": (ctypes.c_double, [ctypes.c_void_p]),
     "mimo_ldpc_decode": (ctypes.c_int32, [ctypes.POINTER(LdpcCode), _i8p, ctypes.c_int64, _i16p]),
     "mimo_engine_last_kernel_ms": (ctypes.c_double, [ctypes.c_void_p]),
     "mimo_engine_last_beam_ms": (ctypes.c_double, [ctypes.c_void_p]),
@@ -162,6 +188,7 @@ ENV_FIXED = 4    # include/mimo_engine.h MIMO_ENV_FIXED
 ENV_WIDTH = 2 * ENV_BINS + ENV_FIXED
 SOFT_BINS = 256  # include/mimo_engine.h MIMO_SOFT_BINS
 CODED_FIXED = 4  # include/mimo_engine.h MIMO_CODED_FIXED
+TDL_MAX_TAPS = 64  # include/mimo_engine.h MIMO_TDL_MAX_TAPS
 
 
 def lib():
@@ -951,6 +978,33 @@ class Engine:
         return (out[0][0], out[1][0], out[2][0]) + tuple(out[3:])
 
     @property
+    def chan_kernel_ms(self):
+        """Device time of the TDL generator kernels of the last call [ms] (0 unless channel="tdl")."""
+        return self._L.mimo_engine_last_chan_ms(self._h)
+
+    def set_channel_bank(self, tables):
+        """A channel bank for a ``channel="table"`` engine (mimo_engine_set_channel_bank): ``tables``
+        [n_bank, n_ant, n_fft] complex, and from then on trial i of every run uses table
+        ``i % n_bank``.  ``None`` or an empty bank: back to the create-time table.  Copied; uploaded
+        at the next run."""
+        if tables is None:
+            tab = np.zeros((0, self.n_ant, self.n_fft), np.complex128)
+        else:
+            tab = np.asarray(tables, dtype=np.complex128)
+        if tab.ndim != 3 or tab.shape[1:] != (self.n_ant, self.n_fft):
+            raise ValueError("tables must be [n_bank, n_ant, n_fft] channel matrices")
+        iq = np.ascontiguousarray(tab).view(np.float64)
+        _check(self._L.mimo_engine_set_channel_bank(self._h, tab.shape[0], _ptr(iq, ctypes.c_double) if tab.size else None))
+
+    def set_tdl(self, delays, powers, ant_amp=None):
+        """The power-delay profile of a ``channel="tdl"`` engine (mimo_engine_set_tdl): whole-sample
+        ``delays``, linear ``powers`` and, optionally, an amplitude per antenna.  Copied."""
+        if ant_amp is not None and np.size(ant_amp) != self.n_ant:
+            raise ValueError("ant_amp must hold n_ant amplitudes")
+        prof = TdlProfile(delays, powers, ant_amp)
+        _check(self._L.mimo_engine_set_tdl(self._h, ctypes.byref(prof)))
+
+    @property
     def decode_kernel_ms(self):
         """Device time of the decoder kernels of the last coded call (0 after any other call)."""
         return self._L.mimo_engine_last_decode_ms(self._h)
@@ -1048,6 +1102,31 @@ def ldpc_decode(code, chan):
     out = np.zeros(c.size, np.int16)
     _check(lib().mimo_ldpc_decode(ctypes.byref(code), _ptr(c, ctypes.c_int8), n_cw, _ptr(out, ctypes.c_int16)))
     return out.reshape(n_cw, n) if n > 0 else out
+
+
+def bank_capacity(n_ant, n_sub_carr, precision="f64"):
+    """Entries a channel bank holds (mimo_bank_capacity): what fits MIMO_BANK_BUFFER_BYTES; also
+    the trials of one launch of a ``channel="tdl"`` engine.  Host only."""
+    n = lib().mimo_bank_capacity(int(n_ant), int(n_sub_carr), PRECISIONS[precision])
+    if n < 0:
+        raise ValueError(lib().mimo_last_error().decode())
+    return int(n)
+
+
+def tdl_channels(delays, powers, n_ant, n_fft, seed, first_trial, n, ant_amp=None, taps=False):
+    """The TDL engine's channel realisations on host arrays (mimo_tdl_channels): trials
+    ``first_trial ... first_trial + n - 1`` under the key ``seed``, by the engine's own generator.
+    -> H [n, n_ant, n_fft] complex (numpy.fft bin order), with ``taps=True`` (H, taps [n, n_ant, L])."""
+    if ant_amp is not None and np.size(ant_amp) != n_ant:
+        raise ValueError("ant_amp must hold n_ant amplitudes")
+    prof = TdlProfile(delays, powers, ant_amp)
+    n = int(n)
+    h = np.zeros((max(n, 0), n_ant, n_fft), np.complex128)
+    g = np.zeros((max(n, 0), n_ant, prof.n_taps), np.complex128) if taps else None
+    _check(lib().mimo_tdl_channels(ctypes.byref(prof), int(n_ant), int(n_fft), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                   int(first_trial) & 0xFFFFFFFFFFFFFFFF, n, _ptr(h.view(np.float64), ctypes.c_double),
+                                   _ptr(g.view(np.float64), ctypes.c_double) if taps else None))
+    return (h, g) if taps else h
 
 
 def fft(x, inverse=False):

@@ -23,6 +23,7 @@
 #include "beam.h"
 #endif
 #include "ldpc.h"
+#include "tdl.h"
 
 namespace {
 
@@ -150,6 +151,20 @@ struct mimo_engine {
   mimo_config cfg{};
   std::vector<double> tx_pos, freqs;
   std::vector<double> chan_inband;        // MIMO_CH_TABLE: [A][S] (re, im), sub-carrier order k
+  // MIMO_CH_TABLE with a channel bank (mimo_engine_set_channel_bank): the in-band columns of its
+  // n_bank tables, [n_bank][A][S] in the engine's precision alone (a bank may fill 1 GiB), and
+  // whether the device copy behind tab64 / tab32 is still to be replaced (at the next run)
+  int n_bank = 0;
+  std::vector<double2> bank64;
+  std::vector<float2> bank32;
+  bool tab_stale = false;
+  // MIMO_CH_TDL: the profile (mimo_engine_set_tdl), its device tables (tdl.h TdlHost::blob) and
+  // whether those are still to be uploaded.  The generator fills tab64 / tab32 launch by launch.
+  bool have_tdl = false;
+  mimo::TdlHost tdl;
+  bool tdl_stale = false;
+  Buf<double> tdl_blob;
+  double last_chan_ms = 0.0;
   mimo_point pt{};
   bool have_point = false;
   // device state (created lazily on the first run: fork safety); whatever of it exists is released
@@ -159,6 +174,7 @@ struct mimo_engine {
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipEvent_t ev2 = nullptr;               // after the beamforming / decoder kernel of a launch
+  hipEvent_t ev3 = nullptr;               // ahead of the TDL generator kernel of a launch (ev0 follows it)
   Buf<float2> tw[2];                      // fp32 stage twiddles for team_size(F), alt_team_size(F)
   Buf<double2> tw64;                      // fp64 stage twiddles for team_size64(F)
   Buf<double2> twave64;                   // wave-split FFT twiddles (wave_fft.h) where the instance uses it
@@ -201,7 +217,7 @@ struct mimo_engine {
   // (the buffers free themselves after this; no HIP call for an engine that never ran)
   ~mimo_engine() {
     if (stream) (void)hipStreamSynchronize(stream);
-    for (hipEvent_t ev : {ev0, ev1, ev2})
+    for (hipEvent_t ev : {ev0, ev1, ev2, ev3})
       if (ev) (void)hipEventDestroy(ev);
     if (stream) (void)hipStreamDestroy(stream);
   }
@@ -239,7 +255,8 @@ mimo::InstanceKey select_instance(const mimo_engine* e, bool csi) {
   const int P = k.F / k.T;
   k.aligned = aligned_at(k.T);
   k.nslot = k.aligned ? S / k.T : P;
-  k.ch = e->cfg.channel_kind;
+  // (a TDL engine runs the table instances on the bank its generator fills)
+  k.ch = e->cfg.channel_kind == MIMO_CH_TDL ? MIMO_CH_TABLE : e->cfg.channel_kind;
   k.csi = csi;
   return k;
 }
@@ -351,8 +368,10 @@ int validate_config(const mimo_config* c) {
   if (L * L != c->constel_size || !is_pow2(c->constel_size) || c->constel_size < 4 || c->constel_size > 4096)
     return fail(MIMO_EINVAL, "Constellation size must be a power of some number, only square QAM supported.");
   if (c->n_ant < 1 || c->n_ant > 4096) return fail(MIMO_EINVAL, "n_ant must be in [1, 4096]");
-  if (c->channel_kind < MIMO_CH_RAYLEIGH || c->channel_kind > MIMO_CH_TABLE)
+  if (c->channel_kind < MIMO_CH_RAYLEIGH || c->channel_kind > MIMO_CH_TDL)
     return fail(MIMO_EINVAL, "unknown channel_kind");
+  if (c->channel_kind == MIMO_CH_TDL && !c->reroll_chan)
+    return fail(MIMO_EINVAL, "reroll_chan = 0 is not a MIMO_CH_TDL engine: a fixed channel is a table (MIMO_CH_TABLE)");
   if (c->channel_kind == MIMO_CH_TABLE && !c->chan_table)
     return fail(MIMO_EINVAL, "chan_table is required for MIMO_CH_TABLE");
   if (c->receiver_kind != MIMO_RX_CNC && c->receiver_kind != MIMO_RX_MCNC)
@@ -386,10 +405,10 @@ int validate_config(const mimo_config* c) {
 // engine that is only created, described or given points may hold any finite positions): the
 // Rayleigh attenuation's, from the nominal RX, and for LoS / two-path the centre the jitter is
 // drawn around, (rx_pos[0], rx_pos[0], rx_pos[2]) (mp_model.py:192-199 uses rx_loc_x for the y
-// coordinate too).  Table channels read no position.
+// coordinate too).  Table and TDL channels read no position.
 int validate_distances(const mimo_engine* e) {
   const mimo_config& c = e->cfg;
-  if (c.channel_kind == MIMO_CH_TABLE) return MIMO_OK;
+  if (c.channel_kind == MIMO_CH_TABLE || c.channel_kind == MIMO_CH_TDL) return MIMO_OK;
   const bool moves = c.channel_kind == MIMO_CH_LOS || c.channel_kind == MIMO_CH_TWOPATH;
   // (the distance as ensure_device forms it: one that rounds to 0 or overflows is refused too)
   auto no_distance = [](const double* t, double x, double y, double z) {
@@ -496,7 +515,7 @@ int ensure_device(mimo_engine* e) {
   if (e->cfg.device >= 0) HIP_TRY(hipSetDevice(e->cfg.device));
   HIP_TRY(hipGetDevice(&e->device));
   if (!e->stream) HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-  for (hipEvent_t* ev : {&e->ev0, &e->ev1, &e->ev2})
+  for (hipEvent_t* ev : {&e->ev0, &e->ev1, &e->ev2, &e->ev3})
     if (!*ev) HIP_TRY(hipEventCreate(ev));
   const int F = e->cfg.n_fft, S = e->cfg.n_sub_carr, A = e->cfg.n_ant;
   // the FFT tables (host_tables.h): the team FFT's per team size, the split FFT's in place of
@@ -521,8 +540,9 @@ int ensure_device(mimo_engine* e) {
   const double fc = e->freqs[0];  // bin 0 = centre frequency
   for (int k = 0; k < S; ++k) {
     const double f = e->freqs[band_bin(k, S, F)];
-    // table channels carry their full attenuation: nothing is factored out of the loops
-    f_rel64[k] = e->cfg.channel_kind == MIMO_CH_TABLE ? 1.0 : fc / f;
+    // table and TDL channels carry their full attenuation: nothing is factored out of the loops
+    const bool whole = e->cfg.channel_kind == MIMO_CH_TABLE || e->cfg.channel_kind == MIMO_CH_TDL;
+    f_rel64[k] = whole ? 1.0 : fc / f;
     f_rel[k] = (float)f_rel64[k];
     f_over_c[k] = f / kSpeedOfLight;
   }
@@ -569,6 +589,34 @@ int ensure_device(mimo_engine* e) {
   up(e->tx_pos_dev, e->tx_pos);
   if (rc) return rc;
   e->ready = true;
+  return MIMO_OK;
+}
+
+// What the setters changed since the last run, uploaded before this one (the setters make no HIP
+// call): the channel bank of a table engine in the engine's precision -- or, back at n_bank = 0,
+// the create-time table -- and a TDL engine's profile tables.
+int refresh_channel_tables(mimo_engine* e) {
+  if (!e->tab_stale && !e->tdl_stale) return MIMO_OK;
+  HIP_TRY(hipStreamSynchronize(e->stream));  // no launch of a call that failed half-way still reads them
+  if (e->tab_stale) {
+    if (e->n_bank > 0) {
+      if (int rc = e->cfg.precision == MIMO_PREC_F32 ? e->tab32.upload(e->bank32) : e->tab64.upload(e->bank64)) return rc;
+    } else {
+      std::vector<float2> tab32;
+      std::vector<double2> tab64;
+      for (size_t i = 0; i < e->chan_inband.size() / 2; ++i) {
+        tab64.push_back(make_double2(e->chan_inband[2 * i], e->chan_inband[2 * i + 1]));
+        tab32.push_back(make_float2((float)e->chan_inband[2 * i], (float)e->chan_inband[2 * i + 1]));
+      }
+      if (int rc = e->tab32.upload(tab32)) return rc;
+      if (int rc = e->tab64.upload(tab64)) return rc;
+    }
+    e->tab_stale = false;
+  }
+  if (e->tdl_stale) {
+    if (int rc = e->tdl_blob.upload(e->tdl.blob())) return rc;
+    e->tdl_stale = false;
+  }
   return MIMO_OK;
 }
 
@@ -772,20 +820,25 @@ mimo::TrialParams<R> base_params(const mimo_engine* e, const mimo::InstanceKey& 
 #endif
   base.counts = e->counts.p;
   base.chan_period = (uint32_t)std::max(0, c.chan_replay_period);
+  // table instances: the entries of the bank behind chan_tab (trial_kernel.h ch_trial); a TDL
+  // engine's 0 gives every block of a launch the entry its generator filled for it
+  if (c.channel_kind == MIMO_CH_TABLE) base.chan_period = (uint32_t)std::max(1, e->n_bank);
   return base;
 }
 
 // Byte offsets of the per-launch tables in the blob (mimo_engine::blob), each 16-byte aligned.
+// (tdl: the TDL generator's segment table, TdlSeg [segments], behind the others on a TDL engine)
 struct BlobLayout {
-  size_t start, slice, point_of, bytes;
+  size_t start, slice, point_of, tdl, bytes;
 };
-BlobLayout blob_layout(const Plan& plan, size_t params_bytes) {
+BlobLayout blob_layout(const Plan& plan, size_t params_bytes, bool tdl) {
   auto up16 = [](size_t b) { return (b + 15) & ~size_t(15); };
   BlobLayout o{};
   o.start = up16(plan.max_seg * params_bytes);
   o.slice = o.start + up16((plan.max_seg + 1) * sizeof(uint32_t));
   o.point_of = o.slice + up16((plan.max_slices + 1) * sizeof(uint32_t));
-  o.bytes = o.point_of + up16(plan.max_slices * sizeof(int32_t));
+  o.tdl = o.point_of + up16(plan.max_slices * sizeof(int32_t));
+  o.bytes = o.tdl + (tdl ? up16(plan.max_seg * sizeof(mimo::TdlSeg)) : 0);
   return o;
 }
 
@@ -795,7 +848,7 @@ struct Progress {
   // row modes: the slice partials of every launch, in launch and slice order, and their points
   std::vector<double> part;
   std::vector<int> part_point;
-  double ms = 0.0, beam_ms = 0.0, decode_ms = 0.0;
+  double ms = 0.0, beam_ms = 0.0, decode_ms = 0.0, chan_ms = 0.0;
 };
 
 // The tables of one launch, written into the host blob: the segments' parameters and block
@@ -850,8 +903,24 @@ int run_launch(mimo_engine* e, const mimo::InstanceKey& key, const mimo::TrialPa
   kp.point_start = reinterpret_cast<const uint32_t*>(e->blob.p + o.start);
   kp.n_points = (int)t.nseg;
   kp.seed = ptab[segs[0].point].seed;  // unused by the kernel (read from the table)
+  const bool tdl = e->cfg.channel_kind == MIMO_CH_TDL;
+  if (tdl) {  // the generator's segments: the key and the first trial of every block range
+    mimo::TdlSeg* ts = reinterpret_cast<mimo::TdlSeg*>(e->h_blob.p + o.tdl);
+    for (size_t i = 0; i < t.nseg; ++i) ts[i] = mimo::TdlSeg{ptab[segs[i].point].seed, segs[i].first};
+  }
   // the whole blob (unused tails included: one contiguous DMA)
-  HIP_TRY(hipMemcpyAsync(e->blob.p, e->h_blob.p, o.point_of + nsl * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+  const size_t blob_bytes = tdl ? o.tdl + t.nseg * sizeof(mimo::TdlSeg) : o.point_of + nsl * sizeof(int32_t);
+  HIP_TRY(hipMemcpyAsync(e->blob.p, e->h_blob.p, blob_bytes, hipMemcpyHostToDevice, e->stream));
+  if (tdl) {
+    // the bank entries of this launch's blocks, in device memory (tdl.hip), ahead of the trial kernel
+    // on the same stream and timed on an event of its own
+    HIP_TRY(hipEventRecord(e->ev3, e->stream));
+    const hipError_t ge = mimo::launch_tdl(
+        e->stream, e->tdl, e->tdl_blob.p, reinterpret_cast<const mimo::TdlSeg*>(e->blob.p + o.tdl), kp.point_start,
+        (int)t.nseg, nb, e->cfg.n_sub_carr, sizeof(R) == 8 ? e->tab64.p : nullptr, sizeof(R) == 8 ? nullptr : e->tab32.p,
+        nullptr);
+    if (ge != hipSuccess) return fail(MIMO_EHIP, std::string("TDL generator kernel launch: ") + hipGetErrorString(ge));
+  }
   HIP_TRY(hipEventRecord(e->ev0, e->stream));
   bool found = false;
   // (the beam instances fill the launch's cells; the beamforming kernel forms the rows from them.
@@ -910,6 +979,10 @@ int run_launch(mimo_engine* e, const mimo::InstanceKey& key, const mimo::TrialPa
   float ms = 0.f;
   HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
   pg->ms += ms;
+  if (tdl) {
+    HIP_TRY(hipEventElapsedTime(&ms, e->ev3, e->ev0));
+    pg->chan_ms += ms;
+  }
   if (rm.beam) {
     HIP_TRY(hipEventSynchronize(e->ev2));
     HIP_TRY(hipEventElapsedTime(&ms, e->ev1, e->ev2));
@@ -931,7 +1004,7 @@ int run_launches(mimo_engine* e, const mimo::InstanceKey& key, const mimo::Trial
   // per-point parameter table (host), built once
   std::vector<mimo::TrialParams<R>> ptab(n_points, base);
   for (int i = 0; i < n_points; ++i) fill_point(e, pts[i], seeds[i], 0, ptab[i]);
-  const BlobLayout o = blob_layout(plan, sizeof(mimo::TrialParams<R>));
+  const BlobLayout o = blob_layout(plan, sizeof(mimo::TrialParams<R>), e->cfg.channel_kind == MIMO_CH_TDL);
   if (int rc = e->blob.ensure(o.bytes)) return rc;
   if (int rc = e->h_blob.ensure(o.bytes)) return rc;
   for (auto& segs : plan.launches)
@@ -955,8 +1028,16 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
   bool csi = false;
   if (int rc = validate_points(e, n_points, pts, first_trial, n_trials, &csi)) return rc;
   if (int rc = validate_distances(e)) return rc;
+  const bool tdl = c.channel_kind == MIMO_CH_TDL;
+  // one shared erroneous estimate per table is the table engine's rule; per-entry estimates are not built
+  if (csi && e->n_bank > 1)
+    return fail(MIMO_EINVAL, "csi_eps >= 0 is not supported with a channel bank of n_bank > 1 (one estimate per table)");
+  if (csi && tdl) return fail(MIMO_EINVAL, "csi_eps >= 0 is not supported on a MIMO_CH_TDL engine");
+  if (tdl && !e->have_tdl)
+    return fail(MIMO_EINVAL, "a MIMO_CH_TDL engine needs a profile before it runs: mimo_engine_set_tdl was not called");
   const mimo::InstanceKey key = select_instance(e, csi);
   if (int rc = ensure_device(e)) return rc;
+  if (int rc = refresh_channel_tables(e)) return rc;
   if (csi)
     if (int rc = check_csi_lds(e, key, rm.mode)) return rc;
   if (!c.reroll_chan && (c.channel_kind == MIMO_CH_LOS || c.channel_kind == MIMO_CH_TWOPATH)) {
@@ -966,7 +1047,23 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
   }
   e->desc = describe(key);
 
-  const Plan plan = plan_launches(n_points, first_trial, n_trials, rm.max_trials);
+  // a TDL launch holds no more trials than bank entries fit MIMO_BANK_BUFFER_BYTES
+  uint64_t max_trials = rm.max_trials;
+  if (tdl) {
+    uint64_t cap = (uint64_t)mimo_bank_capacity(c.n_ant, c.n_sub_carr, c.precision);
+    if (const char* env = std::getenv("MIMO_BANK_BUFFER_BYTES")) {  // lowers it, for measurements and tests of the splitting
+      const uint64_t v = std::strtoull(env, nullptr, 10) /
+                         ((uint64_t)c.n_ant * (uint64_t)c.n_sub_carr * (key.f64 ? sizeof(double2) : sizeof(float2)));
+      if (v >= 1 && v < cap) cap = v;
+    }
+    max_trials = std::min(max_trials, cap);
+  }
+  if (max_trials < 1) return fail(MIMO_EINVAL, "n_ant, n_sub_carr: one trial's channel does not fit the bank buffer");
+  const Plan plan = plan_launches(n_points, first_trial, n_trials, max_trials);
+  if (tdl) {
+    const size_t cells = std::max<size_t>(1, plan.max_blocks * (size_t)c.n_ant * (size_t)c.n_sub_carr);
+    if (int rc = key.f64 ? e->tab64.ensure(cells) : e->tab32.ensure(cells)) return rc;
+  }
   Progress pg;
   if (rm.rows()) {
     if (int rc = e->rows.ensure(std::max<size_t>(1, plan.max_blocks * rm.width))) return rc;
@@ -1018,6 +1115,7 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
   e->last_ms = pg.ms;
   e->last_beam_ms = pg.beam_ms;
   e->last_decode_ms = pg.decode_ms;
+  e->last_chan_ms = pg.chan_ms;
   return MIMO_OK;
 }
 
@@ -1275,6 +1373,62 @@ int32_t mimo_engine_coded_points(mimo_engine* e, int32_t n_points, const mimo_po
                     per_trial, rm);
 }
 
+int64_t mimo_bank_capacity(int32_t n_ant, int32_t n_sub_carr, int32_t precision) {
+  if (n_ant < 1) return fail(MIMO_EINVAL, "n_ant must be >= 1");
+  if (n_sub_carr < 1) return fail(MIMO_EINVAL, "n_sub_carr must be >= 1");
+  if (precision != MIMO_PREC_F64 && precision != MIMO_PREC_F32)
+    return fail(MIMO_EINVAL, "precision must be MIMO_PREC_F64 or MIMO_PREC_F32");
+  const uint64_t cell = precision == MIMO_PREC_F32 ? sizeof(float2) : sizeof(double2);
+  return (int64_t)(MIMO_BANK_BUFFER_BYTES / ((uint64_t)n_ant * (uint64_t)n_sub_carr * cell));
+}
+
+int32_t mimo_engine_set_channel_bank(mimo_engine* e, int32_t n_bank, const double* tables) {
+  if (!e) return fail(MIMO_EINVAL, "null engine");
+  const mimo_config& c = e->cfg;
+  if (c.channel_kind != MIMO_CH_TABLE)
+    return fail(MIMO_EINVAL, "channel_kind: a channel bank needs a MIMO_CH_TABLE engine");
+  const int64_t cap = mimo_bank_capacity(c.n_ant, c.n_sub_carr, c.precision);
+  if (n_bank < 0 || n_bank > cap)
+    return fail(MIMO_EINVAL, "n_bank must be in [0, " + std::to_string(cap) + "] (mimo_bank_capacity)");
+  if (n_bank > 0 && !tables) return fail(MIMO_EINVAL, "tables is required for n_bank > 0");
+  const size_t A = (size_t)c.n_ant, S = (size_t)c.n_sub_carr, F = (size_t)c.n_fft;
+  for (size_t j = 0; j < (size_t)n_bank; ++j)
+    for (size_t i = 0; i < A * F * 2; ++i)
+      if (!std::isfinite(tables[j * A * F * 2 + i]))
+        return fail(MIMO_EINVAL, "tables must be finite (entry " + std::to_string(j) + ", antenna " +
+                                     std::to_string(i / 2 / F) + ")");
+  // keep the in-band columns, bins b(k), in the engine's precision (float32: rounded to nearest)
+  const bool f32 = c.precision == MIMO_PREC_F32;
+  std::vector<double2> b64(f32 ? 0 : (size_t)n_bank * A * S);
+  std::vector<float2> b32(f32 ? (size_t)n_bank * A * S : 0);
+  for (size_t j = 0; j < (size_t)n_bank; ++j)
+    for (size_t a = 0; a < A; ++a)
+      for (size_t k = 0; k < S; ++k) {
+        const double* v = tables + ((j * A + a) * F + (size_t)band_bin((int)k, (int)S, (int)F)) * 2;
+        if (f32) b32[(j * A + a) * S + k] = make_float2((float)v[0], (float)v[1]);
+        else b64[(j * A + a) * S + k] = make_double2(v[0], v[1]);
+      }
+  e->bank64.swap(b64);
+  e->bank32.swap(b32);
+  e->n_bank = n_bank;
+  e->tab_stale = true;
+  return MIMO_OK;
+}
+
+int32_t mimo_engine_set_tdl(mimo_engine* e, const mimo_tdl* prof) {
+  if (!e) return fail(MIMO_EINVAL, "null engine");
+  if (e->cfg.channel_kind != MIMO_CH_TDL)
+    return fail(MIMO_EINVAL, "channel_kind: a TDL profile needs a MIMO_CH_TDL engine");
+  mimo::TdlHost host;
+  std::string err;
+  if (!mimo::tdl_prepare(prof, e->cfg.n_ant, e->cfg.n_fft, &host, &err)) return fail(MIMO_EINVAL, err);
+  e->tdl = std::move(host);
+  e->have_tdl = true;
+  e->tdl_stale = true;
+  return MIMO_OK;
+}
+
+double mimo_engine_last_chan_ms(const mimo_engine* e) { return e ? e->last_chan_ms : 0.0; }
 double mimo_engine_last_kernel_ms(const mimo_engine* e) { return e ? e->last_ms : 0.0; }
 double mimo_engine_last_decode_ms(const mimo_engine* e) { return e ? e->last_decode_ms : 0.0; }
 double mimo_engine_last_beam_ms(const mimo_engine* e) { return e ? e->last_beam_ms : 0.0; }

@@ -1,0 +1,246 @@
+// The tapped-delay-line channel's generator kernel and its fine seam (tdl.h; include/mimo_engine.h
+// mimo_engine_set_tdl, mimo_tdl_channels).  One workgroup per (block, antenna): its first wave draws
+// the L taps into LDS, and after one barrier every thread accumulates the response of its columns
+// over the taps in ascending order and stores it, the threads of a wave at adjacent columns.  The
+// engine (in-band columns, the engine's precision) and the seam (every bin, complex128, the taps as
+// well) run the same kernel template, so the same device functions: equal inputs, equal bits.
+#include "tdl.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "philox.h"
+
+namespace mimo {
+void set_error(const std::string& m);  // engine.hip: one thread-local message for mimo_last_error()
+
+namespace {
+
+constexpr int kTdlThreads = 256;
+// Where the kernel reads the twiddle table W from: up to this n_fft a copy that every workgroup
+// stages in dynamic LDS first (16 n_fft bytes: 64 KiB at 4096), beyond it global memory.  The
+// generator is bound by these look-ups, not by its stores: against global memory the staged copy
+// measured -26 % (8 taps) and -24 % (32) at n_fft 2048 and -46 % / -51 % at 4096
+// (profiles/r20/tdl/; -DMIMO_TDL_W_LDS_MAX_F=0 builds the other side).  n_fft 8192 would take
+// 128 KiB, one workgroup per CU, and was not measured: it reads global memory.  The values are the
+// same either way, and so are the bits.
+#ifndef MIMO_TDL_W_LDS_MAX_F
+#define MIMO_TDL_W_LDS_MAX_F 4096
+#endif
+constexpr uint32_t kStreamTdl = 7;  // Philox stream of the taps (philox.h Stream; 6 is mimo_awgn's)
+
+// Tap l of antenna a in trial `trial`: scale sqrt(-ln u1) exp(j 2 pi u2), mimo_awgn's formula.
+__device__ __forceinline__ double2 tdl_tap(Key key, uint32_t l, uint32_t trial, uint32_t a, double scale) {
+  const uint4 w = philox4x32_10(make_uint4(l, trial, kStreamTdl, a), key);
+  const double u1 = ((double)w.x + 0.5) * 2.3283064365386963e-10, u2 = (double)w.y * 2.3283064365386963e-10;
+  const double r = scale * sqrt(-log(u1));
+  double s, c;
+  sincospi(2.0 * u2, &s, &c);
+  return make_double2(r * c, r * s);
+}
+
+// H at FFT bin `bin`: sum_l g[l] W[(bin d[l]) mod F] in ascending l from 0, each complex product as
+// four fused multiply-adds written out (no contraction left to the compiler).  bin d < 2^26.
+__device__ __forceinline__ double2 tdl_response(const double2* g, const int* d, int L, const double2* W,
+                                                uint32_t bin, uint32_t fmask) {
+  double re = 0.0, im = 0.0;
+  for (int l = 0; l < L; ++l) {
+    const double2 w = W[(bin * (uint32_t)d[l]) & fmask];
+    const double2 t = g[l];
+    re = fma(t.x, w.x, re);
+    re = fma(-t.y, w.y, re);
+    im = fma(t.x, w.y, im);
+    im = fma(t.y, w.x, im);
+  }
+  return make_double2(re, im);
+}
+
+__device__ __forceinline__ void tdl_store(double2* p, double2 v) { *p = v; }
+__device__ __forceinline__ void tdl_store(float2* p, double2 v) { *p = make_float2((float)v.x, (float)v.y); }
+
+// grid (blocks, antennas).  n_sc > 0: the in-band columns of the trial kernel's table [block][A][S];
+// n_sc = 0: all F bins.  WLDS: W staged in F double2 of dynamic LDS (the same values: the same bits).
+template <typename OUT, bool WLDS>
+__global__ __launch_bounds__(kTdlThreads) void tdl_fill(const double2* W, const double* __restrict__ sqrt_pow,
+                                                        const double* __restrict__ ant_amp,
+                                                        const int32_t* __restrict__ delays, int L, int F, int A, int n_sc,
+                                                        const TdlSeg* __restrict__ segs,
+                                                        const uint32_t* __restrict__ seg_start, int n_seg,
+                                                        OUT* __restrict__ out, double2* __restrict__ taps) {
+  __shared__ double2 g_s[kTdlMaxTaps];
+  __shared__ int d_s[kTdlMaxTaps];
+  const uint32_t b = blockIdx.x;
+  const uint32_t a = blockIdx.y;
+  uint32_t lo = 0, hi = (uint32_t)n_seg;  // uniform binary search, as the trial kernel's over point_start
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (seg_start[mid] <= b) lo = mid; else hi = mid;
+  }
+  const TdlSeg sg = segs[lo];
+  const uint32_t trial = (uint32_t)(sg.first_trial + (b - seg_start[lo]));
+  const Key key{(uint32_t)sg.seed, (uint32_t)(sg.seed >> 32)};
+  const int t = threadIdx.x;
+  if (t < L) {  // L <= 64: the first wave
+    const double2 g = tdl_tap(key, (uint32_t)t, trial, a, ant_amp[a] * sqrt_pow[t]);
+    g_s[t] = g;
+    d_s[t] = delays[t];
+    if (taps) taps[((size_t)b * A + a) * L + t] = g;
+  }
+  if constexpr (WLDS) {
+    extern __shared__ double2 w_s[];
+    for (int m = t; m < F; m += kTdlThreads) w_s[m] = W[m];
+    W = w_s;
+  }
+  __syncthreads();
+  const int n_cols = n_sc ? n_sc : F;
+  const int half = n_sc >> 1;
+  OUT* row = out + ((size_t)b * A + a) * n_cols;
+  for (int c = t; c < n_cols; c += kTdlThreads) {
+    const int bin = n_sc ? (c < half ? F - half + c : c - half + 1) : c;
+    tdl_store(row + c, tdl_response(g_s, d_s, L, W, (uint32_t)bin, (uint32_t)F - 1u));
+  }
+}
+
+}  // namespace
+
+std::vector<double> TdlHost::blob() const {
+  const int L = n_taps, F = n_fft, A = n_ant;
+  std::vector<double> v((size_t)2 * F + L + A + (L + 1) / 2, 0.0);
+  // W[m] = exp(-j 2 pi m / F), formed in long double and rounded once; W[0] = (1, -0.0)
+  const long double two_pi = 8.0L * atanl(1.0L);
+  for (int m = 0; m < F; ++m) {
+    const long double ang = two_pi * (long double)m / (long double)F;
+    v[2 * (size_t)m] = (double)cosl(ang);
+    v[2 * (size_t)m + 1] = (double)(-sinl(ang));
+  }
+  std::copy(sqrt_pow.begin(), sqrt_pow.end(), v.begin() + 2 * (size_t)F);
+  std::copy(ant_amp.begin(), ant_amp.end(), v.begin() + 2 * (size_t)F + L);
+  std::memcpy(v.data() + 2 * (size_t)F + L + A, delays.data(), sizeof(int32_t) * (size_t)L);
+  return v;
+}
+
+bool tdl_prepare(const mimo_tdl* prof, int n_ant, int n_fft, TdlHost* out, std::string* err) {
+  auto bad = [&](const std::string& m) {
+    *err = m;
+    return false;
+  };
+  if (!prof) return bad("null profile (mimo_tdl)");
+  if (prof->n_taps < 1 || prof->n_taps > kTdlMaxTaps)
+    return bad("n_taps must be in [1, " + std::to_string(kTdlMaxTaps) + "]");
+  if (!prof->delays) return bad("delays is required");
+  if (!prof->powers) return bad("powers is required");
+  const int L = prof->n_taps;
+  for (int l = 0; l < L; ++l) {
+    if (prof->delays[l] < 0 || prof->delays[l] >= n_fft)
+      return bad("delays must be in [0, n_fft) (tap " + std::to_string(l) + ")");
+    if (l && prof->delays[l] <= prof->delays[l - 1])
+      return bad("delays must be strictly ascending (tap " + std::to_string(l) + ")");
+    if (!(prof->powers[l] > 0) || !std::isfinite(prof->powers[l]))
+      return bad("powers must be finite and > 0 (tap " + std::to_string(l) + ")");
+  }
+  if (prof->ant_amp)
+    for (int a = 0; a < n_ant; ++a)
+      if (!(prof->ant_amp[a] > 0) || !std::isfinite(prof->ant_amp[a]))
+        return bad("ant_amp must be finite and > 0 (antenna " + std::to_string(a) + ")");
+  out->n_taps = L;
+  out->n_ant = n_ant;
+  out->n_fft = n_fft;
+  out->delays.assign(prof->delays, prof->delays + L);
+  out->sqrt_pow.resize(L);
+  for (int l = 0; l < L; ++l) out->sqrt_pow[l] = std::sqrt(prof->powers[l]);
+  if (prof->ant_amp) out->ant_amp.assign(prof->ant_amp, prof->ant_amp + n_ant);
+  else out->ant_amp.assign(n_ant, 1.0);
+  return true;
+}
+
+hipError_t launch_tdl(hipStream_t st, const TdlHost& prof, const double* blob, const TdlSeg* segs,
+                      const uint32_t* seg_start, int n_seg, uint32_t n_blocks, int n_sc, double2* out64, float2* out32,
+                      double2* taps) {
+  if (n_blocks == 0) return hipSuccess;
+  const int L = prof.n_taps, F = prof.n_fft, A = prof.n_ant;
+  const double2* W = reinterpret_cast<const double2*>(blob);
+  const double* sqrt_pow = blob + 2 * (size_t)F;
+  const double* ant_amp = sqrt_pow + L;
+  const int32_t* delays = reinterpret_cast<const int32_t*>(ant_amp + A);
+  const dim3 grid(n_blocks, (unsigned)A);
+  auto go = [&](auto kernel, auto* out) -> hipError_t {
+    const size_t lds = F <= MIMO_TDL_W_LDS_MAX_F ? (size_t)F * sizeof(double2) : 0;
+    if (lds > (48u << 10))  // beyond the default limit of a launch
+      if (hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
+        return e;
+    hipLaunchKernelGGL(kernel, grid, dim3(kTdlThreads), lds, st, W, sqrt_pow, ant_amp, delays, L, F, A, n_sc, segs,
+                       seg_start, n_seg, out, taps);
+    return hipGetLastError();
+  };
+  const bool wlds = F <= MIMO_TDL_W_LDS_MAX_F;
+  if (out64) return wlds ? go(tdl_fill<double2, true>, out64) : go(tdl_fill<double2, false>, out64);
+  return wlds ? go(tdl_fill<float2, true>, out32) : go(tdl_fill<float2, false>, out32);
+}
+
+}  // namespace mimo
+
+namespace {
+
+int tfail(int code, const std::string& m) {
+  mimo::set_error(m);
+  return code;
+}
+
+struct TBuf {  // a device allocation of the seam's, released with the call
+  void* p = nullptr;
+  ~TBuf() {
+    if (p) (void)hipFree(p);
+  }
+};
+
+#define T_TRY(expr)                                                                                \
+  do {                                                                                             \
+    hipError_t _e = (expr);                                                                        \
+    if (_e != hipSuccess) return tfail(MIMO_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+  } while (0)
+
+}  // namespace
+
+extern "C" int32_t mimo_tdl_channels(const mimo_tdl* prof, int32_t n_ant, int32_t n_fft, uint64_t seed,
+                                     uint64_t first_trial, int64_t n, double* h_out, double* taps_out) {
+  if (n_fft < 2 || n_fft > 8192 || (n_fft & (n_fft - 1)))
+    return tfail(MIMO_EINVAL, "n_fft must be a power of two in [2, 8192]");
+  if (n_ant < 1 || n_ant > 4096) return tfail(MIMO_EINVAL, "n_ant must be in [1, 4096]");
+  if (n < 0) return tfail(MIMO_EINVAL, "n must be >= 0");
+  mimo::TdlHost host;
+  std::string err;
+  if (!mimo::tdl_prepare(prof, n_ant, n_fft, &host, &err)) return tfail(MIMO_EINVAL, err);
+  if (n == 0) return MIMO_OK;
+  if (!h_out) return tfail(MIMO_EINVAL, "null h_out");
+  const std::vector<double> blob = host.blob();
+  const size_t per_trial = (size_t)n_ant * (size_t)n_fft, L = (size_t)host.n_taps;
+  // trials of one launch: at most 256 MiB of responses
+  const int64_t chunk = std::max<int64_t>(1, (int64_t)((256u << 20) / (per_trial * sizeof(double2))));
+  const int64_t nb_max = std::min(n, chunk);
+  TBuf d_blob, d_seg, d_h, d_taps;
+  T_TRY(hipMalloc(&d_blob.p, blob.size() * sizeof(double)));
+  T_TRY(hipMalloc(&d_seg.p, sizeof(mimo::TdlSeg) + 2 * sizeof(uint32_t)));
+  T_TRY(hipMalloc(&d_h.p, (size_t)nb_max * per_trial * sizeof(double2)));
+  if (taps_out) T_TRY(hipMalloc(&d_taps.p, (size_t)nb_max * n_ant * L * sizeof(double2)));
+  T_TRY(hipMemcpy(d_blob.p, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice));
+  for (int64_t done = 0; done < n; done += chunk) {
+    const int64_t nb = std::min(chunk, n - done);
+    struct {
+      mimo::TdlSeg seg;
+      uint32_t start[2];
+    } tab{{seed, first_trial + (uint64_t)done}, {0u, (uint32_t)nb}};
+    T_TRY(hipMemcpy(d_seg.p, &tab, sizeof tab, hipMemcpyHostToDevice));
+    const char* seg_base = static_cast<const char*>(d_seg.p);
+    T_TRY(mimo::launch_tdl(nullptr, host, static_cast<const double*>(d_blob.p),
+                           reinterpret_cast<const mimo::TdlSeg*>(seg_base),
+                           reinterpret_cast<const uint32_t*>(seg_base + sizeof(mimo::TdlSeg)), 1, (uint32_t)nb, 0,
+                           static_cast<double2*>(d_h.p), nullptr, static_cast<double2*>(d_taps.p)));
+    T_TRY(hipMemcpy(h_out + (size_t)done * per_trial * 2, d_h.p, (size_t)nb * per_trial * sizeof(double2),
+                    hipMemcpyDeviceToHost));
+    if (taps_out)
+      T_TRY(hipMemcpy(taps_out + (size_t)done * n_ant * L * 2, d_taps.p, (size_t)nb * n_ant * L * sizeof(double2),
+                      hipMemcpyDeviceToHost));
+  }
+  return MIMO_OK;
+}

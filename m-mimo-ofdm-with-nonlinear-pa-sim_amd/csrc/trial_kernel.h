@@ -152,7 +152,7 @@ struct TrialParams {
   const double* f_over_c;        // [S]  f_k / c       (LoS / two-path phases)
   const double* tx_pos;          // [A*3]
   const double2* lut;            // [kLut64] fp64 ln / sincos tables (real.h; fp64 instances only)
-  const C* chan_tab;             // CH_TABLE: fixed in-band channel [A][S] (sub-carrier order k)
+  const C* chan_tab;             // CH_TABLE: in-band channels [entries][A][S] (sub-carrier order k), see chan_period
   int n_ant, n_sc, qam_l, half_bits;
   uint32_t label_mask;
   int pa_kind, cnc_pa_kind;
@@ -186,7 +186,9 @@ struct TrialParams {
   const TrialParams* points;     // [n_points] (device)
   const uint32_t* point_start;   // [n_points + 1] block offsets (device)
   int n_points;
-  uint32_t chan_period;          // 0, or the channel-replay period (mimo_config.chan_replay_period)
+  uint32_t chan_period;          // 0, or the channel-replay period (mimo_config.chan_replay_period);
+                                 // CH_TABLE: the entries of chan_tab (trial i reads entry i mod
+                                 // chan_period), or 0: one entry per block of the launch
   // Last, so that the fields the antenna loop reloads keep their 16-byte alignment (the
   // scalar loads pair them as s_load_dwordx4; inserted after `seed` it cost the F 4096
   // instance 1 %, profiles/r04/misc/).
@@ -806,13 +808,15 @@ struct Channel {
         }
       }
     } else if constexpr (CH == CH_TABLE) {
-      // the caller's fixed channel (Link.simulate reroll_chan=False): coalesced loads of the
-      // in-band row (f_rel is 1 for table engines: nothing is factored out)
+      // the caller's channel (Link.simulate reroll_chan=False), entry `trial` of the bank (the
+      // kernel's ch_trial): coalesced loads of the in-band row (f_rel is 1 for table engines:
+      // nothing is factored out).  The bank holds at most 2^27 values: the index fits 32 bits.
+      const size_t row = ((size_t)trial * (size_t)p.n_ant + (size_t)a) * (size_t)S;
 #pragma unroll
       for (int s = 0; s < NSLOT; ++s) {
         bool v;
         const int k = SL::k_of(s, t, S, v);
-        h[s] = v ? p.chan_tab[(size_t)a * S + k] : czero<R>();
+        h[s] = v ? p.chan_tab[row + k] : czero<R>();
       }
     } else {
       const double tx = p.tx_pos[3 * a], ty = p.tx_pos[3 * a + 1], tz = p.tx_pos[3 * a + 2];
@@ -1057,7 +1061,12 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
   // period -- every group of chan_period trials replays one sequence of Rayleigh channels,
   // as the reference's forked workers all replay the channel object's seeded generator
   // (channel.py:209-212, mp_model.py:61); bits and noise stay per trial.
-  const uint32_t ch_trial = p0.chan_period ? trial % p0.chan_period : trial;
+  // Table instances: the channel counter is the entry of the channel bank, [entries][A][S] behind
+  // chan_tab, that the trial reads.  chan_period holds the bank's size there (1: the one
+  // create-time table) and the trial takes entry trial mod chan_period; 0: the bank was filled for
+  // this launch, block by block (the TDL generator, tdl.hip), and the block takes its own entry.
+  const uint32_t ch_trial = CH == CH_TABLE ? (p0.chan_period ? trial % p0.chan_period : (uint32_t)blockIdx.x)
+                                           : (p0.chan_period ? trial % p0.chan_period : trial);
   const int S = p.n_sc, A = p.n_ant, L = p.qam_l, hb = p.half_bits;
   const R inv_sqrt_f = p.inv_sqrt_f;
   if constexpr (sizeof(R) == 8) fill_lut64<T>(&p, t);

@@ -289,7 +289,8 @@ class Link:
         self.my_noise = copy.deepcopy(noise_obj)
         self.my_csi_noise = copy.deepcopy(noise_obj)
         self.csi_epsylon = csi_epsylon
-        if not isinstance(chan_obj, (channel.MisoRayleighFd, channel.MisoLosFd, channel.MisoTwoPathFd)):
+        if not isinstance(chan_obj, (channel.MisoRayleighFd, channel.MisoLosFd, channel.MisoTwoPathFd,
+                                     channel.MisoTdlFd)):
             raise NotImplementedError(f"{type(chan_obj).__name__} is out of scope (MATLAB / NumPy-1 channels)")
         self.is_quadriga = False
         self.my_miso_chan = copy.deepcopy(chan_obj)
@@ -331,22 +332,38 @@ class Link:
             return "rayleigh"
         if isinstance(self.my_miso_chan, channel.MisoTwoPathFd):
             return "two_path"
+        if isinstance(self.my_miso_chan, channel.MisoTdlFd):
+            return "tdl"
         return "los"
+
+    def _tdl_profile(self):
+        """(delays, powers, ant_amp) of the TDL channel object as the engine takes them.  The
+        amplitudes go in relative to the strongest antenna's, as the Rayleigh engine takes its
+        attenuations relative to the nearest antenna's: a common factor cancels in the MRT precoder,
+        the AGC and the SNR normalisation, and the float32 engine keeps its range."""
+        ch = self.my_miso_chan
+        return ch.delays, ch.powers, ch.ant_amp / np.max(ch.ant_amp)
 
     def engine(self, reroll_chan: bool = True):
         """The configured GPU engine for the current grid point (created lazily, per process).
 
         ``reroll_chan=False`` (mp_model.py:190-206: every trial sees the channel object's
-        current matrix) runs the table-channel instances on ``channel_mat_fd``."""
+        current matrix) runs the table-channel instances on ``channel_mat_fd``.  A ``MisoTdlFd``
+        channel with ``reroll_chan=True`` runs a TDL engine on the object's profile: an independent
+        realisation per trial, drawn on the device."""
         kind = self._chan_kind()
         table = None
+        prof = None
         if not reroll_chan:
             table = np.asarray(self.my_miso_chan.channel_mat_fd, dtype=np.complex128)
             kind = "table"
         dev = self.device if self.device is not None else _default_device()
         acquire_device_slot(dev)  # best effort here; simulate() waits for a slot
+        if kind == "tdl":
+            prof = self._tdl_profile()
         key = (dev, kind, bool(reroll_chan), self.is_mcnc, self.precision,
-               None if table is None else hash(table.tobytes()))
+               None if table is None else hash(table.tobytes()),
+               None if prof is None else hash(b"".join(np.ascontiguousarray(v).tobytes() for v in prof)))
         if self._engine is None or self._engine_key != key:
             m = self.my_mod
             rx = self.my_standard_rx
@@ -356,6 +373,8 @@ class Link:
                 (self.rx_loc_x, self.rx_loc_y, rx.cord_z), self.rx_loc_var,
                 channel.carrier_freqs(m.n_fft, rx.carrier_spacing, rx.center_freq), reroll=reroll_chan, device=dev,
                 precision=self.precision, chan_table=table, csi_seed=self.csi_seed if table is not None else 0)
+            if prof is not None:
+                self._engine.set_tdl(*prof)
             self._engine_key = key
         self._push_point()
         return self._engine

@@ -42,14 +42,31 @@ BASELINE_C4 = dict(ibo=np.arange(0.0, 7.01, 0.5), ebn0=np.arange(0.0, 30.01, 0.5
                    n_ant=64, n_sc=2048, n_fft=4096, qam=64, cp=128, bits_sent_max=int(5e6), n_err_min=int(1e5))
 
 
+def make_channel(kind, tx_transceivers, rx_transceiver, tdl=(8, 4, 3.0)):
+    """The channel object of ``kind``: "rayleigh" (seed 1234, as the reference's drivers), "los",
+    "two_path", or "tdl" -- a ``MisoTdlFd`` on the stand-in profile ``utilities.exp_pdp(*tdl)``
+    (taps, step in samples, decay in dB per tap)."""
+    import channel as ch_mod
+    import utilities
+    if kind == "rayleigh":
+        return ch_mod.MisoRayleighFd(tx_transceivers=tx_transceivers, rx_transceiver=rx_transceiver, seed=1234)
+    if kind == "tdl":
+        delays, powers = utilities.exp_pdp(*tdl)
+        return ch_mod.MisoTdlFd(tx_transceivers=tx_transceivers, rx_transceiver=rx_transceiver, delays=delays,
+                                powers_db=10 * np.log10(powers), seed=1234)
+    ch = ch_mod.MisoLosFd() if kind == "los" else ch_mod.MisoTwoPathFd()
+    ch.calc_channel_mat(tx_transceivers=tx_transceivers, rx_transceiver=rx_transceiver, skip_attenuation=False)
+    return ch
+
+
 def paper_link(channel="rayleigh", receiver="cnc", precision="f64", device=None, n_ant=64, n_sc=2048, n_fft=4096,
-               qam=64, cp=128, n_err_min=int(1e5), bits_sent_max=int(5e6)):
+               qam=64, cp=128, n_err_min=int(1e5), bits_sent_max=int(5e6), tdl=(8, 4, 3.0)):
     """The reference drivers' Link (main_mp_miso_cnc_constant_ber_req_ebn0_vs_ibo.py:40-98):
-    ULA at z = 15 m, RX at (212, 212, 1.5), 3.5 GHz / 15 kHz, soft limiter, seed-1234 Rayleigh."""
+    ULA at z = 15 m, RX at (212, 212, 1.5), 3.5 GHz / 15 kHz, soft limiter, seed-1234 Rayleigh
+    (``channel="tdl"``: the TDL channel on ``utilities.exp_pdp(*tdl)``)."""
     import copy
 
     import antenna_array
-    import channel as ch_mod
     import distortion
     import modulation
     import mp_model
@@ -63,11 +80,7 @@ def paper_link(channel="rayleigh", receiver="cnc", precision="f64", device=None,
                                  cord_y=212, cord_z=1.5, center_freq=int(3.5e9), carrier_spacing=int(15e3))
     arr = antenna_array.LinearArray(n_elements=n_ant, base_transceiver=tx, center_freq=int(3.5e9),
                                     wav_len_spacing=0.5, cord_x=0, cord_y=0, cord_z=15)
-    if channel == "rayleigh":
-        ch = ch_mod.MisoRayleighFd(tx_transceivers=arr.array_elements, rx_transceiver=rx, seed=1234)
-    else:
-        ch = ch_mod.MisoLosFd() if channel == "los" else ch_mod.MisoTwoPathFd()
-        ch.calc_channel_mat(tx_transceivers=arr.array_elements, rx_transceiver=rx, skip_attenuation=False)
+    ch = make_channel(channel, arr.array_elements, rx, tdl)
     return mp_model.Link(mod_obj=mod, array_obj=arr, std_rx_obj=rx, chan_obj=ch, noise_obj=noise.Awgn(snr_db=10),
                          rx_loc_var=10.0, n_err_min=n_err_min, bits_sent_max=bits_sent_max,
                          is_mcnc=receiver == "mcnc", device=device, precision=precision)
@@ -98,7 +111,7 @@ def owned_points(n_points: int, rank: int, world: int, costs=None) -> list:
 # i.i.d. Rayleigh the distortion is not beamformed (~1/A of it reaches the user); over LoS /
 # two-path it is, and the CNC / MCNC iterations remove ~90 % of it.  Calibrated on the
 # committed one-GPU records of the 915-point grid (profiles/r05/grid/, tests/test_grid_balance.py).
-RESIDUAL_DISTORTION = {"rayleigh": None, "los": 0.1, "two_path": 0.1}
+RESIDUAL_DISTORTION = {"rayleigh": None, "tdl": None, "los": 0.1, "two_path": 0.1}  # (tdl: not calibrated, as Rayleigh)
 
 
 def soft_limiter_sdr(ibo_db):
@@ -455,7 +468,6 @@ def _build_link(args, device):
     import copy
 
     import antenna_array
-    import channel
     import distortion
     import modulation
     import mp_model
@@ -473,17 +485,13 @@ def _build_link(args, device):
                                  cord_y=212.0, cord_z=1.5, center_freq=int(3.5e9), carrier_spacing=int(15e3))
     arr = antenna_array.LinearArray(n_elements=args.n_ant, base_transceiver=tx, center_freq=int(3.5e9),
                                     wav_len_spacing=0.5, cord_x=0, cord_y=0, cord_z=15)
-    if args.channel == "rayleigh":
-        ch = channel.MisoRayleighFd(tx_transceivers=arr.array_elements, rx_transceiver=rx, seed=1234)
-    else:
-        ch = channel.MisoLosFd() if args.channel == "los" else channel.MisoTwoPathFd()
-        ch.calc_channel_mat(tx_transceivers=arr.array_elements, rx_transceiver=rx, skip_attenuation=False)
+    ch = make_channel(args.channel, arr.array_elements, rx, (args.tdl_taps, args.tdl_step, args.tdl_decay_db))
     return mp_model.Link(mod_obj=mod, array_obj=arr, std_rx_obj=rx, chan_obj=ch, noise_obj=noise.Awgn(snr_db=10),
                          rx_loc_var=10.0, n_err_min=args.n_err_min, bits_sent_max=args.bits_sent_max,
                          is_mcnc=args.receiver == "mcnc", device=device)
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--grid", choices=["ber_vs_ebn0", "fixed_ber", "sdr_vs_ibo", "psd_vs_ibo", "beam_vs_angle",
                                        "ccdf_vs_ibo", "gmi_vs_ebn0", "coded_ber_vs_ebn0"],
@@ -513,7 +521,12 @@ def main():
     ap.add_argument("--qam", type=int, default=64)
     ap.add_argument("--pa", choices=["softlim", "rapp"], default="softlim")
     ap.add_argument("--p-hardness", type=float, default=3.0)
-    ap.add_argument("--channel", choices=["rayleigh", "los", "two_path"], default="rayleigh")
+    ap.add_argument("--channel", choices=["rayleigh", "los", "two_path", "tdl"], default="rayleigh",
+                    help="tdl: a tapped-delay-line Rayleigh channel (frequency-selective) on the stand-in profile of "
+                         "--tdl-taps, --tdl-step and --tdl-decay-db (utilities.exp_pdp); every --grid runs on it")
+    ap.add_argument("--tdl-taps", type=int, default=8, help="--channel tdl: taps of the profile (1 ... 64)")
+    ap.add_argument("--tdl-step", type=int, default=4, help="--channel tdl: tap spacing in whole samples")
+    ap.add_argument("--tdl-decay-db", type=float, default=3.0, help="--channel tdl: decay per tap [dB]")
     ap.add_argument("--receiver", choices=["cnc", "mcnc"], default="cnc")
     ap.add_argument("--ibo", type=str, default="0:8:0.5", help="start:stop:step (numpy arange)")
     ap.add_argument("--ebn0", type=str, default="10:22.1:0.5",
@@ -531,7 +544,11 @@ def main():
                     help="ranks deal whole points by cost (one all-reduce at the end), or share every point's "
                          "trials (one all-reduce per stopping-rule round); auto: trials when there are fewer "
                          "points than ranks")
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))

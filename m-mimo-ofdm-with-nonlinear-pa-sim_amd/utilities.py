@@ -135,6 +135,21 @@ def qc_ldpc_code(z: int, n_rows: int, n_cols: int, n_dec_iters: int = 10, seed: 
     return _engine.LdpcCode(z, s, n_dec_iters)
 
 
+def exp_pdp(n_taps: int, step: int, decay_db_per_tap: float):
+    """An exponential power-delay profile for the TDL channel (``channel.MisoTdlFd``,
+    ``_engine.Engine.set_tdl``): ``n_taps`` taps ``step`` whole samples apart from delay 0, tap ``l``
+    ``l * decay_db_per_tap`` dB below the first, the linear powers normalised to sum 1.
+    -> (delays int32 [n_taps], powers float64 [n_taps]); ``10 * np.log10(powers)`` is ``MisoTdlFd``'s
+    ``powers_db``.  No standard's table: a stand-in of the usual shape for anyone who has none at hand."""
+    n_taps, step = int(n_taps), int(step)
+    if n_taps < 1 or step < 1:
+        raise ValueError("n_taps and step must be >= 1")
+    if not np.isfinite(decay_db_per_tap) or decay_db_per_tap < 0:
+        raise ValueError("decay_db_per_tap must be finite and >= 0")
+    p = np.power(10.0, -float(decay_db_per_tap) * np.arange(n_taps) / 10)
+    return (np.arange(n_taps) * step).astype(np.int32), p / np.sum(p)
+
+
 def save_to_csv(data_lst: list, filename: str, directory: str = "figs/csv_results") -> None:
     """One row per vector, ``csv.writer.writerows`` (utilities.py:342-352); the reference
     writes to ``figs/csv_results`` relative to the working directory."""
