@@ -267,7 +267,9 @@ template <typename R, int MODE>
 hipError_t launch_sized(const mimo::InstanceKey& k, dim3 grid, hipStream_t st, const mimo::TrialParams<R>& p,
                         bool* found, hipFuncAttributes* attr, double* out, double aux) {
   *found = false;
-#ifdef MIMO_ONLY_F  // single-size diagnostic / A-B builds (Makefile targets ablation, variant): plain only
+#if defined(MIMO_ONLY_F) && defined(MIMO_ONLY_MEAS)  // A-B builds (Makefile target variant): plain and measure
+  constexpr bool built = MODE == MIMO_MODE_PLAIN || (MODE == MIMO_MODE_MEAS && sizeof(R) == 8);
+#elif defined(MIMO_ONLY_F)  // single-size diagnostic builds (Makefile target ablation): plain only
   constexpr bool built = MODE == MIMO_MODE_PLAIN;
 #else
   constexpr bool built = MODE == MIMO_MODE_PLAIN || sizeof(R) == 8;

@@ -65,6 +65,24 @@ int32_t mimo_probe_alpha_fit(double g0sq, double* amono19, double* apoly9, doubl
  * out: the table's length.  Copies only if it fits. */
 int32_t mimo_probe_table(int32_t kind, int32_t prec, int32_t F, void* buf, int64_t* n);
 
+/* Host only: the transform addresses that the float64 wave-split instance at F (1024, 2048) holds
+ * across its antenna loop (wave_fft.h XAddr).  words: [T][3] packed words (address pairs, low half
+ * first: cross | row, x0r | x1w, tw | x1r), computed by the kernel's formulas, or copied from
+ * words_in if that is not null.  sites: [T][MIMO_PROBE_XADDR_SITES] byte offsets as the kernel's
+ * accessors unpack them from those words: 0 the cross-wave base, 1 the wave's row plus lane,
+ * 2 exchange 0's read base, 3 exchange 1's write base, 4 its read base, 5 / 6 the lane's offset in
+ * the rows of stage 1's / stage 2's LDS constants, 7 / 8 the inverse's inter-step twiddle offsets
+ * for k = 1 / 2, 9 the forward's.  info: T, waves, points per thread, butterflies NB, FW, row
+ * elements, exchange array elements, R0, XS0, NS of stages 1 and 2, their offsets in the LDS
+ * constants, that copy's entries, the inter-step twiddles' offset in the table, bytes per element,
+ * constant rows of stages 1 and 2, exchange 1's padding shift, the table's entries, 1 where the
+ * sub-transform's stages are in cot-tan form.  Without it (two-wave teams) stage 1's rows are its
+ * twiddle block in the LDS copy and stage 2's are that stage's block of the table in global
+ * memory, whose offset and rows the info then gives. */
+#define MIMO_PROBE_XADDR_SITES 10
+#define MIMO_PROBE_XADDR_INFO 21
+int32_t mimo_probe_xaddr(int32_t F, const uint32_t* words_in, uint32_t* words, uint32_t* sites, int32_t* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -263,6 +263,41 @@ int give_table(const std::vector<V>& t, void* buf, int64_t* n) {
   return MIMO_PROBE_OK;
 }
 
+// The held transform addresses of the float64 wave-split instance at F (wave_fft.h XAddr): every
+// thread's packed words from the formulas the kernel packs them with, or the caller's, and what
+// the kernel's accessors unpack from them at each use site.
+template <int F>
+int32_t xaddr_of(const uint32_t* words_in, uint32_t* words, uint32_t* sites, int32_t* info) {
+  constexpr int T = team_size64(F);
+  using W = WaveFft<F, T, double, true, true>;
+  using S = typename W::Sub;
+  using XA = typename W::XAddr;
+  static_assert(W::XA_PLAN, "the plan the held addresses are written for");
+  constexpr int NS1 = 1 << S::bits_before(1), NS2 = 1 << S::bits_before(2);
+  const int32_t inf[MIMO_PROBE_XADDR_INFO] = {T, W::WV, W::P, W::NB, W::FW, W::ROW, W::LDS_TOTAL, S::R0, S::XS0, NS1, NS2,
+                                              S::CT ? S::ct_off(1) : 0, S::CT ? S::ct_off(2) : fft_tw_off(W::FW, W::P, 2),
+                                              W::TWL_N, W::TW_INTER, W::CB,
+                                              S::CT ? ct_rows(1 << S::bits(1)) : 1 << S::bits(1),
+                                              S::CT ? ct_rows(1 << S::bits(2)) : 1 << S::bits(2), S::psh(1),
+                                              wave_fft_tw_total(F, T) + wave_fft_ct_n(F, T), S::CT ? 1 : 0};
+  for (int i = 0; i < MIMO_PROBE_XADDR_INFO; ++i) info[i] = inf[i];
+  for (int t = 0; t < T; ++t) {
+    XA xa{};
+    if (words_in) {
+      xa.w_cr = words_in[3 * t], xa.w_x = words_in[3 * t + 1], xa.w_t = words_in[3 * t + 2];
+    } else {
+      xa.w_cr = XA::word_cr(t), xa.w_x = XA::word_x(t), xa.w_t = XA::word_t(t);
+    }
+    xa.w = t >> 6;
+    words[3 * t] = xa.w_cr, words[3 * t + 1] = xa.w_x, words[3 * t + 2] = xa.w_t;
+    uint32_t* o = sites + (size_t)MIMO_PROBE_XADDR_SITES * t;
+    o[0] = xa.cross(), o[1] = xa.row(), o[2] = xa.x0r(), o[3] = xa.x1w(), o[4] = xa.x1r();
+    o[5] = xa.template tws<NS1>(), o[6] = xa.template tws<NS2>();
+    o[7] = xa.tw_inv(1), o[8] = xa.tw_inv(2), o[9] = xa.tw_fwd(xa.w);
+  }
+  return MIMO_PROBE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -375,6 +410,13 @@ int32_t mimo_probe_table(int32_t kind, int32_t prec, int32_t F, void* buf, int64
     default:
       return pfail(MIMO_PROBE_EINVAL, "kind must be in [0, 4]");
   }
+}
+
+int32_t mimo_probe_xaddr(int32_t F, const uint32_t* words_in, uint32_t* words, uint32_t* sites, int32_t* info) {
+  if (!words || !sites || !info) return pfail(MIMO_PROBE_EINVAL, "null output");
+  if (!known_size(F) || !wave_fft_used(F, team_size64(F), true))
+    return pfail(MIMO_PROBE_ENOINST, "no wave-split FFT at this size");
+  return F == 1024 ? xaddr_of<1024>(words_in, words, sites, info) : xaddr_of<2048>(words_in, words, sites, info);
 }
 
 }  // extern "C"

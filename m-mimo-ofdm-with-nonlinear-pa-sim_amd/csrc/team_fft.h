@@ -388,6 +388,10 @@ __device__ __forceinline__ void xchg_sync() {
 }
 
 // ---------------------------------------------------------------- team FFT
+// No held LDS addresses (wave_fft.h XAddr is the other kind): every address from the thread id.
+struct NoXA {
+  static constexpr bool on = false;
+};
 // LTW1: stage 1's twiddle block comes from an LDS copy (run()'s tw1 argument; the wave-split
 // FFT's one-wave sub-transforms, whose stage-1 block is small: 64 entries at F 2048) -- all
 // R - 1 twiddles read, none formed as products (fp64: 16 VALU ops per stage saved).
@@ -486,11 +490,33 @@ struct TeamFft {
   }
   template <int S>
   static __host__ __device__ constexpr int pad(int e) { return e + (e >> psh(S)); }
+  // The exchanges' per-thread bases (element indices in the buffer; host mirror: wave_fft.h xa_*).
+  // Transposed exchange 0: element t + T m is read at (t % R0) XS0 + t / R0 + (T / R0) m.
+  static __host__ __device__ constexpr int x0_read(int t) { return (t % R0) * XS0 + t / R0; }
+  // Stage S >= 1 writes butterfly j's outputs at pad(base + r NS), base = (j / NS) NS R + j % NS.
+  template <int S>
+  static __host__ __device__ constexpr int x_write(int j) {
+    return pad<S>((j / (1 << fft_bits_before(F, P, S))) * (1 << (fft_bits_before(F, P, S) + fft_bits(F, P, S))) +
+                  (j & ((1 << fft_bits_before(F, P, S)) - 1)));
+  }
+  static __device__ __forceinline__ C* at(C* base, uint32_t boff) {
+    return reinterpret_cast<C*>(reinterpret_cast<char*>(base) + boff);
+  }
+  static __device__ __forceinline__ const C* at(const C* base, uint32_t boff) {
+    return reinterpret_cast<const C*>(reinterpret_cast<const char*>(base) + boff);
+  }
   // Global-address-space load (the laundered table pointer would otherwise be generic
   // and compile to flat loads, which also count against lgkmcnt with the LDS traffic).
   static __device__ __forceinline__ C gload(const C* p, int i) {
     typedef Re v2f __attribute__((ext_vector_type(2)));
     const v2f v = ((const __attribute__((address_space(1))) v2f*)p)[i];
+    return mkc(v.x, v.y);
+  }
+  // ... at a uniform base plus a 32-bit per-lane byte offset (no 64-bit per-lane arithmetic)
+  static __device__ __forceinline__ C gload_b(const C* base, uint32_t boff) {
+    typedef Re v2f __attribute__((ext_vector_type(2)));
+    const auto* q = (const __attribute__((address_space(1))) char*)base + boff;
+    const v2f v = *(const __attribute__((address_space(1))) v2f*)q;
     return mkc(v.x, v.y);
   }
 
@@ -513,9 +539,9 @@ struct TeamFft {
     return m;
   }
 
-  template <int S, int DIR, int I, uint32_t ZM>
+  template <int S, int DIR, int I, uint32_t ZM, class XA = NoXA>
   static __device__ __forceinline__ void butterfly(C (&d)[P], C* buf, const C (&w0)[1 << bits(S)],
-                                                   int t, bool no_xchg) {
+                                                   int t, bool no_xchg, const XA& xa = XA{}) {
     constexpr int R = 1 << bits(S);
     constexpr int NS = 1 << bits_before(S);
     constexpr int B = P / R;
@@ -557,7 +583,13 @@ struct TeamFft {
       // overwritten.  The barrier sits after this stage's twiddle loads and DFT, so
       // their latency overlaps the previous exchange's reads.
       if constexpr (NBUF == 1 && I == 0) xchg_sync<WAVE>();
-      if constexpr (S == 0 && XP0) {
+      if constexpr (XA::on) {
+        // held addresses (one butterfly per thread and stage: I = 0); buf is the whole array
+        static_assert(I == 0 && S <= 1 && XP0, "XADDR: the three-stage one-wave plan");
+        C* wb = at(buf, S == 0 ? xa.row() : xa.x1w());
+#pragma unroll
+        for (int r = 0; r < R; ++r) wb[S == 0 ? r * XS0 : pad<S>(r * NS)] = v[r];
+      } else if constexpr (S == 0 && XP0) {
         // transposed exchange 0: element R j + r at r XS0 + j
         C* wb = buf + j;
 #pragma unroll
@@ -572,12 +604,12 @@ struct TeamFft {
     }
   }
 
-  template <int S, int DIR, uint32_t ZM, int I = 0>
+  template <int S, int DIR, uint32_t ZM, int I = 0, class XA = NoXA>
   static __device__ __forceinline__ void butterflies(C (&d)[P], C* buf, const C (&w0)[1 << bits(S)],
-                                                     int t, bool no_xchg) {
+                                                     int t, bool no_xchg, const XA& xa = XA{}) {
     if constexpr (I < P / (1 << bits(S))) {
-      butterfly<S, DIR, I, ZM>(d, buf, w0, t, no_xchg);
-      butterflies<S, DIR, ZM, I + 1>(d, buf, w0, t, no_xchg);
+      butterfly<S, DIR, I, ZM>(d, buf, w0, t, no_xchg, xa);
+      butterflies<S, DIR, ZM, I + 1>(d, buf, w0, t, no_xchg, xa);
     }
   }
 
@@ -607,27 +639,34 @@ struct TeamFft {
   struct Base {
     C v[NST][kMaxB];
   };
-  template <int S>
-  static __device__ __forceinline__ void load_base(Base& b, const C* __restrict__ tw, int t) {
+  template <int S, class XA = NoXA>
+  static __device__ __forceinline__ void load_base(Base& b, const C* __restrict__ tw, int t, const XA& xa = XA{}) {
     if constexpr (S < NST) {
       constexpr int R = 1 << bits(S);
       constexpr int NS = 1 << bits_before(S);
       if constexpr (NS > 1 && !(LTW1 && S == 1) && !ct_stage(S)) {
         constexpr int TW_OFF = fft_tw_off(F, P, S);
-        const int jm0 = t & (NS - 1);
+        if constexpr (XA::on) {
+          // held addresses: the lane's byte offset in a row and a uniform base per row
 #pragma unroll
-        for (int k = 0; k < bits(S) && k < kMaxB; ++k)
-          b.v[S][k] = gload(tw + TW_OFF + (1 << k) * NS, jm0);
+          for (int k = 0; k < bits(S) && k < kMaxB; ++k)
+            b.v[S][k] = gload_b(tw + TW_OFF + (1 << k) * NS, xa.template tws<NS>());
+        } else {
+          const int jm0 = t & (NS - 1);
+#pragma unroll
+          for (int k = 0; k < bits(S) && k < kMaxB; ++k)
+            b.v[S][k] = gload(tw + TW_OFF + (1 << k) * NS, jm0);
+        }
         (void)R;
       }
-      load_base<S + 1>(b, tw, t);
+      load_base<S + 1>(b, tw, t, xa);
     }
   }
 
-  template <int S, int DIR, int PAR, uint32_t ZM, typename Fill>
+  template <int S, int DIR, int PAR, uint32_t ZM, typename Fill, class XA = NoXA>
   static __device__ __forceinline__ void stage(C (&d)[P], C* lds, const C* __restrict__ tw, int t,
                                                bool no_xchg, const Base& base, const Fill& fill,
-                                               const C* tw1, C (&wct)[8]) {
+                                               const C* tw1, C (&wct)[8], const XA& xa = XA{}) {
     constexpr int R = 1 << bits(S);
     constexpr int NS = 1 << bits_before(S);
     constexpr int B = P / R;
@@ -642,6 +681,11 @@ struct TeamFft {
       if constexpr (CT_PF) {
 #pragma unroll
         for (int q = 0; q < Q; ++q) w0[q] = wct[q];  // loaded before the previous exchange
+      } else if constexpr (XA::on) {
+        static_assert(WAVE && NBUF == 1, "XADDR: the one-wave sub-transform on one buffer");
+        const C* cts = at(tw1 + ct_off(S), xa.template tws<NS>());
+#pragma unroll
+        for (int q = 0; q < Q; ++q) w0[q] = cts[q * NS];
       } else if constexpr (WAVE) {
         const C* cts = tw1 + ct_off(S) + (t & (NS - 1));
 #pragma unroll
@@ -653,7 +697,9 @@ struct TeamFft {
         for (int q = 0; q < Q; ++q) w0[q] = gload(cts + q * NS, jm0);
       }
     } else if constexpr (NS > 1 && LTW1 && S == 1) {
-      const C* tws = tw1 + (t & (NS - 1));
+      const C* tws;
+      if constexpr (XA::on) tws = at(tw1, xa.template tws<NS>());
+      else tws = tw1 + (t & (NS - 1));
 #pragma unroll
       for (int r = 1; r < R; ++r) w0[r] = tws[r * NS];
     } else if constexpr (NS > 1 && PREFETCH) {
@@ -684,12 +730,16 @@ struct TeamFft {
         }
       }
     }
-    butterflies<S, DIR, ZM>(d, buf, w0, t, no_xchg);
+    butterflies<S, DIR, ZM>(d, buf, w0, t, no_xchg, xa);
     if constexpr (!LAST) {
       if constexpr (CT_PF && ct_stage(S + 1)) load_ct<S + 1>(wct, tw, t);
       if (!no_xchg) {
         xchg_sync<WAVE>();
-        if constexpr (S == 0 && XP0) {
+        if constexpr (XA::on) {
+          const C* rb = at(buf, S == 0 ? xa.x0r() : xa.x1r());
+#pragma unroll
+          for (int m = 0; m < P; ++m) d[m] = rb[S == 0 ? (T / R0) * m : pad<S>(T * m)];
+        } else if constexpr (S == 0 && XP0) {
           // element t + T m at (t % R0) XS0 + t / R0 + (T / R0) m
           const C* rb = buf + (t % R0) * XS0 + t / R0;
 #pragma unroll
@@ -706,13 +756,13 @@ struct TeamFft {
     }
   }
 
-  template <int S, int DIR, int PAR, uint32_t ZM, typename Fill>
+  template <int S, int DIR, int PAR, uint32_t ZM, typename Fill, class XA = NoXA>
   static __device__ __forceinline__ void stages(C (&d)[P], C* lds, const C* __restrict__ tw, int t,
                                                 bool no_xchg, const Base& base, const Fill& fill, const C* tw1,
-                                                C (&wct)[8]) {
+                                                C (&wct)[8], const XA& xa = XA{}) {
     if constexpr (S < NST) {
-      stage<S, DIR, PAR, ZM>(d, lds, tw, t, no_xchg, base, fill, tw1, wct);
-      stages<S + 1, DIR, PAR, ZM>(d, lds, tw, t, no_xchg, base, fill, tw1, wct);
+      stage<S, DIR, PAR, ZM>(d, lds, tw, t, no_xchg, base, fill, tw1, wct, xa);
+      stages<S + 1, DIR, PAR, ZM>(d, lds, tw, t, no_xchg, base, fill, tw1, wct, xa);
     }
   }
 
@@ -728,7 +778,10 @@ struct TeamFft {
   // The twiddles and LDS addresses depend only on the thread id, so inside the
   // caller's antenna loop LICM would hoist all of them (~60 VGPRs) out of the loop and
   // spill.  Laundering t and tw through empty asm makes them opaque per transform:
-  // they are re-derived (cheap ALU + L1-hit loads) instead of held.
+  // they are re-derived (ALU + L1-hit loads) instead of held.  (Cheap while the kernel waited
+  // on LDS; of a VALU-bound loop the integer arithmetic was ~7 % of the instructions, so the
+  // fp64 wave-split instances hold the addresses instead, packed two per VGPR, and launder
+  // those words: run_x below, wave_fft.h XAddr, tuning.h MIMO_XADDR.)
   //
   // ZM: registers d[m] (bit m) that are zero in every thread on entry (the IFFT's
   // out-of-band bins); stage 0 skips their additions.
@@ -747,6 +800,20 @@ struct TeamFft {
     if constexpr (PREFETCH) load_base<1>(base, twl, tl);
     C wct[8];
     stages<0, DIR, PAR, ZM>(d, lds, twl, tl, no_xchg, base, fill, tw1, wct);
+  }
+  // The one-wave sub-transform of wave_fft.h on addresses its caller holds (XADDR: xa, already
+  // laundered for this transform; lds is the team's whole exchange array, the wave's row is in
+  // the addresses).  The thread id is not needed: stage 1's constants come from the LDS copy tw1,
+  // stage 2's from it too (cot-tan form) or as prefetched bases from the table tw (already opaque).
+  template <int DIR, int PAR, uint32_t ZM, typename Fill, class XA>
+  static __device__ __forceinline__ void run_x(C (&d)[P], C* lds, const C* __restrict__ tw, bool no_xchg,
+                                               const Fill& fill, const C* tw1, const XA& xa) {
+    static_assert(XA::on && WAVE && LTW1 && NBUF == 1 && NST == 3 && (CT || (PREFETCH && !LTW2)),
+                  "XADDR: the three-stage one-wave plan");
+    Base base;
+    if constexpr (!CT) load_base<1>(base, tw, 0, xa);
+    C wct[8];
+    stages<0, DIR, PAR, ZM>(d, lds, tw, 0, no_xchg, base, fill, tw1, wct, xa);
   }
   // IFFT then FFT of one antenna / CNC iteration: an even number of exchanges in total.
   template <int DIR, typename Fill = NoFill>

@@ -873,6 +873,27 @@ using trial_fft_t = std::conditional_t<
     std::conditional_t<split_fft_used(F, T, sizeof(R) == 8), SplitFft<F, T, NBUF, R>,
                        TeamFft<F, T, NBUF, R, false, false, false, sizeof(R) == 8 && F <= 4096>>>;
 
+// The held transform addresses of an instance (wave_fft.h XAddr), or nothing.
+template <class FFT, bool ON>
+struct XAddrOf {
+  using type = NoXA;
+};
+template <class FFT>
+struct XAddrOf<FFT, true> {
+  using type = typename FFT::XAddr;
+};
+// Instances that hold them (tuning.h MIMO_XADDR): the fp64 wave-split instances without CSI whose
+// scratch does not grow with the three words (profiles/r22/xaddr/resources.txt; one that grows,
+// by 16 to 64 B / lane, keeps re-deriving).  Per size and run mode a mask
+// over (aligned ? 0 : 4) + channel kind - 1 of the instances left out.
+constexpr bool xaddr_inst_ok(int F, int mode, bool aligned, int ch) {
+  constexpr unsigned out1024[7] = {0x91, 0x82, 0x81, 0x91, 0x00, 0xD8, 0xD1};
+  constexpr unsigned out2048[7] = {0x80, 0x90, 0x00, 0x80, 0x20, 0x40, 0x80};
+  if (mode < 0 || mode > 6 || ch < 1 || ch > 4) return false;
+  const unsigned bit = 1u << ((aligned ? 0 : 4) + ch - 1);
+  return F == 1024 ? !(out1024[mode] & bit) : F == 2048 ? !(out2048[mode] & bit) : false;
+}
+
 // Box-Muller tables (real.h ln_unit / sincos_lut) into LDS, by the whole team; the caller
 // barriers before the first read.  p: the kernel parameters, or anything with their `lut`
 // (a pointer, not a reference: the table pointer is then loaded where the kernel always
@@ -1393,6 +1414,15 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
   static_assert(SUBH >= 1 && (SUBH & (SUBH - 1)) == 0 && SUBH <= 64, "a power of two of lane residues");
   __shared__ uint32_t env_hist[ENV ? 2 * kEnvBins * SUBH : 1];
   R en_pin = R(0), en_pout = R(0), en_cre = R(0), en_cim = R(0);
+  // XADDR (tuning.h; fp64 wave-split instances without CSI): the thread's LDS addresses of the two
+  // transforms, packed two per word (wave_fft.h XAddr), formed here once per trial and held
+  // through the main pass and the MCNC passes; the transforms launder the words, not the thread
+  // id.  The receiver-phase transforms (once per iteration) keep re-deriving.
+  constexpr bool XADDR =
+      MIMO_XADDR != 0 && WAVEFFT && sizeof(R) == 8 && !CSI && xaddr_inst_ok(F, MIMO_INST_MODE, ALIGNED, CH);
+  using XAD = typename XAddrOf<FFT, XADDR>::type;
+  XAD xaddr;
+  if constexpr (XADDR) xaddr.set(t, __builtin_amdgcn_readfirstlane(wid));
   auto array_pass = [&](bool main_pass, C (&acc)[NSLOT]) __attribute__((always_inline)) {
 #pragma unroll
     for (int s = 0; s < NSLOT; ++s) acc[s] = czero<R>();
@@ -1536,9 +1566,13 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
       // the FFTs take the thread id already laundered for this antenna (tl) where it is the
       // physical one: their own opaque copy of it then costs no register move in run_second
       const int tfft = SPLITFFT ? t : tl;
-      if (!MIMO_ABL(p, ABL_FFT))
-        FFT::template run<+1, 0, SL::zero_mask()>(d, lds, WAVEFFT ? p.tw_wave : p.tw, tfft, MIMO_ABL(p, ABL_XCHG), hfill_ifft,
-                                                  tw1);
+      if (!MIMO_ABL(p, ABL_FFT)) {
+        if constexpr (XADDR)
+          FFT::template run<+1, 0, SL::zero_mask()>(d, lds, p.tw_wave, xaddr, tfft, MIMO_ABL(p, ABL_XCHG), hfill_ifft, tw1);
+        else
+          FFT::template run<+1, 0, SL::zero_mask()>(d, lds, WAVEFFT ? p.tw_wave : p.tw, tfft, MIMO_ABL(p, ABL_XCHG),
+                                                    hfill_ifft, tw1);
+      }
       C xin[ENV ? P : 1];  // envelope instances: the PA input, held across pa_block
       if constexpr (ENV) {
         if (main_pass) {
@@ -1633,8 +1667,12 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
           if (lane == 0) alpha_s[vkb] = al;
         }
       }
-      if (!MIMO_ABL(p, ABL_FFT))
-        FFT::template run_second<-1>(d, lds, WAVEFFT ? p.tw_wave : p.tw, tfft, MIMO_ABL(p, ABL_XCHG), hfill_fft, tw1);
+      if (!MIMO_ABL(p, ABL_FFT)) {
+        if constexpr (XADDR)
+          FFT::template run_second<-1>(d, lds, p.tw_wave, xaddr, tfft, MIMO_ABL(p, ABL_XCHG), hfill_fft, tw1);
+        else
+          FFT::template run_second<-1>(d, lds, WAVEFFT ? p.tw_wave : p.tw, tfft, MIMO_ABL(p, ABL_XCHG), hfill_fft, tw1);
+      }
       if constexpr (PIPE) {
         if (MIMO_ABL(p, ABL_FFT)) {  // no transforms ran, so no exchange windows (ABL_XCHG keeps them)
 #pragma unroll

@@ -99,6 +99,35 @@
 #define MIMO_BM_SIN_DEG 5
 #endif
 
+// ---- the transforms' LDS and twiddle addresses of the fp64 wave-split instances without CSI held
+// across the antenna loop, two 16-bit byte addresses per VGPR (wave_fft.h XAddr; three words),
+// instead of re-derived from the thread id by every transform.  The words are what the transforms
+// launder, in place, so the unpacked forms are not hoisted (team_fft.h run).  Every LDS byte
+// address of these teams is below 34,816 and a multiple of 16 (static_assert in wave_fft.h, and
+// every thread's and use site's by tests/test_xaddr_host.py).  Outputs bit for bit the parent's.
+// XADDR: the LDS addresses -- the cross-wave base 16 t, the wave's row plus lane, the sub-transform's
+// transposed exchange 0 read, exchange 1's padded write and read, the lane's offset in the rows of
+// the stage constants; one v_and_b32 / v_lshrrev_b32 per use.  At F 1024 (two waves, stage
+// twiddles instead of cot-tan constants) stage 2's base twiddles are loaded at that offset from
+// a uniform base as well.  XADDR_TW, on top of it (nothing without it): the inter-step twiddle
+// loads take a 32-bit per-lane byte offset (16 k t; 16 w l) and a wave-uniform base per butterfly
+// / register formed on the SALU per transform, instead of 64-bit per-lane arithmetic.
+// Config 2, 100 interleaved rounds, A/A spread 0.01 ms (profiles/r22/xaddr/ab_switches.json): both
+// off 43.60 ms (= the parent, 43.61), XADDR alone -0.29 ms (-0.7 %), both -0.75 ms (-1.7 %, 42.86 ms
+// in ab_long.json); 2mcnc -0.78 / -2.36 ms of 122.8 (-1.9 %), 2los -0.18 / -0.67 ms of 40.1 (-1.7 %).
+// Static VALU per antenna of the config-2 instance: every wave 941 -> 907 -> 894, waves 1-3 add
+// 50 -> 50 -> 34; SQ_INSTS_VALU 1,154.3 -> 1,095.9 per antenna-wave (-58.4, static -59.0), VGPRs
+// 168, LDS 53,296 B and the loops free of scratch as before.  Time follows the count less than in
+// rounds 16 / 17 (-5.1 % instructions, -1.7 % time): what went are full-rate 32-bit integer
+// operations, and VALU busy fell from 0.815 to 0.785 of the SIMD.  An instance whose scratch would
+// grow keeps re-deriving (trial_kernel.h xaddr_inst_ok).
+#ifndef MIMO_XADDR
+#define MIMO_XADDR 1
+#endif
+#ifndef MIMO_XADDR_TW
+#define MIMO_XADDR_TW 1
+#endif
+
 // ---- Philox rounds whose words are uniform across the team on the SALU (philox.h kUni)
 // Always in the fp64 wave-split instances (F <= 2048).  F 4096: with CSI only (-2.4 % on the
 // paper-CSI line, +1.1 % without CSI, profiles/r06/k4096/).  F 8192: with the folded weight
