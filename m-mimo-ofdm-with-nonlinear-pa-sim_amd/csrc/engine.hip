@@ -13,6 +13,7 @@
 #include <cstring>
 #include <limits>
 #include <string>
+#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -261,11 +262,23 @@ mimo::InstanceKey select_instance(const mimo_engine* e, bool csi) {
   return k;
 }
 
-// The launcher of the key's instance in the given mode (trial_launch.h launch_trial).  The only
-// table over the FFT sizes; the combinations that are not built are not found.
+// The mode arguments of a launch (trial_kernel.h ModeArgs), built here alone: the engine's buffer
+// that the mode's instances fill -- the launch's rows; the beam instances its cells and the coded
+// instances its channel values, from which the mode's second kernel forms the rows -- and the scale.
+template <int MODE>
+mimo::ModeArgs<MODE> mode_args(const mimo_engine* e, double scale) {
+  if constexpr (MODE == MIMO_MODE_PLAIN) return {};
+  else if constexpr (MODE == MIMO_MODE_BEAM) return {e->bcell.p};
+  else if constexpr (MODE == MIMO_MODE_CODED) return {e->cchan.p, scale};
+  else if constexpr (std::tuple_size_v<mimo::ModeArgs<MODE>> == 2) return {e->rows.p, scale};
+  else return {e->rows.p};
+}
+
+// The launcher of the key's instance in the given mode (trial_launch.h launch_trial), on the engine's
+// stream.  The only table over the FFT sizes; the combinations that are not built are not found.
 template <typename R, int MODE>
-hipError_t launch_sized(const mimo::InstanceKey& k, dim3 grid, hipStream_t st, const mimo::TrialParams<R>& p,
-                        bool* found, hipFuncAttributes* attr, double* out, double aux) {
+hipError_t launch_sized(const mimo_engine* e, const mimo::InstanceKey& k, dim3 grid, const mimo::TrialParams<R>& p,
+                        bool* found, hipFuncAttributes* attr, double scale) {
   *found = false;
 #if defined(MIMO_ONLY_F) && defined(MIMO_ONLY_MEAS)  // A-B builds (Makefile target variant): plain and measure
   constexpr bool built = MODE == MIMO_MODE_PLAIN || (MODE == MIMO_MODE_MEAS && sizeof(R) == 8);
@@ -276,7 +289,7 @@ hipError_t launch_sized(const mimo::InstanceKey& k, dim3 grid, hipStream_t st, c
 #endif
   if constexpr (built) {
 #define MIMO_LAUNCH_F(FV) \
-  case FV: return mimo::launch_trial<FV, R, MODE>(k, grid, st, p, found, attr, out, aux);
+  case FV: return mimo::launch_trial<FV, R, MODE>(k, grid, e->stream, p, found, attr, mode_args<MODE>(e, scale));
     switch (k.F) {
 #ifdef MIMO_ONLY_F
       MIMO_LAUNCH_F(MIMO_ONLY_F)
@@ -297,16 +310,19 @@ hipError_t launch_sized(const mimo::InstanceKey& k, dim3 grid, hipStream_t st, c
 }
 
 template <typename R>
-hipError_t launch(int mode, const mimo::InstanceKey& k, dim3 grid, hipStream_t st, const mimo::TrialParams<R>& p,
-                  bool* found, hipFuncAttributes* attr, double* out, double aux = 0.0) {
+hipError_t launch(int mode, const mimo_engine* e, const mimo::InstanceKey& k, dim3 grid, const mimo::TrialParams<R>& p,
+                  bool* found, hipFuncAttributes* attr, double scale = 0.0) {
   switch (mode) {
-    case MIMO_MODE_MEAS: return launch_sized<R, MIMO_MODE_MEAS>(k, grid, st, p, found, attr, out, aux);
-    case MIMO_MODE_SPEC: return launch_sized<R, MIMO_MODE_SPEC>(k, grid, st, p, found, attr, out, aux);
-    case MIMO_MODE_BEAM: return launch_sized<R, MIMO_MODE_BEAM>(k, grid, st, p, found, attr, out, aux);
-    case MIMO_MODE_ENV: return launch_sized<R, MIMO_MODE_ENV>(k, grid, st, p, found, attr, out, aux);
-    case MIMO_MODE_SOFT: return launch_sized<R, MIMO_MODE_SOFT>(k, grid, st, p, found, attr, out, aux);
-    case MIMO_MODE_CODED: return launch_sized<R, MIMO_MODE_CODED>(k, grid, st, p, found, attr, out, aux);
-    default: return launch_sized<R, MIMO_MODE_PLAIN>(k, grid, st, p, found, attr, out, aux);
+#define MIMO_LAUNCH_MODE(M) \
+  case M: return launch_sized<R, M>(e, k, grid, p, found, attr, scale);
+    MIMO_LAUNCH_MODE(MIMO_MODE_MEAS)
+    MIMO_LAUNCH_MODE(MIMO_MODE_SPEC)
+    MIMO_LAUNCH_MODE(MIMO_MODE_BEAM)
+    MIMO_LAUNCH_MODE(MIMO_MODE_ENV)
+    MIMO_LAUNCH_MODE(MIMO_MODE_SOFT)
+    MIMO_LAUNCH_MODE(MIMO_MODE_CODED)
+#undef MIMO_LAUNCH_MODE
+    default: return launch_sized<R, MIMO_MODE_PLAIN>(e, k, grid, p, found, attr, scale);
   }
 }
 
@@ -314,6 +330,7 @@ hipError_t launch(int mode, const mimo::InstanceKey& k, dim3 grid, hipStream_t s
 // (mimo_engine_beam_points): geo = dist [n_probes][A] | 1 / dist [n_probes][A] | f / c [F].
 struct BeamCall {
   int n_probes;
+  uint64_t buffer;  // bytes the cells of one launch may take: one trial's at least
   std::vector<double> geo;
 };
 
@@ -326,39 +343,74 @@ struct CodedCall {
   int8_t* per_trial_chan = nullptr;  // [trials of the call][n_idx][stream], or null
 };
 
-// What a row mode adds to a plain run, filled once by the extern "C" entry point of the mode:
-//  measure (mimo_engine_measure_points): the measure instance runs, and its per-trial rows of
-//   MIMO_MEAS_FIXED + n_idx sums are reduced per slice on the device (reduce_meas) and per point,
-//   in slice order, on the host;
-//  spectrum (mimo_engine_spectrum_points): rows of n_fft + MIMO_SPEC_FIXED sums; the spectrum
-//   instance runs, reduce_spec forms the slice partials, and a launch holds no more trials than
-//   its rows fit MIMO_SPEC_BUFFER_BYTES;
-//  beam (mimo_engine_beam_points): rows of n_probes MIMO_BEAM_FIXED sums; the beam instance runs
-//   and fills the launch's cells, the beamforming kernel (beam.hip) forms the per-trial rows from
-//   them, reduce_spec the slice partials; the cells and rows of a launch fit their buffers;
-//  envelope (mimo_engine_envelope_points): rows of 2 MIMO_ENV_BINS + MIMO_ENV_FIXED sums (the two
-//   histograms' cells are integers in doubles); the envelope instance runs with the bin scale
-//   1.0625 / ref_pow as its second extra argument, reduce_spec forms the slice partials, and a
-//   launch holds no more trials than its rows fit MIMO_ENV_BUFFER_BYTES;
-//  soft (mimo_engine_soft_points): rows of n_idx MIMO_SOFT_BINS histogram cells (integers in
-//   doubles); the soft instance runs with the bin scale 128 / rho_max as its second extra
-//   argument, reduce_spec forms the slice partials, and a launch holds no more trials than its
-//   rows fit MIMO_SOFT_BUFFER_BYTES;
-//  coded (mimo_engine_coded_points): rows of n_idx MIMO_CODED_FIXED counts (integers in doubles); the
-//   coded instance runs with the scale 32 / rho_max as its second extra argument and fills the
-//   launch's channel values, the decoder kernel (ldpc.hip) forms the per-trial rows from them,
-//   reduce_spec the slice partials; the channel values of a launch fit MIMO_CODED_BUFFER_BYTES.
+// What a row mode adds to a plain run, filled by the extern "C" entry point of the mode.  The mode's
+// instances run and leave per-trial rows of row_width doubles, which are reduced per slice on the
+// device (reduce_spec; measure: reduce_meas) and per point, in slice order, on the host; a launch
+// holds no more trials than the mode's buffer fits (launch_trials).  Particular to a mode:
+//  envelope, soft, coded: the instances take a scale;
+//  beam, coded: the instances fill the launch's cells / channel values instead, and a second kernel
+//   (beam.hip, ldpc.hip) forms the rows from them, from the call's tables (launch_second).
 struct RowMode {
   int mode = MIMO_MODE_PLAIN;
-  int width = 0;                        // doubles of one trial's row, and of one point's in out
-  uint64_t max_trials = UINT64_MAX;     // of one launch, where the mode's buffers bound them
   double* out = nullptr;                // [points][width], added into
   double* per_trial_out = nullptr;      // [trials of the call][width], or null
+  double scale = 0.0;                   // envelope, soft, coded
   const BeamCall* beam = nullptr;       // beam only
   const CodedCall* coded = nullptr;     // coded only
-  double aux = 0.0;                     // envelope, soft, coded: the kernel's bin scale
+  int width = 0;                        // row_width, once run_points has checked the iteration list
   bool rows() const { return mode != MIMO_MODE_PLAIN; }
+  bool second() const { return beam || coded; }
 };
+
+// Doubles of one trial's row in a mode, and of one point's in the mode's output: what the
+// mimo_*_width functions return and the callers allocate.
+int row_width(int mode, int n_fft, int n_idx, int n_probes) {
+  switch (mode) {
+    case MIMO_MODE_MEAS: return MIMO_MEAS_FIXED + n_idx;
+    case MIMO_MODE_SPEC: return n_fft + MIMO_SPEC_FIXED;
+    case MIMO_MODE_BEAM: return n_probes * MIMO_BEAM_FIXED;
+    case MIMO_MODE_ENV: return 2 * MIMO_ENV_BINS + MIMO_ENV_FIXED;
+    case MIMO_MODE_SOFT: return MIMO_SOFT_BINS * n_idx;
+    case MIMO_MODE_CODED: return MIMO_CODED_FIXED * n_idx;
+    default: return 0;
+  }
+}
+
+// A limit that an environment variable lowers, for measurements and tests of the splitting: the
+// variable's value in units, where that is in [1, limit).
+uint64_t env_lowered(const char* name, uint64_t limit, uint64_t unit = 1) {
+  if (const char* env = std::getenv(name)) {
+    const uint64_t v = std::strtoull(env, nullptr, 10) / unit;
+    if (v >= 1 && v < limit) return v;
+  }
+  return limit;
+}
+
+// The cells of one trial of a beam launch: Y and X of every antenna and bin, complex128.
+uint64_t beam_trial_bytes(const mimo_config& c) { return 2ull * (uint64_t)c.n_ant * (uint64_t)c.n_fft * 16ull; }
+
+// The trials one launch may hold (0: not one fits): what the mode's buffer fits -- the rows'
+// (measure: no bound), for beam the cells' too, for coded the channel values' instead -- and on a
+// TDL engine the bank entries that fit MIMO_BANK_BUFFER_BYTES.
+uint64_t launch_trials(const mimo_config& c, const RowMode& rm, int n_idx) {
+  const uint64_t row = sizeof(double) * (uint64_t)rm.width;
+  uint64_t n = UINT64_MAX;
+  switch (rm.mode) {
+    case MIMO_MODE_SPEC: n = MIMO_SPEC_BUFFER_BYTES / row; break;
+    case MIMO_MODE_BEAM: n = std::min<uint64_t>(rm.beam->buffer / beam_trial_bytes(c), MIMO_BEAM_ROWS_BYTES / row); break;
+    case MIMO_MODE_ENV: n = MIMO_ENV_BUFFER_BYTES / row; break;
+    case MIMO_MODE_SOFT: n = MIMO_SOFT_BUFFER_BYTES / row; break;
+    case MIMO_MODE_CODED: n = MIMO_CODED_BUFFER_BYTES / (rm.coded->stream * (size_t)n_idx); break;
+    default: break;
+  }
+  if (c.channel_kind == MIMO_CH_TDL) {
+    const uint64_t entry = (uint64_t)c.n_ant * (uint64_t)c.n_sub_carr *
+                           (c.precision == MIMO_PREC_F32 ? sizeof(float2) : sizeof(double2));
+    n = std::min(n, env_lowered("MIMO_BANK_BUFFER_BYTES", (uint64_t)mimo_bank_capacity(c.n_ant, c.n_sub_carr, c.precision),
+                                entry));
+  }
+  return n;
+}
 
 int validate_config(const mimo_config* c) {
   if (!c) return fail(MIMO_EINVAL, "null config");
@@ -709,8 +761,8 @@ int check_csi_lds(const mimo_engine* e, const mimo::InstanceKey& key, int mode) 
   hipFuncAttributes fa{};
   bool found = false;
   const hipError_t qe =
-      key.f64 ? launch(mode, key, dim3(0), e->stream, mimo::TrialParams<double>{}, &found, &fa, nullptr)
-              : launch(MIMO_MODE_PLAIN, key, dim3(0), e->stream, mimo::TrialParams<float>{}, &found, &fa, nullptr);
+      key.f64 ? launch(mode, e, key, dim3(0), mimo::TrialParams<double>{}, &found, &fa)
+              : launch(MIMO_MODE_PLAIN, e, key, dim3(0), mimo::TrialParams<float>{}, &found, &fa);
   int lds_max = 0;
   if (!found || qe != hipSuccess ||
       hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, e->device) != hipSuccess ||
@@ -741,12 +793,7 @@ struct Plan {
 // max_trials: what the mode's buffers allow in one launch.  Without it a launch holds 2^20 trials
 // (MIMO_MAX_LAUNCH_TRIALS lowers it, for tests of the splitting).
 Plan plan_launches(int n_points, const uint64_t* first_trial, const uint64_t* n_trials, uint64_t max_trials) {
-  uint64_t chunk = 1ull << 20;
-  if (const char* env = std::getenv("MIMO_MAX_LAUNCH_TRIALS")) {
-    const uint64_t v = std::strtoull(env, nullptr, 10);
-    if (v >= 1 && v < chunk) chunk = v;
-  }
-  chunk = std::min(chunk, max_trials);
+  const uint64_t chunk = std::min(env_lowered("MIMO_MAX_LAUNCH_TRIALS", 1ull << 20), max_trials);
   Plan plan;
   uint64_t fill = 0;
   for (int i = 0; i < n_points; ++i) {
@@ -850,7 +897,7 @@ struct Progress {
   // row modes: the slice partials of every launch, in launch and slice order, and their points
   std::vector<double> part;
   std::vector<int> part_point;
-  double ms = 0.0, beam_ms = 0.0, decode_ms = 0.0, chan_ms = 0.0;
+  double ms = 0.0, second_ms = 0.0, chan_ms = 0.0;  // trial kernel, second kernel (RowMode), TDL generator
 };
 
 // The tables of one launch, written into the host blob: the segments' parameters and block
@@ -887,8 +934,53 @@ LaunchTables fill_launch_tables(char* h_blob, const BlobLayout& o, const std::ve
   return t;
 }
 
-// One launch: its tables into the blob, the trial kernel of the mode, for beam the beamforming
-// kernel, for coded the decoder kernel, the count and row reductions and the copies back; waits for the launch and times it.
+// The second kernel of a beam or coded call (RowMode).  Before the first launch: its buffers for
+// the largest launch of the plan, and the call's tables uploaded.
+int prepare_second(mimo_engine* e, const RowMode& rm, const Plan& plan, int n_idx) {
+  const mimo_config& c = e->cfg;
+  if (rm.beam) {
+    const size_t cells = 2 * plan.max_blocks * (size_t)c.n_ant * (size_t)c.n_fft * 2;  // doubles
+    if (int rc = e->bcell.ensure(std::max<size_t>(2, cells))) return rc;
+    if (int rc = e->bgeo.ensure(rm.beam->geo.size())) return rc;
+    HIP_TRY(hipMemcpyAsync(e->bgeo.p, rm.beam->geo.data(), sizeof(double) * rm.beam->geo.size(), hipMemcpyHostToDevice,
+                           e->stream));
+  } else {
+    const std::vector<int32_t>& tab = rm.coded->code.tables;
+    if (int rc = e->cchan.ensure(std::max<size_t>(1, plan.max_blocks * (size_t)n_idx * rm.coded->stream))) return rc;
+    if (int rc = e->ctab.ensure(tab.size())) return rc;
+    HIP_TRY(hipMemcpyAsync(e->ctab.p, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice, e->stream));
+  }
+  return MIMO_OK;
+}
+
+// In a launch, behind the trial kernel: the rows of its nb trials from what the instances left, ev2
+// behind it (run_launch times ev1 to ev2), and a coded call's channel values copied back where asked.
+int launch_second(mimo_engine* e, const RowMode& rm, uint32_t nb, int n_idx, uint64_t trials_done) {
+  hipError_t se = hipSuccess;
+  if (const CodedCall* cc = rm.coded) {
+    se = mimo::launch_ldpc(e->stream, cc->code, e->ctab.p, e->cchan.p, (int64_t)nb * n_idx, (int64_t)cc->stream, cc->n_cw,
+                           cc->n_cw, e->rows.p, nullptr);
+  } else {
+#ifndef MIMO_ONLY_F  // (the single-size diagnostic builds find no beam instance to launch before this)
+    const mimo_config& c = e->cfg;
+    const size_t na = (size_t)rm.beam->n_probes * (size_t)c.n_ant;
+    se = mimo::launch_beam(e->stream, e->bcell.p, e->bgeo.p, e->bgeo.p + na, e->bgeo.p + 2 * na, (int)nb, c.n_ant, c.n_fft,
+                           c.n_sub_carr, rm.beam->n_probes, e->rows.p);
+#endif
+  }
+  if (se != hipSuccess)
+    return fail(MIMO_EHIP, std::string(rm.coded ? "decoder" : "beamforming") + " kernel launch: " + hipGetErrorString(se));
+  HIP_TRY(hipEventRecord(e->ev2, e->stream));
+  if (rm.coded && rm.coded->per_trial_chan) {
+    const size_t per_trial = (size_t)n_idx * rm.coded->stream;
+    HIP_TRY(hipMemcpyAsync(rm.coded->per_trial_chan + trials_done * per_trial, e->cchan.p, (size_t)nb * per_trial,
+                           hipMemcpyDeviceToHost, e->stream));
+  }
+  return MIMO_OK;
+}
+
+// One launch: its tables into the blob, the trial kernel of the mode, the mode's second kernel, the
+// count and row reductions and the copies back; waits for the launch and times it.
 template <typename R>
 int run_launch(mimo_engine* e, const mimo::InstanceKey& key, const mimo::TrialParams<R>& base,
                const std::vector<mimo::TrialParams<R>>& ptab, const BlobLayout& o, const std::vector<Seg>& segs,
@@ -925,34 +1017,12 @@ int run_launch(mimo_engine* e, const mimo::InstanceKey& key, const mimo::TrialPa
   }
   HIP_TRY(hipEventRecord(e->ev0, e->stream));
   bool found = false;
-  // (the beam instances fill the launch's cells; the beamforming kernel forms the rows from them.
-  // The coded instances fill the launch's channel values, int8 behind the same pointer; the decoder
-  // kernel forms the rows from them)
-  double* const inst_out = rm.beam ? e->bcell.p : rm.coded ? reinterpret_cast<double*>(e->cchan.p) : e->rows.p;
-  const hipError_t le = launch(rm.mode, key, dim3(nb), e->stream, kp, &found, nullptr, inst_out, rm.aux);
+  const hipError_t le = launch(rm.mode, e, key, dim3(nb), kp, &found, nullptr, rm.scale);
   if (!found) return fail(MIMO_ENOKERNEL, "no kernel instance for " + e->desc);
   if (le != hipSuccess) return fail(MIMO_EHIP, std::string("trial kernel launch: ") + hipGetErrorString(le));
   HIP_TRY(hipEventRecord(e->ev1, e->stream));
-#ifndef MIMO_ONLY_F  // (the single-size diagnostic builds found no beam instance above)
-  if (rm.beam) {
-    const mimo_config& c = e->cfg;
-    const size_t na = (size_t)rm.beam->n_probes * (size_t)c.n_ant;
-    const hipError_t be = mimo::launch_beam(e->stream, e->bcell.p, e->bgeo.p, e->bgeo.p + na, e->bgeo.p + 2 * na,
-                                            (int)nb, c.n_ant, c.n_fft, c.n_sub_carr, rm.beam->n_probes, e->rows.p);
-    if (be != hipSuccess) return fail(MIMO_EHIP, std::string("beamforming kernel launch: ") + hipGetErrorString(be));
-    HIP_TRY(hipEventRecord(e->ev2, e->stream));
-  }
-#endif
-  if (rm.coded) {
-    const CodedCall& cc = *rm.coded;
-    const hipError_t de = mimo::launch_ldpc(e->stream, cc.code, e->ctab.p, e->cchan.p, (int64_t)nb * n_idx,
-                                            (int64_t)cc.stream, cc.n_cw, cc.n_cw, e->rows.p, nullptr);
-    if (de != hipSuccess) return fail(MIMO_EHIP, std::string("decoder kernel launch: ") + hipGetErrorString(de));
-    HIP_TRY(hipEventRecord(e->ev2, e->stream));
-    if (cc.per_trial_chan)
-      HIP_TRY(hipMemcpyAsync(cc.per_trial_chan + pg->trials_done * (size_t)n_idx * cc.stream, e->cchan.p,
-                             (size_t)nb * n_idx * cc.stream, hipMemcpyDeviceToHost, e->stream));
-  }
+  if (rm.second())
+    if (int rc = launch_second(e, rm, nb, n_idx, pg->trials_done)) return rc;
   hipLaunchKernelGGL(reduce_counts, dim3((unsigned)nsl, n_idx), dim3(256), 0, e->stream, e->counts.p, d_slice_first,
                      reinterpret_cast<const int32_t*>(e->blob.p + o.point_of), n_idx, e->tot.p);
   HIP_TRY(hipGetLastError());
@@ -985,15 +1055,10 @@ int run_launch(mimo_engine* e, const mimo::InstanceKey& key, const mimo::TrialPa
     HIP_TRY(hipEventElapsedTime(&ms, e->ev3, e->ev0));
     pg->chan_ms += ms;
   }
-  if (rm.beam) {
+  if (rm.second()) {
     HIP_TRY(hipEventSynchronize(e->ev2));
     HIP_TRY(hipEventElapsedTime(&ms, e->ev1, e->ev2));
-    pg->beam_ms += ms;
-  }
-  if (rm.coded) {
-    HIP_TRY(hipEventSynchronize(e->ev2));
-    HIP_TRY(hipEventElapsedTime(&ms, e->ev1, e->ev2));
-    pg->decode_ms += ms;
+    pg->second_ms += ms;
   }
   return MIMO_OK;
 }
@@ -1016,9 +1081,10 @@ int run_launches(mimo_engine* e, const mimo::InstanceKey& key, const mimo::Trial
 
 // Runs n_points grid points of one system in as few launches as possible (plan_launches), and a
 // segmented reduction sums each point's counts; rm: the rows a mode adds (RowMode; none: plain).
+// The row's width and the trials of a launch come from the iteration list once it is checked.
 int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64_t* seeds,
                const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters, int32_t n_iters,
-               int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out, uint32_t* per_trial, const RowMode& rm) {
+               int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out, uint32_t* per_trial, RowMode rm) {
   if (n_points < 0) return fail(MIMO_EINVAL, "n_points must be >= 0");
   Iters it;
   if (int rc = validate_iters(iters, n_iters, &it)) return rc;
@@ -1027,6 +1093,7 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
   if (!pts || !seeds || !first_trial || !n_trials) return fail(MIMO_EINVAL, "null point arrays");
   const int n_idx = n_iters + (incl_clean ? 1 : 0);
   const mimo_config& c = e->cfg;
+  rm.width = row_width(rm.mode, c.n_fft, n_idx, rm.beam ? rm.beam->n_probes : 0);
   bool csi = false;
   if (int rc = validate_points(e, n_points, pts, first_trial, n_trials, &csi)) return rc;
   if (int rc = validate_distances(e)) return rc;
@@ -1049,17 +1116,7 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
   }
   e->desc = describe(key);
 
-  // a TDL launch holds no more trials than bank entries fit MIMO_BANK_BUFFER_BYTES
-  uint64_t max_trials = rm.max_trials;
-  if (tdl) {
-    uint64_t cap = (uint64_t)mimo_bank_capacity(c.n_ant, c.n_sub_carr, c.precision);
-    if (const char* env = std::getenv("MIMO_BANK_BUFFER_BYTES")) {  // lowers it, for measurements and tests of the splitting
-      const uint64_t v = std::strtoull(env, nullptr, 10) /
-                         ((uint64_t)c.n_ant * (uint64_t)c.n_sub_carr * (key.f64 ? sizeof(double2) : sizeof(float2)));
-      if (v >= 1 && v < cap) cap = v;
-    }
-    max_trials = std::min(max_trials, cap);
-  }
+  const uint64_t max_trials = launch_trials(c, rm, n_idx);
   if (max_trials < 1) return fail(MIMO_EINVAL, "n_ant, n_sub_carr: one trial's channel does not fit the bank buffer");
   const Plan plan = plan_launches(n_points, first_trial, n_trials, max_trials);
   if (tdl) {
@@ -1073,19 +1130,8 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
     pg.part.resize(plan.tot_slices * rm.width);
     pg.part_point.reserve(plan.tot_slices);
   }
-  if (rm.beam) {
-    const size_t cells = 2 * plan.max_blocks * (size_t)c.n_ant * (size_t)c.n_fft * 2;  // doubles
-    if (int rc = e->bcell.ensure(std::max<size_t>(2, cells))) return rc;
-    if (int rc = e->bgeo.ensure(rm.beam->geo.size())) return rc;
-    HIP_TRY(hipMemcpyAsync(e->bgeo.p, rm.beam->geo.data(), sizeof(double) * rm.beam->geo.size(), hipMemcpyHostToDevice,
-                           e->stream));
-  }
-  if (rm.coded) {
-    if (int rc = e->cchan.ensure(std::max<size_t>(1, plan.max_blocks * (size_t)n_idx * rm.coded->stream))) return rc;
-    if (int rc = e->ctab.ensure(rm.coded->code.tables.size())) return rc;
-    HIP_TRY(hipMemcpyAsync(e->ctab.p, rm.coded->code.tables.data(), sizeof(int32_t) * rm.coded->code.tables.size(),
-                           hipMemcpyHostToDevice, e->stream));
-  }
+  if (rm.second())
+    if (int rc = prepare_second(e, rm, plan, n_idx)) return rc;
   if (int rc = e->counts.ensure((size_t)(1ull << 20) * n_idx)) return rc;
   if (int rc = e->tot.ensure((size_t)n_points * n_idx)) return rc;
   HIP_TRY(hipMemsetAsync(e->tot.p, 0, sizeof(unsigned long long) * n_points * n_idx, e->stream));
@@ -1115,10 +1161,36 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
     for (size_t i = 0; i < ptot.size(); ++i) rm.out[i] += ptot[i];
   }
   e->last_ms = pg.ms;
-  e->last_beam_ms = pg.beam_ms;
-  e->last_decode_ms = pg.decode_ms;
+  e->last_beam_ms = rm.beam ? pg.second_ms : 0.0;
+  e->last_decode_ms = rm.coded ? pg.second_ms : 0.0;
   e->last_chan_ms = pg.chan_ms;
   return MIMO_OK;
+}
+
+// What every row-mode entry point checks first: the engine, its precision and the mode's output (or
+// first required) argument; mode and arg are their names in the refusals.
+int row_call(const mimo_engine* e, const char* mode, const void* arg, const char* arg_name) {
+  if (!e) return fail(MIMO_EINVAL, "null engine");
+  if (e->cfg.precision != MIMO_PREC_F64)
+    return fail(MIMO_EINVAL, std::string(mode) + " needs a float64 engine (no float32 " + mode + " instances are built)");
+  if (!arg) return fail(MIMO_EINVAL, std::string("null ") + arg_name);
+  return MIMO_OK;
+}
+
+// The instances' scale num / x of a call's x (name: ref_pow, rho_max), or why it has none; what: the
+// scale in the refusal's words.
+int scale_of(const char* name, double x, double num, const char* what, double* scale) {
+  if (!(x > 0) || !std::isfinite(x)) return fail(MIMO_EINVAL, std::string(name) + " must be finite and > 0");
+  *scale = num / x;
+  if (!(*scale > 0) || !std::isfinite(*scale))
+    return fail(MIMO_EINVAL, std::string(name) + " leaves no finite " + what + " > 0");
+  return MIMO_OK;
+}
+
+// n_idx of a width function's arguments, or its refusal.
+int width_n_idx(int32_t n_iters, int32_t incl_clean) {
+  if (n_iters < 1 || n_iters > 32) return fail(MIMO_EINVAL, "n_iters must be in [1, 32]");
+  return n_iters + (incl_clean ? 1 : 0);
 }
 
 }  // namespace
@@ -1147,55 +1219,38 @@ int32_t mimo_engine_run_points(mimo_engine* e, int32_t n_points, const mimo_poin
 }
 
 int32_t mimo_measure_width(int32_t n_iters, int32_t incl_clean) {
-  if (n_iters < 1 || n_iters > 32) return fail(MIMO_EINVAL, "n_iters must be in [1, 32]");
-  return MIMO_MEAS_FIXED + n_iters + (incl_clean ? 1 : 0);
+  const int n_idx = width_n_idx(n_iters, incl_clean);
+  return n_idx < 0 ? n_idx : row_width(MIMO_MODE_MEAS, 0, n_idx, 0);
 }
 
 int32_t mimo_engine_measure_points(mimo_engine* e, int32_t n_points, const mimo_point* points, const uint64_t* seeds,
                                    const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters,
                                    int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
                                    uint32_t* per_trial, double* meas_out, double* per_trial_meas) {
-  if (!e) return fail(MIMO_EINVAL, "null engine");
-  if (e->cfg.precision != MIMO_PREC_F64)
-    return fail(MIMO_EINVAL, "measure needs a float64 engine (no float32 measure instances are built)");
-  if (!meas_out) return fail(MIMO_EINVAL, "null meas_out");
-  RowMode rm;
-  rm.mode = MIMO_MODE_MEAS;
-  rm.width = MIMO_MEAS_FIXED + n_iters + (incl_clean ? 1 : 0);  // (run_points checks n_iters before it reads this)
-  rm.out = meas_out;
-  rm.per_trial_out = per_trial_meas;
+  if (int rc = row_call(e, "measure", meas_out, "meas_out")) return rc;
   return run_points(e, n_points, points, seeds, first_trial, n_trials, iters, n_iters, incl_clean, err_out, bits_out,
-                    per_trial, rm);
+                    per_trial, RowMode{MIMO_MODE_MEAS, meas_out, per_trial_meas});
 }
 
 int32_t mimo_spectrum_width(int32_t n_fft) {
   if (!is_pow2(n_fft) || n_fft < 128 || n_fft > 8192)
     return fail(MIMO_EINVAL, "n_fft must be a power of two in [128, 8192]");
-  return n_fft + MIMO_SPEC_FIXED;
+  return row_width(MIMO_MODE_SPEC, n_fft, 0, 0);
 }
 
 int32_t mimo_engine_spectrum_points(mimo_engine* e, int32_t n_points, const mimo_point* points, const uint64_t* seeds,
                                     const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters,
                                     int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
                                     uint32_t* per_trial, double* spec_out, double* per_trial_spec) {
-  if (!e) return fail(MIMO_EINVAL, "null engine");
-  if (e->cfg.precision != MIMO_PREC_F64)
-    return fail(MIMO_EINVAL, "spectrum needs a float64 engine (no float32 spectrum instances are built)");
-  if (!spec_out) return fail(MIMO_EINVAL, "null spec_out");
-  RowMode rm;
-  rm.mode = MIMO_MODE_SPEC;
-  rm.width = e->cfg.n_fft + MIMO_SPEC_FIXED;
-  rm.max_trials = MIMO_SPEC_BUFFER_BYTES / (sizeof(double) * (size_t)rm.width);
-  rm.out = spec_out;
-  rm.per_trial_out = per_trial_spec;
+  if (int rc = row_call(e, "spectrum", spec_out, "spec_out")) return rc;
   return run_points(e, n_points, points, seeds, first_trial, n_trials, iters, n_iters, incl_clean, err_out, bits_out,
-                    per_trial, rm);
+                    per_trial, RowMode{MIMO_MODE_SPEC, spec_out, per_trial_spec});
 }
 
 int32_t mimo_beam_width(int32_t n_probes) {
   if (n_probes < 1 || n_probes > MIMO_BEAM_MAX_PROBES)
     return fail(MIMO_EINVAL, "n_probes must be in [1, " + std::to_string(MIMO_BEAM_MAX_PROBES) + "]");
-  return n_probes * MIMO_BEAM_FIXED;
+  return row_width(MIMO_MODE_BEAM, 0, 0, n_probes);
 }
 
 int32_t mimo_engine_beam_points(mimo_engine* e, int32_t n_points, const mimo_point* points, const uint64_t* seeds,
@@ -1203,36 +1258,17 @@ int32_t mimo_engine_beam_points(mimo_engine* e, int32_t n_points, const mimo_poi
                                 int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
                                 uint32_t* per_trial, const double* probes, int32_t n_probes, double* beam_out,
                                 double* per_trial_beam) {
-  if (!e) return fail(MIMO_EINVAL, "null engine");
-  if (e->cfg.precision != MIMO_PREC_F64)
-    return fail(MIMO_EINVAL, "beam needs a float64 engine (no float32 beam instances are built)");
-  if (!probes) return fail(MIMO_EINVAL, "null probes");
+  if (int rc = row_call(e, "beam", probes, "probes")) return rc;
   if (!beam_out) return fail(MIMO_EINVAL, "null beam_out");
   if (mimo_beam_width(n_probes) < 0) return MIMO_EINVAL;
   const int A = e->cfg.n_ant, F = e->cfg.n_fft;
   BeamCall bc;
   bc.n_probes = n_probes;
-  RowMode rm;
-  rm.mode = MIMO_MODE_BEAM;
-  rm.width = n_probes * MIMO_BEAM_FIXED;
-  rm.out = beam_out;
-  rm.per_trial_out = per_trial_beam;
-  rm.beam = &bc;
-  // the launch's cells: Y and X of every antenna and bin, complex128
-  const uint64_t per_trial_bytes = 2ull * (uint64_t)A * (uint64_t)F * 16ull;
-  uint64_t buffer = MIMO_BEAM_BUFFER_BYTES;
-  if (const char* env = std::getenv("MIMO_BEAM_BUFFER_BYTES")) {  // lowers it, for tests of the splitting
-    const uint64_t v = std::strtoull(env, nullptr, 10);
-    if (v >= 1 && v < buffer) buffer = v;
-  }
-  rm.max_trials = buffer / per_trial_bytes;
-  if (rm.max_trials < 1)
-    return fail(MIMO_EINVAL, "one trial's beam cells (" + std::to_string(per_trial_bytes) + " B at n_ant " +
+  bc.buffer = env_lowered("MIMO_BEAM_BUFFER_BYTES", MIMO_BEAM_BUFFER_BYTES);
+  if (bc.buffer < beam_trial_bytes(e->cfg))
+    return fail(MIMO_EINVAL, "one trial's beam cells (" + std::to_string(beam_trial_bytes(e->cfg)) + " B at n_ant " +
                                  std::to_string(A) + ", n_fft " + std::to_string(F) +
-                                 ") do not fit the beam buffer of " + std::to_string(buffer) + " B");
-  // ... and its per-trial rows, as for the spectrum mode (one trial's 40 n_probes bytes always fit)
-  rm.max_trials = std::min<uint64_t>(
-      rm.max_trials, MIMO_BEAM_ROWS_BYTES / (sizeof(double) * (uint64_t)MIMO_BEAM_FIXED * (uint64_t)n_probes));
+                                 ") do not fit the beam buffer of " + std::to_string(bc.buffer) + " B");
   const size_t na = (size_t)n_probes * (size_t)A;
   bc.geo.resize(2 * na + (size_t)F);
   for (int q = 0; q < n_probes; ++q) {
@@ -1253,10 +1289,10 @@ int32_t mimo_engine_beam_points(mimo_engine* e, int32_t n_points, const mimo_poi
   }
   for (int k = 0; k < F; ++k) bc.geo[2 * na + k] = e->freqs[k] / kSpeedOfLight;
   return run_points(e, n_points, points, seeds, first_trial, n_trials, iters, n_iters, incl_clean, err_out, bits_out,
-                    per_trial, rm);
+                    per_trial, RowMode{MIMO_MODE_BEAM, beam_out, per_trial_beam, 0.0, &bc});
 }
 
-int32_t mimo_envelope_width(void) { return 2 * MIMO_ENV_BINS + MIMO_ENV_FIXED; }
+int32_t mimo_envelope_width(void) { return row_width(MIMO_MODE_ENV, 0, 0, 0); }
 
 // The lower edge of bin b >= 1 in units of u = |.|^2 / ref_pow: the smallest v = 1.0625 u whose
 // bits >> 49 are 8088 + b is 2^(-12 + b / 8) (1 + (b % 8) / 8), exactly.
@@ -1271,58 +1307,32 @@ int32_t mimo_engine_envelope_points(mimo_engine* e, int32_t n_points, const mimo
                                     const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters,
                                     int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
                                     uint32_t* per_trial, double ref_pow, double* env_out, double* per_trial_env) {
-  if (!e) return fail(MIMO_EINVAL, "null engine");
-  if (e->cfg.precision != MIMO_PREC_F64)
-    return fail(MIMO_EINVAL, "envelope needs a float64 engine (no float32 envelope instances are built)");
-  if (!env_out) return fail(MIMO_EINVAL, "null env_out");
-  if (!(ref_pow > 0) || !std::isfinite(ref_pow)) return fail(MIMO_EINVAL, "ref_pow must be finite and > 0");
-  const double scale = 1.0625 / ref_pow;
-  if (!(scale > 0) || !std::isfinite(scale))
-    return fail(MIMO_EINVAL, "ref_pow leaves no finite bin scale 1.0625 / ref_pow > 0");
-  RowMode rm;
-  rm.mode = MIMO_MODE_ENV;
-  rm.width = 2 * MIMO_ENV_BINS + MIMO_ENV_FIXED;
-  rm.max_trials = MIMO_ENV_BUFFER_BYTES / (sizeof(double) * (size_t)rm.width);
-  rm.out = env_out;
-  rm.per_trial_out = per_trial_env;
-  rm.aux = scale;
+  if (int rc = row_call(e, "envelope", env_out, "env_out")) return rc;
+  double scale;
+  if (int rc = scale_of("ref_pow", ref_pow, 1.0625, "bin scale 1.0625 / ref_pow", &scale)) return rc;
   return run_points(e, n_points, points, seeds, first_trial, n_trials, iters, n_iters, incl_clean, err_out, bits_out,
-                    per_trial, rm);
+                    per_trial, RowMode{MIMO_MODE_ENV, env_out, per_trial_env, scale});
 }
 
 int32_t mimo_soft_width(int32_t n_iters, int32_t incl_clean) {
-  if (n_iters < 1 || n_iters > 32) return fail(MIMO_EINVAL, "n_iters must be in [1, 32]");
-  return MIMO_SOFT_BINS * (n_iters + (incl_clean ? 1 : 0));
+  const int n_idx = width_n_idx(n_iters, incl_clean);
+  return n_idx < 0 ? n_idx : row_width(MIMO_MODE_SOFT, 0, n_idx, 0);
 }
 
 int32_t mimo_engine_soft_points(mimo_engine* e, int32_t n_points, const mimo_point* points, const uint64_t* seeds,
                                 const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters,
                                 int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
                                 uint32_t* per_trial, double rho_max, double* soft_out, double* per_trial_soft) {
-  if (!e) return fail(MIMO_EINVAL, "null engine");
-  if (e->cfg.precision != MIMO_PREC_F64)
-    return fail(MIMO_EINVAL, "soft needs a float64 engine (no float32 soft instances are built)");
-  if (!soft_out) return fail(MIMO_EINVAL, "null soft_out");
-  if (!(rho_max > 0) || !std::isfinite(rho_max)) return fail(MIMO_EINVAL, "rho_max must be finite and > 0");
-  const double scale = 128.0 / rho_max;
-  if (!(scale > 0) || !std::isfinite(scale))
-    return fail(MIMO_EINVAL, "rho_max leaves no finite bin scale 128 / rho_max > 0");
-  // (run_points checks n_iters before it reads the width; a list it refuses gets one index here)
-  const int n_idx = (n_iters >= 1 && n_iters <= 32 ? n_iters : 1) + (incl_clean ? 1 : 0);
-  RowMode rm;
-  rm.mode = MIMO_MODE_SOFT;
-  rm.width = MIMO_SOFT_BINS * n_idx;
-  rm.max_trials = MIMO_SOFT_BUFFER_BYTES / (sizeof(double) * (size_t)rm.width);
-  rm.out = soft_out;
-  rm.per_trial_out = per_trial_soft;
-  rm.aux = scale;
+  if (int rc = row_call(e, "soft", soft_out, "soft_out")) return rc;
+  double scale;
+  if (int rc = scale_of("rho_max", rho_max, 128.0, "bin scale 128 / rho_max", &scale)) return rc;
   return run_points(e, n_points, points, seeds, first_trial, n_trials, iters, n_iters, incl_clean, err_out, bits_out,
-                    per_trial, rm);
+                    per_trial, RowMode{MIMO_MODE_SOFT, soft_out, per_trial_soft, scale});
 }
 
 int32_t mimo_coded_width(int32_t n_iters, int32_t incl_clean) {
-  if (n_iters < 1 || n_iters > 32) return fail(MIMO_EINVAL, "n_iters must be in [1, 32]");
-  return MIMO_CODED_FIXED * (n_iters + (incl_clean ? 1 : 0));
+  const int n_idx = width_n_idx(n_iters, incl_clean);
+  return n_idx < 0 ? n_idx : row_width(MIMO_MODE_CODED, 0, n_idx, 0);
 }
 
 int32_t mimo_coded_codewords(int32_t n_sub_carr, int32_t constel_size, const mimo_ldpc_code* code) {
@@ -1345,34 +1355,19 @@ int32_t mimo_engine_coded_points(mimo_engine* e, int32_t n_points, const mimo_po
                                  int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
                                  uint32_t* per_trial, const mimo_ldpc_code* code, double rho_max, double* coded_out,
                                  double* per_trial_coded, int8_t* per_trial_chan) {
-  if (!e) return fail(MIMO_EINVAL, "null engine");
-  if (e->cfg.precision != MIMO_PREC_F64)
-    return fail(MIMO_EINVAL, "coded needs a float64 engine (no float32 coded instances are built)");
-  if (!coded_out) return fail(MIMO_EINVAL, "null coded_out");
+  if (int rc = row_call(e, "coded", coded_out, "coded_out")) return rc;
   const int n_cw = mimo_coded_codewords(e->cfg.n_sub_carr, e->cfg.constel_size, code);
   if (n_cw < 0) return MIMO_EINVAL;
-  if (!(rho_max > 0) || !std::isfinite(rho_max)) return fail(MIMO_EINVAL, "rho_max must be finite and > 0");
-  const double scale = 32.0 / rho_max;
-  if (!(scale > 0) || !std::isfinite(scale))
-    return fail(MIMO_EINVAL, "rho_max leaves no finite scale 32 / rho_max > 0");
+  double scale;
+  if (int rc = scale_of("rho_max", rho_max, 32.0, "scale 32 / rho_max", &scale)) return rc;
   CodedCall cc;
   std::string err;
   if (!mimo::ldpc_prepare(code, &cc.code, &err)) return fail(MIMO_EINVAL, err);
   cc.n_cw = n_cw;
   cc.stream = (size_t)e->cfg.n_sub_carr * (size_t)std::lround(std::log2((double)e->cfg.constel_size));
   cc.per_trial_chan = per_trial_chan;
-  // (run_points checks n_iters before it reads the width; a list it refuses gets one index here)
-  const int n_idx = (n_iters >= 1 && n_iters <= 32 ? n_iters : 1) + (incl_clean ? 1 : 0);
-  RowMode rm;
-  rm.mode = MIMO_MODE_CODED;
-  rm.width = MIMO_CODED_FIXED * n_idx;
-  rm.max_trials = MIMO_CODED_BUFFER_BYTES / (cc.stream * (size_t)n_idx);
-  rm.out = coded_out;
-  rm.per_trial_out = per_trial_coded;
-  rm.coded = &cc;
-  rm.aux = scale;
   return run_points(e, n_points, points, seeds, first_trial, n_trials, iters, n_iters, incl_clean, err_out, bits_out,
-                    per_trial, rm);
+                    per_trial, RowMode{MIMO_MODE_CODED, coded_out, per_trial_coded, scale, nullptr, &cc});
 }
 
 int64_t mimo_bank_capacity(int32_t n_ant, int32_t n_sub_carr, int32_t precision) {

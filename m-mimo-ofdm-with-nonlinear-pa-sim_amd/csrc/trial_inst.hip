@@ -1,7 +1,7 @@
-// Instantiates the fused trial kernel for one FFT size, arithmetic type and run mode: compiled
-// once per -DINST_F=<size> -DINST_F64=<0|1>, and once more per size with -DINST_F64=1
-// -DINST_MODE=<1 measure | 2 spectrum | 3 beam | 4 envelope | 5 soft | 6 coded> (trial_kernel.h
-// MIMO_MODE_*; 0, plain, by default).
+// Defines launch_trial<F, R, MODE> (trial_launch.h), and with it instantiates the fused trial kernel,
+// for one FFT size, arithmetic type and run mode: compiled once per -DINST_F=<size> -DINST_F64=<0|1>,
+// and once more per size with -DINST_F64=1 -DINST_MODE=<1 measure | 2 spectrum | 3 beam | 4 envelope |
+// 5 soft | 6 coded> (trial_kernel.h MIMO_MODE_*; 0, plain, by default).
 #include <type_traits>
 
 #ifndef INST_F
@@ -16,32 +16,16 @@
 #if INST_MODE && !INST_F64
 #error "the measure, spectrum, beam, envelope, soft and coded instances are float64 only"
 #endif
-#define MIMO_INST_MODE INST_MODE
 
 #include "trial_launch.h"
-
-// the one kernel trial_kernel.h defines for the mode
-#if INST_MODE == MIMO_MODE_MEAS
-#define MIMO_TRIAL_KERNEL trial_kernel_meas
-#elif INST_MODE == MIMO_MODE_SPEC
-#define MIMO_TRIAL_KERNEL trial_kernel_spec
-#elif INST_MODE == MIMO_MODE_BEAM
-#define MIMO_TRIAL_KERNEL trial_kernel_beam
-#elif INST_MODE == MIMO_MODE_ENV
-#define MIMO_TRIAL_KERNEL trial_kernel_env
-#elif INST_MODE == MIMO_MODE_SOFT
-#define MIMO_TRIAL_KERNEL trial_kernel_soft
-#elif INST_MODE == MIMO_MODE_CODED
-#define MIMO_TRIAL_KERNEL trial_kernel_coded
-#else
-#define MIMO_TRIAL_KERNEL trial_kernel
-#endif
 
 namespace mimo {
 namespace {
 
 constexpr int kF = INST_F;
 constexpr bool kF64 = INST_F64 != 0;
+constexpr int kMode = INST_MODE;
+using Args = ModeArgs<kMode>;
 using Real = std::conditional_t<kF64, double, float>;
 
 // Occupancy profile per instance (see trial_kernel): waves/SIMD target, exchange buffers,
@@ -58,7 +42,7 @@ struct Profile {
   int minw, nbuf;
   bool symw_lds;
 };
-constexpr Profile profile_for(int T, bool aligned, int ch) {
+constexpr Profile profile_for(int mode, int T, bool aligned, int ch) {
   const int P = kF / T;
   if (kF64 && kF >= 8192) return Profile{2, 1, false};  // 136 KiB exchange buffer: one team per CU (T = 512: 2 waves/SIMD)
   // fp64 up to F 2048: 3 waves/SIMD (168 VGPRs; the symbols rebuilt from the labels and
@@ -70,10 +54,10 @@ constexpr Profile profile_for(int T, bool aligned, int ch) {
   // 326 VGPRs and run at one wave/SIMD, would be capped at 256 and spill, profiles/r18/soft/resources.txt)
   // (the F 2048 coded instances: tuning.h MIMO_CODED_W64_2048, profiles/r19/coded/)
   if (kF64 && kF <= 2048)
-    return Profile{INST_MODE == MIMO_MODE_ENV    ? MIMO_ENV_W64_2048
-                   : INST_MODE == MIMO_MODE_SOFT && kF == 2048 ? MIMO_SOFT_W64_2048
-                   : INST_MODE == MIMO_MODE_CODED && kF == 2048 ? MIMO_CODED_W64_2048
-                                                 : MIMO_W64_2048,
+    return Profile{mode == MIMO_MODE_ENV                   ? MIMO_ENV_W64_2048
+                   : mode == MIMO_MODE_SOFT && kF == 2048  ? MIMO_SOFT_W64_2048
+                   : mode == MIMO_MODE_CODED && kF == 2048 ? MIMO_CODED_W64_2048
+                                                           : MIMO_W64_2048,
                    1, false};
   if (kF64 && kF == 4096) return Profile{2, 1, false};  // 16-point team, symbols from levels: 2 teams/CU
   if (kF64) return Profile{2, 1, true};
@@ -85,45 +69,39 @@ constexpr Profile profile_for(int T, bool aligned, int ch) {
 
 // attr != null: no launch, the instance's attributes instead (its static LDS, which the
 // engine checks with the CSI table's dynamic LDS against the device limit before a launch).
-// out, aux: the kernel's extra arguments (trial_launch.h launch_trial; the plain kernel has none,
-// the envelope, soft and coded kernels alone take aux; the coded kernel's buffer holds int8).
+// m: the kernel's mode arguments.
 template <int T, int NSLOT, bool AL, int CH, bool CSI>
-hipError_t go(dim3 grid, hipStream_t st, const TrialParams<Real>& p, hipFuncAttributes* attr, double* out,
-              double aux) {
-  constexpr Profile pr = profile_for(T, AL, CH);
-  auto* kern = &MIMO_TRIAL_KERNEL<Real, kF, T, NSLOT, AL, CH, CSI, pr.minw, pr.nbuf, pr.symw_lds>;
-  if (attr) return hipFuncGetAttributes(attr, reinterpret_cast<const void*>(kern));
+hipError_t go(dim3 grid, hipStream_t st, const TrialParams<Real>& p, hipFuncAttributes* attr, const Args& m) {
+  constexpr Profile pr = profile_for(kMode, T, AL, CH);
   // CSI: the per-antenna power table is dynamic LDS, A reals (trial_kernel pw_csi)
   const size_t dyn = CSI ? sizeof(Real) * (size_t)p.n_ant : 0;
-#if INST_MODE == MIMO_MODE_CODED
-  hipLaunchKernelGGL(kern, grid, dim3(T), dyn, st, p, reinterpret_cast<int8_t*>(out), aux);
-#elif INST_MODE == MIMO_MODE_ENV || INST_MODE == MIMO_MODE_SOFT
-  hipLaunchKernelGGL(kern, grid, dim3(T), dyn, st, p, out, aux);
-#elif INST_MODE
-  hipLaunchKernelGGL(kern, grid, dim3(T), dyn, st, p, out);
-#else
-  hipLaunchKernelGGL(kern, grid, dim3(T), dyn, st, p);
-#endif
-  return hipGetLastError();
+  return std::apply(
+      [&](auto... a) {
+        auto* kern = &trial_kernel<kMode, Real, kF, T, NSLOT, AL, CH, CSI, pr.minw, pr.nbuf, pr.symw_lds, decltype(a)...>;
+        if (attr) return hipFuncGetAttributes(attr, reinterpret_cast<const void*>(kern));
+        hipLaunchKernelGGL(kern, grid, dim3(T), dyn, st, p, a...);
+        return hipGetLastError();
+      },
+      m);
 }
 
 template <int T, int NSLOT, bool AL>
 hipError_t by_channel(const InstanceKey& k, dim3 grid, hipStream_t st, const TrialParams<Real>& p, bool* found,
-                      hipFuncAttributes* a, double* m, double x) {
+                      hipFuncAttributes* a, const Args& m) {
   *found = true;
   switch (k.ch) {
     case CH_RAYLEIGH:
-      return k.csi ? go<T, NSLOT, AL, CH_RAYLEIGH, true>(grid, st, p, a, m, x)
-                   : go<T, NSLOT, AL, CH_RAYLEIGH, false>(grid, st, p, a, m, x);
+      return k.csi ? go<T, NSLOT, AL, CH_RAYLEIGH, true>(grid, st, p, a, m)
+                   : go<T, NSLOT, AL, CH_RAYLEIGH, false>(grid, st, p, a, m);
     case CH_LOS:
-      return k.csi ? go<T, NSLOT, AL, CH_LOS, true>(grid, st, p, a, m, x)
-                   : go<T, NSLOT, AL, CH_LOS, false>(grid, st, p, a, m, x);
+      return k.csi ? go<T, NSLOT, AL, CH_LOS, true>(grid, st, p, a, m)
+                   : go<T, NSLOT, AL, CH_LOS, false>(grid, st, p, a, m);
     case CH_TWOPATH:
-      return k.csi ? go<T, NSLOT, AL, CH_TWOPATH, true>(grid, st, p, a, m, x)
-                   : go<T, NSLOT, AL, CH_TWOPATH, false>(grid, st, p, a, m, x);
+      return k.csi ? go<T, NSLOT, AL, CH_TWOPATH, true>(grid, st, p, a, m)
+                   : go<T, NSLOT, AL, CH_TWOPATH, false>(grid, st, p, a, m);
     case CH_TABLE:
-      return k.csi ? go<T, NSLOT, AL, CH_TABLE, true>(grid, st, p, a, m, x)
-                   : go<T, NSLOT, AL, CH_TABLE, false>(grid, st, p, a, m, x);
+      return k.csi ? go<T, NSLOT, AL, CH_TABLE, true>(grid, st, p, a, m)
+                   : go<T, NSLOT, AL, CH_TABLE, false>(grid, st, p, a, m);
     default:
       *found = false;
       return hipSuccess;
@@ -132,34 +110,34 @@ hipError_t by_channel(const InstanceKey& k, dim3 grid, hipStream_t st, const Tri
 
 template <int T>
 hipError_t by_team(const InstanceKey& k, dim3 grid, hipStream_t st, const TrialParams<Real>& p, bool* found,
-                   hipFuncAttributes* a, double* m, double x) {
+                   hipFuncAttributes* a, const Args& m) {
   constexpr int P = kF / T;
   if (k.aligned) {
     if constexpr (8 < P) {
-      if (k.nslot == 8) return by_channel<T, 8, true>(k, grid, st, p, found, a, m, x);
+      if (k.nslot == 8) return by_channel<T, 8, true>(k, grid, st, p, found, a, m);
     }
     if constexpr (4 < P) {
-      if (k.nslot == 4) return by_channel<T, 4, true>(k, grid, st, p, found, a, m, x);
+      if (k.nslot == 4) return by_channel<T, 4, true>(k, grid, st, p, found, a, m);
     }
     return hipSuccess;
   }
   if (k.nslot != P) return hipSuccess;
-  return by_channel<T, P, false>(k, grid, st, p, found, a, m, x);
+  return by_channel<T, P, false>(k, grid, st, p, found, a, m);
 }
 
 }  // namespace
 
 template <>
-hipError_t launch_trial<kF, Real, INST_MODE>(const InstanceKey& k, dim3 grid, hipStream_t st, const TrialParams<Real>& p,
-                                             bool* found, hipFuncAttributes* attr, double* out, double aux) {
+hipError_t launch_trial<kF, Real, kMode>(const InstanceKey& k, dim3 grid, hipStream_t st, const TrialParams<Real>& p,
+                                         bool* found, hipFuncAttributes* attr, const Args& m) {
   *found = false;
   if (k.F != kF || k.f64 != kF64) return hipSuccess;
   if constexpr (kF64) {
-    if (k.T == team_size64(kF)) return by_team<team_size64(kF)>(k, grid, st, p, found, attr, out, aux);
+    if (k.T == team_size64(kF)) return by_team<team_size64(kF)>(k, grid, st, p, found, attr, m);
   } else {
-    if (k.T == team_size(kF)) return by_team<team_size(kF)>(k, grid, st, p, found, attr, out, aux);
+    if (k.T == team_size(kF)) return by_team<team_size(kF)>(k, grid, st, p, found, attr, m);
     if constexpr (alt_team_size(kF) != team_size(kF)) {
-      if (k.T == alt_team_size(kF)) return by_team<alt_team_size(kF)>(k, grid, st, p, found, attr, out, aux);
+      if (k.T == alt_team_size(kF)) return by_team<alt_team_size(kF)>(k, grid, st, p, found, attr, m);
     }
   }
   return hipSuccess;

@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <tuple>
 #include <type_traits>
 
 #include "tuning.h"
@@ -44,24 +45,35 @@ enum PaKind : int { PA_NONE = 0, PA_SOFTLIM = 1, PA_RAPP = 2, PA_TOI = 3 };
 enum ChanKind : int { CH_RAYLEIGH = 1, CH_LOS = 2, CH_TWOPATH = 3, CH_TABLE = 4 };
 enum RxKind : int { RX_CNC = 1, RX_MCNC = 2 };
 
-// The run mode of the instances a translation unit builds (trial_inst.hip -DINST_MODE=<mode>): one
-// kernel per unit, named and shaped by the mode.  The six row modes are float64 only.
-#define MIMO_MODE_PLAIN 0  // trial_kernel: the counts alone
-#define MIMO_MODE_MEAS 1   // trial_kernel_meas
-#define MIMO_MODE_SPEC 2   // trial_kernel_spec
-#define MIMO_MODE_BEAM 3   // trial_kernel_beam
-#define MIMO_MODE_ENV 4    // trial_kernel_env
-#define MIMO_MODE_SOFT 5   // trial_kernel_soft
-#define MIMO_MODE_CODED 6  // trial_kernel_coded
-#ifndef MIMO_INST_MODE
-#define MIMO_INST_MODE MIMO_MODE_PLAIN
-#endif
+// The run mode of an instance: trial_kernel's first template argument (macros, since the Makefile
+// hands one to each trial_inst.hip object as -DINST_MODE=<mode>).  The six row modes are float64 only.
+#define MIMO_MODE_PLAIN 0  // the counts alone
+#define MIMO_MODE_MEAS 1
+#define MIMO_MODE_SPEC 2
+#define MIMO_MODE_BEAM 3
+#define MIMO_MODE_ENV 4
+#define MIMO_MODE_SOFT 5
+#define MIMO_MODE_CODED 6
+
+// What a mode's kernel takes behind TrialParams, each argument with its true type: the buffer its
+// instances fill (kModeOut; the sections below have the layouts) and the mode's scale (kModeScale).
+// (A tuple, since the kernel takes its members as arguments of their own: one struct of the two
+// would be passed by reference and read at the kernel's entry, and an empty stand-in would move the
+// implicit arguments.)  TrialParams itself stays the stride of the per-point table, and its layout is
+// tuned (see csi_seed).
+template <int MODE>
+using ModeArgs = std::conditional_t<
+    MODE == MIMO_MODE_PLAIN, std::tuple<>,                                                // nothing
+    std::conditional_t<MODE == MIMO_MODE_CODED, std::tuple<int8_t*, double>,              // channel values, 32 / rho_max
+                       std::conditional_t<MODE == MIMO_MODE_ENV || MODE == MIMO_MODE_SOFT,
+                                          std::tuple<double*, double>,                    // rows, the bin scale
+                                          std::tuple<double*>>>>;                         // measure, spectrum: rows; beam: cells
+constexpr int kModeOut = 0, kModeScale = 1;
 
 // Measure instances (MIMO_MODE_MEAS): the same trial, the same
 // counts, and per trial a row of kMeasFixed + n_idx power sums over the valid in-band slots
 // (include/mimo_engine.h mimo_engine_measure_points: Es, Ez0, Re C, Im C, Ed0, then Ee_i per
-// counter index).  The row pointer is an extra argument of that kernel alone: TrialParams is
-// the stride of the per-point table and its layout is tuned (see csi_seed), and the plain
+// counter index).  The row pointer is an argument of those instances alone (ModeArgs), and the plain
 // instances compile to the code they had (profiles/r08/measure/isa_diff.txt).
 constexpr int kMeasFixed = 5;  // MIMO_MEAS_FIXED
 
@@ -77,7 +89,7 @@ constexpr int kMeasFixed = 5;  // MIMO_MEAS_FIXED
 // the rows of the teams in flight stay L2-resident.  (One form for all sizes: from F 256 up the
 // instances sit at their register cap with scratch already -- 168 VGPRs up to F 2048, 256 from
 // F 4096 -- so P more f64 registers would spill to the same memory.)  As for the measure
-// instances the row pointer is an extra argument of that kernel alone.
+// instances the row pointer is an extra argument of those instances alone.
 constexpr int kSpecFixed = 3;  // MIMO_SPEC_FIXED
 
 // Beam instances (MIMO_MODE_BEAM): the same trial, the same
@@ -87,7 +99,7 @@ constexpr int kSpecFixed = 3;  // MIMO_SPEC_FIXED
 // [grid.x][A][F] of the precoder input where Slots::scatter placed it (X_a = d sqrt(F), 0 off
 // band).  Register m of frequency thread tf is bin tf + T m before the inverse and after the
 // forward transform (the spectrum instances' statement).  Plain 16-byte stores, every cell
-// written once per launch; the buffer pointer is an extra argument of that kernel alone.
+// written once per launch; the buffer pointer is an extra argument of those instances alone.
 
 // Envelope instances (MIMO_MODE_ENV): the same trial, the same
 // counts, and per trial a row of 2 kEnvBins + kEnvFixed doubles from the main array pass alone
@@ -102,7 +114,7 @@ constexpr int kSpecFixed = 3;  // MIMO_SPEC_FIXED
 // x is held across pa_block in a copy of d (4 P VGPRs; the instances up to F 2048 are therefore
 // built for 2 waves / SIMD, tuning.h MIMO_ENV_W64_2048: at the plain instances' 168 VGPRs the copy
 // spills and costs more than the resident team).  The row pointer and the bin scale are extra
-// arguments of that kernel alone.
+// arguments of those instances alone.
 constexpr int kEnvBins = 128;   // MIMO_ENV_BINS
 constexpr int kEnvFixed = 4;    // MIMO_ENV_FIXED
 // bin of a sample power: clamp((bits(pw scale) >> 49) - 8088, 0, 127), 8088 = (1023 - 12) << 3
@@ -122,7 +134,7 @@ __device__ __forceinline__ int env_bin(double pw, double scale) {
 // uint32 (1 KiB), which the team stores as doubles to row[idx kSoftBins + ...] after `record` and
 // zeroes again (plain stores, every cell written once, no global atomics).  All of it sits in the
 // receiver phase, outside the antenna loop.  The row pointer and the bin scale 128 / rho_max are
-// extra arguments of that kernel alone.
+// extra arguments of those instances alone.
 
 // Coded instances (MIMO_MODE_CODED): the same trial, the same counts, and per trial and recorded
 // counter index the quantised reliability c (softbits.h coded_value: an odd integer in [-63, 63],
@@ -131,7 +143,7 @@ __device__ __forceinline__ int env_bin(double pw, double scale) {
 // sub-carrier k, the I axis MSB first, then Q.  Plain byte stores from the receiver phase, every cell
 // written once, no LDS and no barrier on top of the plain instance's.  The LDPC decoder (ldpc.hip)
 // reads the buffer after the launch.  The buffer and the scale 32 / rho_max are extra arguments of
-// that kernel alone.
+// those instances alone.
 
 constexpr int kMaxCsiAnt = 512;  // CSI-error runs: antennas (dynamic LDS per team, A doubles; engine.hip checks)
 constexpr uint32_t kFixedCsiTrial = 0xFFFFFFFFu;  // CSI stream counter of fixed-channel runs (oracle/sim.py draws)
@@ -917,65 +929,18 @@ __device__ __forceinline__ void fill_tw1(C* tw1_s, const C* twsrc) {
 // allocation targets, NBUF = FFT exchange buffers (2: one barrier per exchange, 1: half
 // the LDS), SYMW_LDS = keep the pre-weighted symbols in LDS (thread-private) instead of
 // registers.  F = 2048 runs (3, 1, true): 25 KiB LDS and <= 168 VGPRs per 128-thread team.
-template <typename R, int F, int T, int NSLOT, bool ALIGNED, int CH, bool CSI, int MINW, int NBUF, bool SYMW_LDS>
-#if MIMO_INST_MODE == MIMO_MODE_MEAS
-__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel_meas(TrialParams<R> p0,
-                                                                                                  double* meas_rows) {
-  constexpr double* spec_rows = nullptr;
-#elif MIMO_INST_MODE == MIMO_MODE_SPEC
-__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel_spec(TrialParams<R> p0,
-                                                                                                  double* spec_rows) {
-  constexpr double* meas_rows = nullptr;
-#elif MIMO_INST_MODE == MIMO_MODE_BEAM
-__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel_beam(TrialParams<R> p0,
-                                                                                                  double* beam_cells) {
-  constexpr double* meas_rows = nullptr;
-  constexpr double* spec_rows = nullptr;
-#elif MIMO_INST_MODE == MIMO_MODE_ENV
-__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel_env(TrialParams<R> p0,
-                                                                                                 double* env_rows,
-                                                                                                 double env_scale) {
-  constexpr double* meas_rows = nullptr;
-  constexpr double* spec_rows = nullptr;
-#elif MIMO_INST_MODE == MIMO_MODE_SOFT
-__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel_soft(TrialParams<R> p0,
-                                                                                                  double* soft_rows,
-                                                                                                  double soft_scale) {
-  constexpr double* meas_rows = nullptr;
-  constexpr double* spec_rows = nullptr;
-#elif MIMO_INST_MODE == MIMO_MODE_CODED
-__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel_coded(TrialParams<R> p0,
-                                                                                                   int8_t* coded_chan,
-                                                                                                   double coded_scale) {
-  constexpr double* meas_rows = nullptr;
-  constexpr double* spec_rows = nullptr;
-#else
-__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel(TrialParams<R> p0) {
-  constexpr double* meas_rows = nullptr;
-  constexpr double* spec_rows = nullptr;
-#endif
-#if MIMO_INST_MODE != MIMO_MODE_BEAM
-  constexpr double* beam_cells = nullptr;
-#endif
-#if MIMO_INST_MODE != MIMO_MODE_ENV
-  constexpr double* env_rows = nullptr;
-  constexpr double env_scale = 0.0;
-#endif
-#if MIMO_INST_MODE != MIMO_MODE_SOFT
-  constexpr double* soft_rows = nullptr;
-  constexpr double soft_scale = 0.0;
-#endif
-#if MIMO_INST_MODE != MIMO_MODE_CODED
-  constexpr int8_t* coded_chan = nullptr;
-  constexpr double coded_scale = 0.0;
-#endif
+template <int MODE, typename R, int F, int T, int NSLOT, bool ALIGNED, int CH, bool CSI, int MINW, int NBUF, bool SYMW_LDS,
+          typename... MA>
+__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void trial_kernel(TrialParams<R> p0, MA... a) {
+  static_assert(std::is_same_v<std::tuple<MA...>, ModeArgs<MODE>>, "the kernel's arguments behind p0 are the mode's");
+  const ModeArgs<MODE> ma(a...);
   using C = cx<R>;
-  constexpr bool MEAS = MIMO_INST_MODE == MIMO_MODE_MEAS && sizeof(R) == 8;
-  constexpr bool SPEC = MIMO_INST_MODE == MIMO_MODE_SPEC && sizeof(R) == 8;
-  constexpr bool BEAM = MIMO_INST_MODE == MIMO_MODE_BEAM && sizeof(R) == 8;
-  constexpr bool ENV = MIMO_INST_MODE == MIMO_MODE_ENV && sizeof(R) == 8;
-  constexpr bool SOFT = MIMO_INST_MODE == MIMO_MODE_SOFT && sizeof(R) == 8;
-  constexpr bool CODED = MIMO_INST_MODE == MIMO_MODE_CODED && sizeof(R) == 8;
+  constexpr bool MEAS = MODE == MIMO_MODE_MEAS && sizeof(R) == 8;
+  constexpr bool SPEC = MODE == MIMO_MODE_SPEC && sizeof(R) == 8;
+  constexpr bool BEAM = MODE == MIMO_MODE_BEAM && sizeof(R) == 8;
+  constexpr bool ENV = MODE == MIMO_MODE_ENV && sizeof(R) == 8;
+  constexpr bool SOFT = MODE == MIMO_MODE_SOFT && sizeof(R) == 8;
+  constexpr bool CODED = MODE == MIMO_MODE_CODED && sizeof(R) == 8;
   // ---- which point and trial this block runs (uniform binary search over point_start)
   uint32_t pi = 0;
   if (p0.n_points > 1) {
@@ -1419,7 +1384,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
   // through the main pass and the MCNC passes; the transforms launder the words, not the thread
   // id.  The receiver-phase transforms (once per iteration) keep re-deriving.
   constexpr bool XADDR =
-      MIMO_XADDR != 0 && WAVEFFT && sizeof(R) == 8 && !CSI && xaddr_inst_ok(F, MIMO_INST_MODE, ALIGNED, CH);
+      MIMO_XADDR != 0 && WAVEFFT && sizeof(R) == 8 && !CSI && xaddr_inst_ok(F, MODE, ALIGNED, CH);
   using XAD = typename XAddrOf<FFT, XADDR>::type;
   XAD xaddr;
   if constexpr (XADDR) xaddr.set(t, __builtin_amdgcn_readfirstlane(wid));
@@ -1557,7 +1522,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
       if constexpr (BEAM) {
         if (main_pass) {
           // X_a / sqrt(F) as scattered (0 off band): the buffer's second half, bin tl + T m
-          double2* cell = reinterpret_cast<double2*>(beam_cells) +
+          double2* cell = reinterpret_cast<double2*>(std::get<kModeOut>(ma)) +
                           ((size_t)gridDim.x * (size_t)A + (size_t)blockIdx.x * (size_t)A + (size_t)a) * (size_t)F + tl;
 #pragma unroll
           for (int m = 0; m < P; ++m) cell[T * m] = make_double2((double)d[m].x, (double)d[m].y);
@@ -1582,7 +1547,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
             const R pw = fmar(d[m].x, d[m].x, d[m].y * d[m].y);
             en_pin += pw;
 #ifndef MIMO_DIAG_ENV_NOHIST  // cost breakdowns only: the sums and the held x without the histograms
-            atomicAdd(&env_hist[env_bin((double)pw, env_scale) * SUBH + (lane & (SUBH - 1))], 1u);
+            atomicAdd(&env_hist[env_bin((double)pw, std::get<kModeScale>(ma)) * SUBH + (lane & (SUBH - 1))], 1u);
 #endif
           }
         }
@@ -1595,7 +1560,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
             const R pw = fmar(d[m].x, d[m].x, d[m].y * d[m].y);
             en_pout += pw;
 #ifndef MIMO_DIAG_ENV_NOHIST
-            atomicAdd(&env_hist[(kEnvBins + env_bin((double)pw, env_scale)) * SUBH + (lane & (SUBH - 1))], 1u);
+            atomicAdd(&env_hist[(kEnvBins + env_bin((double)pw, std::get<kModeScale>(ma))) * SUBH + (lane & (SUBH - 1))], 1u);
 #endif
             en_cre = fmar(d[m].x, xin[m].x, fmar(d[m].y, xin[m].y, en_cre));
             en_cim = fmar(d[m].y, xin[m].x, fmar(-d[m].x, xin[m].y, en_cim));
@@ -1685,7 +1650,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
         if (main_pass) {
           // Y_a sqrt(F): the thread's P bins of the chain output, bin tl + T m
           double2* cell =
-              reinterpret_cast<double2*>(beam_cells) + ((size_t)blockIdx.x * (size_t)A + (size_t)a) * (size_t)F + tl;
+              reinterpret_cast<double2*>(std::get<kModeOut>(ma)) + ((size_t)blockIdx.x * (size_t)A + (size_t)a) * (size_t)F + tl;
 #pragma unroll
           for (int m = 0; m < P; ++m) cell[T * m] = make_double2((double)d[m].x, (double)d[m].y);
         }
@@ -1693,7 +1658,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
       if constexpr (SPEC) {
         if (main_pass) {
           // psd: |d|^2 / F (ortho) into the thread's cells, bin tl + T m; 1 / F is a power of two
-          double* cell = spec_rows + (size_t)blockIdx.x * (size_t)(F + kSpecFixed) + tl;
+          double* cell = std::get<kModeOut>(ma) + (size_t)blockIdx.x * (size_t)(F + kSpecFixed) + tl;
           R pw[P];
 #pragma unroll
           for (int m = 0; m < P; ++m) pw[m] = fmar(d[m].x, d[m].x, d[m].y * d[m].y) * R(1.0 / F);
@@ -1778,7 +1743,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
     const R pin = team_sum<T>(en_pin, red), pout = team_sum<T>(en_pout, red);
     const R cre = team_sum<T>(en_cre, red), cim = team_sum<T>(en_cim, red);
     __syncthreads();
-    double* row = env_rows + (size_t)blockIdx.x * (size_t)(2 * kEnvBins + kEnvFixed);
+    double* row = std::get<kModeOut>(ma) + (size_t)blockIdx.x * (size_t)(2 * kEnvBins + kEnvFixed);
     for (int i = t; i < 2 * kEnvBins; i += T) {
       uint32_t n = 0;
 #pragma unroll
@@ -1796,7 +1761,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
     // Ex = F sum |x|^2 (x carries 1 / sqrt(F)); Y conj(X) = (d / sqrt(F)) conj(x sqrt(F)) = d conj(x)
     const R ex = team_sum<T>(sp_ex, red), cre = team_sum<T>(sp_cre, red), cim = team_sum<T>(sp_cim, red);
     if (t0) {
-      double* fixed = spec_rows + (size_t)blockIdx.x * (size_t)(F + kSpecFixed) + F;
+      double* fixed = std::get<kModeOut>(ma) + (size_t)blockIdx.x * (size_t)(F + kSpecFixed) + F;
       fixed[0] = (double)(ex * (R)F);
       fixed[1] = (double)cre;
       fixed[2] = (double)cim;
@@ -1835,7 +1800,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
   auto measure = [&](int col, R v) __attribute__((always_inline)) {
     if constexpr (MEAS) {
       const R tot = team_sum<T>(v, red);
-      if (t0) meas_rows[(size_t)blockIdx.x * (size_t)(kMeasFixed + p0.n_idx) + col] = (double)tot;
+      if (t0) std::get<kModeOut>(ma)[(size_t)blockIdx.x * (size_t)(kMeasFixed + p0.n_idx) + col] = (double)tot;
     }
   };
   // soft instances: the team's reliability histogram of the counter index being recorded.  Zeroed
@@ -1852,15 +1817,15 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
         const uint32_t li = lab[s] >> hb, lq = lab[s] & ((1u << hb) - 1u);
 #ifndef MIMO_DIAG_SOFT_NOHIST  // cost breakdowns only: the metric without the LDS adds
         soft_axis((double)v.x, L, hb, [&](int j, double lam) {
-          atomicAdd(&soft_hist[soft_bin(lam, (li >> j) & 1u, soft_scale)], 1u);
+          atomicAdd(&soft_hist[soft_bin(lam, (li >> j) & 1u, std::get<kModeScale>(ma))], 1u);
         });
         soft_axis((double)v.y, L, hb, [&](int j, double lam) {
-          atomicAdd(&soft_hist[soft_bin(lam, (lq >> j) & 1u, soft_scale)], 1u);
+          atomicAdd(&soft_hist[soft_bin(lam, (lq >> j) & 1u, std::get<kModeScale>(ma))], 1u);
         });
 #else
         double keep = 0.0;
-        soft_axis((double)v.x, L, hb, [&](int j, double lam) { keep += (double)soft_bin(lam, (li >> j) & 1u, soft_scale); });
-        soft_axis((double)v.y, L, hb, [&](int j, double lam) { keep += (double)soft_bin(lam, (lq >> j) & 1u, soft_scale); });
+        soft_axis((double)v.x, L, hb, [&](int j, double lam) { keep += (double)soft_bin(lam, (li >> j) & 1u, std::get<kModeScale>(ma)); });
+        soft_axis((double)v.y, L, hb, [&](int j, double lam) { keep += (double)soft_bin(lam, (lq >> j) & 1u, std::get<kModeScale>(ma)); });
         if (keep < 0.0) atomicAdd(&soft_hist[0], 1u);  // never taken: keeps the metric alive
 #endif
       }
@@ -1872,7 +1837,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
   auto soft_flush = [&](int idx) __attribute__((always_inline)) {
     if constexpr (SOFT) {
       __syncthreads();
-      double* row = soft_rows + ((size_t)blockIdx.x * (size_t)p0.n_idx + (size_t)idx) * (size_t)kSoftBins;
+      double* row = std::get<kModeOut>(ma) + ((size_t)blockIdx.x * (size_t)p0.n_idx + (size_t)idx) * (size_t)kSoftBins;
       for (int i = t; i < kSoftBins; i += T) {
         row[i] = (double)soft_hist[i];
         soft_hist[i] = 0u;
@@ -1888,12 +1853,12 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
       const int k = SL::k_of(s, opaque(tf), S, ok);
       if (ok) {
         const uint32_t li = lab[s] >> hb, lq = lab[s] & ((1u << hb) - 1u);
-        int8_t* o = coded_chan + ((size_t)blockIdx.x * (size_t)p0.n_idx + (size_t)idx) * ((size_t)S * (size_t)(2 * hb)) + k;
+        int8_t* o = std::get<kModeOut>(ma) + ((size_t)blockIdx.x * (size_t)p0.n_idx + (size_t)idx) * ((size_t)S * (size_t)(2 * hb)) + k;
         soft_axis((double)v.x, L, hb, [&](int j, double lam) {
-          o[(size_t)(hb - 1 - j) * (size_t)S] = (int8_t)coded_value(lam, (li >> j) & 1u, coded_scale);
+          o[(size_t)(hb - 1 - j) * (size_t)S] = (int8_t)coded_value(lam, (li >> j) & 1u, std::get<kModeScale>(ma));
         });
         soft_axis((double)v.y, L, hb, [&](int j, double lam) {
-          o[(size_t)(2 * hb - 1 - j) * (size_t)S] = (int8_t)coded_value(lam, (lq >> j) & 1u, coded_scale);
+          o[(size_t)(2 * hb - 1 - j) * (size_t)S] = (int8_t)coded_value(lam, (lq >> j) & 1u, std::get<kModeScale>(ma));
         });
       }
     }

@@ -34,21 +34,15 @@ struct InstanceKey {
 // The launcher of the instances of one FFT size, arithmetic type and mode (MIMO_MODE_*), defined by
 // the trial_inst.hip object built for them: *found = the key names one of its instances.
 // attr != null: return the instance's attributes (static LDS ...) instead of launching it.
-// out: the kernel's extra argument -- the measure instances' per-trial rows [grid.x][kMeasFixed +
-// n_idx], the spectrum instances' [grid.x][F + kSpecFixed], the beam instances' cells
-// [2][grid.x][A][F] complex128 (Y sqrt(F), X / sqrt(F)), the envelope instances' rows [grid.x][2 kEnvBins +
-// kEnvFixed], the soft instances' rows [grid.x][n_idx kSoftBins], the coded instances' channel values [grid.x][n_idx]
-// [S log2 M] int8 (passed through the same pointer); the plain instances ignore it.  aux: the envelope
-// instances' bin scale 1.0625 / ref_pow, the soft instances' 128 / rho_max, the coded instances' 32 / rho_max;
-// the others ignore it.
+// m: the kernel's mode arguments (trial_kernel.h ModeArgs).
 template <int F, typename R, int MODE>
 hipError_t launch_trial(const InstanceKey& k, dim3 grid, hipStream_t st, const TrialParams<R>& p, bool* found,
-                        hipFuncAttributes* attr, double* out, double aux) = delete;
+                        hipFuncAttributes* attr, const ModeArgs<MODE>& m) = delete;
 // the combinations that are built: float32 is plain only
 #define MIMO_DECLARE_LAUNCH_AS(FV, R, MODE)                                                                  \
   template <>                                                                                                \
   hipError_t launch_trial<FV, R, MODE>(const InstanceKey&, dim3, hipStream_t, const TrialParams<R>&, bool*, \
-                                       hipFuncAttributes*, double*, double);
+                                       hipFuncAttributes*, const ModeArgs<MODE>&);
 #define MIMO_DECLARE_LAUNCH(FV)                           \
   MIMO_DECLARE_LAUNCH_AS(FV, float, MIMO_MODE_PLAIN)      \
   MIMO_DECLARE_LAUNCH_AS(FV, double, MIMO_MODE_PLAIN)     \

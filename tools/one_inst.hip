@@ -29,4 +29,4 @@
 #ifndef XSYM
 #define XSYM (XNB == 1)
 #endif
-template __global__ void mimo::trial_kernel<XR, XF, XT, XNS, true, XCH, XCSI, XMW, XNB, XSYM>(mimo::TrialParams<XR>);
+template __global__ void mimo::trial_kernel<MIMO_MODE_PLAIN, XR, XF, XT, XNS, true, XCH, XCSI, XMW, XNB, XSYM>(mimo::TrialParams<XR>);
