@@ -1,9 +1,9 @@
 // libmimo_engine: C-ABI host side of the MI355X Monte-Carlo BER engine.
 //
 // Coarse seam = mp_model.Link (mp_model.py:32-329).  mimo_engine_run launches the fused
-// trial kernel (trial_kernel.h) over a batch of trials, reduces the per-trial counts on
-// the device and adds the totals into the caller's counters, like Link.simulate adds
-// into its shared mp.Array counters (mp_model.py:217-222).
+// trial kernel (trial_kernel.h; this file sees its contract alone, trial_params.h) over a batch
+// of trials, reduces the per-trial counts on the device and adds the totals into the caller's
+// counters, like Link.simulate adds into its shared mp.Array counters (mp_model.py:217-222).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/mimo_engine.h"
+#include "host_util.h"
 #include "trial_launch.h"
 #include "host_tables.h"
 #ifndef MIMO_ONLY_F  // the single-size diagnostic builds link neither beam instances nor beam.o
@@ -31,18 +32,9 @@ namespace {
 using mimo::AlphaFit;
 using mimo::fit_alpha;
 
-thread_local std::string g_err;
+using mimo::fail;
 
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t _e = (expr);                                                                    \
-    if (_e != hipSuccess) return fail(MIMO_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
+thread_local std::string g_err;  // behind mimo::set_error (below) and mimo_last_error()
 
 constexpr double kSpeedOfLight = 299792458.0;  // scipy.constants.c
 
@@ -71,16 +63,17 @@ struct Buf {
   }
   int ensure(size_t need) {
     if (need <= cap) return MIMO_OK;
-    HIP_TRY(release());
-    if constexpr (PINNED) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p), need * sizeof(T), hipHostMallocDefault));
-    else HIP_TRY(hipMalloc(&p, need * sizeof(T)));
+    MIMO_HIP_TRY(release());
+    if constexpr (PINNED)
+      MIMO_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p), need * sizeof(T), hipHostMallocDefault));
+    else MIMO_HIP_TRY(hipMalloc(&p, need * sizeof(T)));
     cap = need;
     return MIMO_OK;
   }
   int upload(const std::vector<T>& v) {  // a blocking copy; an empty table stays a null pointer
     if (v.empty()) return MIMO_OK;
     if (int rc = ensure(v.size())) return rc;
-    HIP_TRY(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    MIMO_HIP_TRY(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return MIMO_OK;
   }
 };
@@ -262,7 +255,7 @@ mimo::InstanceKey select_instance(const mimo_engine* e, bool csi) {
   return k;
 }
 
-// The mode arguments of a launch (trial_kernel.h ModeArgs), built here alone: the engine's buffer
+// The mode arguments of a launch (trial_params.h ModeArgs), built here alone: the engine's buffer
 // that the mode's instances fill -- the launch's rows; the beam instances its cells and the coded
 // instances its channel values, from which the mode's second kernel forms the rows -- and the scale.
 template <int MODE>
@@ -566,11 +559,11 @@ void fill_point(mimo_engine* e, const mimo_point& pt, uint64_t seed, uint64_t fi
 // (A call after one that failed half-way keeps what that one created.)
 int ensure_device(mimo_engine* e) {
   if (e->ready) return MIMO_OK;
-  if (e->cfg.device >= 0) HIP_TRY(hipSetDevice(e->cfg.device));
-  HIP_TRY(hipGetDevice(&e->device));
-  if (!e->stream) HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+  if (e->cfg.device >= 0) MIMO_HIP_TRY(hipSetDevice(e->cfg.device));
+  MIMO_HIP_TRY(hipGetDevice(&e->device));
+  if (!e->stream) MIMO_HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
   for (hipEvent_t* ev : {&e->ev0, &e->ev1, &e->ev2, &e->ev3})
-    if (!*ev) HIP_TRY(hipEventCreate(ev));
+    if (!*ev) MIMO_HIP_TRY(hipEventCreate(ev));
   const int F = e->cfg.n_fft, S = e->cfg.n_sub_carr, A = e->cfg.n_ant;
   // the FFT tables (host_tables.h): the team FFT's per team size, the split FFT's in place of
   // the fp64 team's where the instance runs it, the wave-split FFT's where used
@@ -651,7 +644,7 @@ int ensure_device(mimo_engine* e) {
 // the create-time table -- and a TDL engine's profile tables.
 int refresh_channel_tables(mimo_engine* e) {
   if (!e->tab_stale && !e->tdl_stale) return MIMO_OK;
-  HIP_TRY(hipStreamSynchronize(e->stream));  // no launch of a call that failed half-way still reads them
+  MIMO_HIP_TRY(hipStreamSynchronize(e->stream));  // no launch of a call that failed half-way still reads them
   if (e->tab_stale) {
     if (e->n_bank > 0) {
       if (int rc = e->cfg.precision == MIMO_PREC_F32 ? e->tab32.upload(e->bank32) : e->tab64.upload(e->bank64)) return rc;
@@ -942,13 +935,13 @@ int prepare_second(mimo_engine* e, const RowMode& rm, const Plan& plan, int n_id
     const size_t cells = 2 * plan.max_blocks * (size_t)c.n_ant * (size_t)c.n_fft * 2;  // doubles
     if (int rc = e->bcell.ensure(std::max<size_t>(2, cells))) return rc;
     if (int rc = e->bgeo.ensure(rm.beam->geo.size())) return rc;
-    HIP_TRY(hipMemcpyAsync(e->bgeo.p, rm.beam->geo.data(), sizeof(double) * rm.beam->geo.size(), hipMemcpyHostToDevice,
-                           e->stream));
+    MIMO_HIP_TRY(hipMemcpyAsync(e->bgeo.p, rm.beam->geo.data(), sizeof(double) * rm.beam->geo.size(),
+                                hipMemcpyHostToDevice, e->stream));
   } else {
     const std::vector<int32_t>& tab = rm.coded->code.tables;
     if (int rc = e->cchan.ensure(std::max<size_t>(1, plan.max_blocks * (size_t)n_idx * rm.coded->stream))) return rc;
     if (int rc = e->ctab.ensure(tab.size())) return rc;
-    HIP_TRY(hipMemcpyAsync(e->ctab.p, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice, e->stream));
+    MIMO_HIP_TRY(hipMemcpyAsync(e->ctab.p, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice, e->stream));
   }
   return MIMO_OK;
 }
@@ -970,11 +963,11 @@ int launch_second(mimo_engine* e, const RowMode& rm, uint32_t nb, int n_idx, uin
   }
   if (se != hipSuccess)
     return fail(MIMO_EHIP, std::string(rm.coded ? "decoder" : "beamforming") + " kernel launch: " + hipGetErrorString(se));
-  HIP_TRY(hipEventRecord(e->ev2, e->stream));
+  MIMO_HIP_TRY(hipEventRecord(e->ev2, e->stream));
   if (rm.coded && rm.coded->per_trial_chan) {
     const size_t per_trial = (size_t)n_idx * rm.coded->stream;
-    HIP_TRY(hipMemcpyAsync(rm.coded->per_trial_chan + trials_done * per_trial, e->cchan.p, (size_t)nb * per_trial,
-                           hipMemcpyDeviceToHost, e->stream));
+    MIMO_HIP_TRY(hipMemcpyAsync(rm.coded->per_trial_chan + trials_done * per_trial, e->cchan.p, (size_t)nb * per_trial,
+                                hipMemcpyDeviceToHost, e->stream));
   }
   return MIMO_OK;
 }
@@ -1004,31 +997,31 @@ int run_launch(mimo_engine* e, const mimo::InstanceKey& key, const mimo::TrialPa
   }
   // the whole blob (unused tails included: one contiguous DMA)
   const size_t blob_bytes = tdl ? o.tdl + t.nseg * sizeof(mimo::TdlSeg) : o.point_of + nsl * sizeof(int32_t);
-  HIP_TRY(hipMemcpyAsync(e->blob.p, e->h_blob.p, blob_bytes, hipMemcpyHostToDevice, e->stream));
+  MIMO_HIP_TRY(hipMemcpyAsync(e->blob.p, e->h_blob.p, blob_bytes, hipMemcpyHostToDevice, e->stream));
   if (tdl) {
     // the bank entries of this launch's blocks, in device memory (tdl.hip), ahead of the trial kernel
     // on the same stream and timed on an event of its own
-    HIP_TRY(hipEventRecord(e->ev3, e->stream));
+    MIMO_HIP_TRY(hipEventRecord(e->ev3, e->stream));
     const hipError_t ge = mimo::launch_tdl(
         e->stream, e->tdl, e->tdl_blob.p, reinterpret_cast<const mimo::TdlSeg*>(e->blob.p + o.tdl), kp.point_start,
         (int)t.nseg, nb, e->cfg.n_sub_carr, sizeof(R) == 8 ? e->tab64.p : nullptr, sizeof(R) == 8 ? nullptr : e->tab32.p,
         nullptr);
     if (ge != hipSuccess) return fail(MIMO_EHIP, std::string("TDL generator kernel launch: ") + hipGetErrorString(ge));
   }
-  HIP_TRY(hipEventRecord(e->ev0, e->stream));
+  MIMO_HIP_TRY(hipEventRecord(e->ev0, e->stream));
   bool found = false;
   const hipError_t le = launch(rm.mode, e, key, dim3(nb), kp, &found, nullptr, rm.scale);
   if (!found) return fail(MIMO_ENOKERNEL, "no kernel instance for " + e->desc);
   if (le != hipSuccess) return fail(MIMO_EHIP, std::string("trial kernel launch: ") + hipGetErrorString(le));
-  HIP_TRY(hipEventRecord(e->ev1, e->stream));
+  MIMO_HIP_TRY(hipEventRecord(e->ev1, e->stream));
   if (rm.second())
     if (int rc = launch_second(e, rm, nb, n_idx, pg->trials_done)) return rc;
   hipLaunchKernelGGL(reduce_counts, dim3((unsigned)nsl, n_idx), dim3(256), 0, e->stream, e->counts.p, d_slice_first,
                      reinterpret_cast<const int32_t*>(e->blob.p + o.point_of), n_idx, e->tot.p);
-  HIP_TRY(hipGetLastError());
+  MIMO_HIP_TRY(hipGetLastError());
   if (per_trial)
-    HIP_TRY(hipMemcpyAsync(per_trial + pg->trials_done * n_idx, e->counts.p, (size_t)nb * n_idx * sizeof(uint32_t),
-                           hipMemcpyDeviceToHost, e->stream));
+    MIMO_HIP_TRY(hipMemcpyAsync(per_trial + pg->trials_done * n_idx, e->counts.p, (size_t)nb * n_idx * sizeof(uint32_t),
+                                hipMemcpyDeviceToHost, e->stream));
   if (rm.rows()) {
     const int w = rm.width;
     if (rm.mode == MIMO_MODE_MEAS)
@@ -1037,27 +1030,27 @@ int run_launch(mimo_engine* e, const mimo::InstanceKey& key, const mimo::TrialPa
     else
       hipLaunchKernelGGL(reduce_spec, dim3((unsigned)nsl, (unsigned)((w + kReduceSpecThreads - 1) / kReduceSpecThreads)),
                          dim3(kReduceSpecThreads), 0, e->stream, e->rows.p, d_slice_first, w, e->part.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(pg->part.data() + pg->part_point.size() * w, e->part.p, nsl * w * sizeof(double),
-                           hipMemcpyDeviceToHost, e->stream));
+    MIMO_HIP_TRY(hipGetLastError());
+    MIMO_HIP_TRY(hipMemcpyAsync(pg->part.data() + pg->part_point.size() * w, e->part.p, nsl * w * sizeof(double),
+                                hipMemcpyDeviceToHost, e->stream));
     pg->part_point.insert(pg->part_point.end(), t.point_of, t.point_of + nsl);
     if (rm.per_trial_out)
-      HIP_TRY(hipMemcpyAsync(rm.per_trial_out + pg->trials_done * w, e->rows.p, (size_t)nb * w * sizeof(double),
-                             hipMemcpyDeviceToHost, e->stream));
+      MIMO_HIP_TRY(hipMemcpyAsync(rm.per_trial_out + pg->trials_done * w, e->rows.p, (size_t)nb * w * sizeof(double),
+                                  hipMemcpyDeviceToHost, e->stream));
   }
   pg->trials_done += nb;
   // the host tables of the next launch are rewritten: wait for this one's copies
-  HIP_TRY(hipEventSynchronize(e->ev1));
+  MIMO_HIP_TRY(hipEventSynchronize(e->ev1));
   float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+  MIMO_HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
   pg->ms += ms;
   if (tdl) {
-    HIP_TRY(hipEventElapsedTime(&ms, e->ev3, e->ev0));
+    MIMO_HIP_TRY(hipEventElapsedTime(&ms, e->ev3, e->ev0));
     pg->chan_ms += ms;
   }
   if (rm.second()) {
-    HIP_TRY(hipEventSynchronize(e->ev2));
-    HIP_TRY(hipEventElapsedTime(&ms, e->ev1, e->ev2));
+    MIMO_HIP_TRY(hipEventSynchronize(e->ev2));
+    MIMO_HIP_TRY(hipEventElapsedTime(&ms, e->ev1, e->ev2));
     pg->second_ms += ms;
   }
   return MIMO_OK;
@@ -1134,7 +1127,7 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
     if (int rc = prepare_second(e, rm, plan, n_idx)) return rc;
   if (int rc = e->counts.ensure((size_t)(1ull << 20) * n_idx)) return rc;
   if (int rc = e->tot.ensure((size_t)n_points * n_idx)) return rc;
-  HIP_TRY(hipMemsetAsync(e->tot.p, 0, sizeof(unsigned long long) * n_points * n_idx, e->stream));
+  MIMO_HIP_TRY(hipMemsetAsync(e->tot.p, 0, sizeof(unsigned long long) * n_points * n_idx, e->stream));
   if (int rc = key.f64 ? run_launches(e, key, base_params<double>(e, key, it, incl_clean, n_idx), plan, n_points, pts,
                                       seeds, rm, per_trial, &pg)
                        : run_launches(e, key, base_params<float>(e, key, it, incl_clean, n_idx), plan, n_points, pts,
@@ -1142,9 +1135,9 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
     return rc;
 
   std::vector<unsigned long long> tot((size_t)n_points * n_idx);
-  HIP_TRY(hipMemcpyAsync(tot.data(), e->tot.p, sizeof(unsigned long long) * tot.size(), hipMemcpyDeviceToHost,
-                         e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
+  MIMO_HIP_TRY(hipMemcpyAsync(tot.data(), e->tot.p, sizeof(unsigned long long) * tot.size(), hipMemcpyDeviceToHost,
+                              e->stream));
+  MIMO_HIP_TRY(hipStreamSynchronize(e->stream));
   const uint64_t bits_per_trial = (uint64_t)c.n_sub_carr * (uint64_t)std::lround(std::log2((double)c.constel_size));
   for (int i = 0; i < n_points; ++i)
     for (int j = 0; j < n_idx; ++j) {

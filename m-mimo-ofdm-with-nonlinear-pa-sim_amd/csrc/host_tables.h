@@ -9,7 +9,12 @@
 #include <cmath>
 #include <vector>
 
-#include "trial_launch.h"
+#include "real.h"
+#include "alpha_fit.h"
+// (the FFT headers for their constexpr layout functions alone: fft_tw_off, ct_rows, wave_fft_fw ...)
+#include "team_fft.h"
+#include "wave_fft.h"
+#include "split_fft.h"
 
 namespace mimo {
 

@@ -8,6 +8,8 @@
 
 #include <algorithm>
 
+#include "host_util.h"
+
 namespace mimo {
 namespace {
 
@@ -198,49 +200,28 @@ hipError_t launch_ldpc(hipStream_t st, const LdpcHost& code, const int32_t* tabl
 
 }  // namespace mimo
 
-namespace mimo {
-void set_error(const std::string& m);  // engine.hip: one thread-local message for mimo_last_error()
-}
-
-namespace {
-struct DevMem {
-  void* p = nullptr;
-  hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
-  ~DevMem() {
-    if (p) (void)hipFree(p);
-  }
-};
-int lfail(int code, const std::string& m) {
-  mimo::set_error(m);
-  return code;
-}
-#define L_TRY(expr)                                                                               \
-  do {                                                                                            \
-    hipError_t _e = (expr);                                                                       \
-    if (_e != hipSuccess) return lfail(MIMO_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-}  // namespace
+using mimo::fail;
 
 extern "C" int32_t mimo_ldpc_decode(const mimo_ldpc_code* code, const int8_t* chan, int64_t n_cw, int16_t* app_out) {
   mimo::LdpcHost h;
   std::string err;
-  if (!mimo::ldpc_prepare(code, &h, &err)) return lfail(MIMO_EINVAL, err);
-  if (n_cw < 0) return lfail(MIMO_EINVAL, "n_cw must be >= 0");
+  if (!mimo::ldpc_prepare(code, &h, &err)) return fail(MIMO_EINVAL, err);
+  if (n_cw < 0) return fail(MIMO_EINVAL, "n_cw must be >= 0");
   if (n_cw == 0) return MIMO_OK;
-  if (!chan || !app_out) return lfail(MIMO_EINVAL, "null chan or app_out");
+  if (!chan || !app_out) return fail(MIMO_EINVAL, "null chan or app_out");
   const int64_t N = h.n_bits();
-  if (n_cw > (int64_t)0x7fffffff) return lfail(MIMO_EINVAL, "n_cw must be below 2^31");
+  if (n_cw > (int64_t)0x7fffffff) return fail(MIMO_EINVAL, "n_cw must be below 2^31");
   for (int64_t i = 0; i < n_cw * N; ++i)
     if (chan[i] < -63 || chan[i] > 63)
-      return lfail(MIMO_EINVAL, "chan[" + std::to_string(i) + "] must be in [-63, 63]");
-  DevMem dt, dc, da;
-  L_TRY(dt.alloc(h.tables.size() * sizeof(int32_t)));
-  L_TRY(dc.alloc((size_t)(n_cw * N)));
-  L_TRY(da.alloc((size_t)(n_cw * N) * sizeof(int16_t)));
-  L_TRY(hipMemcpy(dt.p, h.tables.data(), h.tables.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  L_TRY(hipMemcpy(dc.p, chan, (size_t)(n_cw * N), hipMemcpyHostToDevice));
-  L_TRY(mimo::launch_ldpc(nullptr, h, static_cast<const int32_t*>(dt.p), static_cast<const int8_t*>(dc.p), n_cw, N, 1,
-                          1, nullptr, static_cast<int16_t*>(da.p)));
-  L_TRY(hipMemcpy(app_out, da.p, (size_t)(n_cw * N) * sizeof(int16_t), hipMemcpyDeviceToHost));
+      return fail(MIMO_EINVAL, "chan[" + std::to_string(i) + "] must be in [-63, 63]");
+  mimo::DBuf dt, dc, da;
+  MIMO_HIP_TRY(dt.alloc(h.tables.size() * sizeof(int32_t)));
+  MIMO_HIP_TRY(dc.alloc((size_t)(n_cw * N)));
+  MIMO_HIP_TRY(da.alloc((size_t)(n_cw * N) * sizeof(int16_t)));
+  MIMO_HIP_TRY(hipMemcpy(dt.p, h.tables.data(), h.tables.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(hipMemcpy(dc.p, chan, (size_t)(n_cw * N), hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(mimo::launch_ldpc(nullptr, h, static_cast<const int32_t*>(dt.p), static_cast<const int8_t*>(dc.p),
+                                 n_cw, N, 1, 1, nullptr, static_cast<int16_t*>(da.p)));
+  MIMO_HIP_TRY(hipMemcpy(app_out, da.p, (size_t)(n_cw * N) * sizeof(int16_t), hipMemcpyDeviceToHost));
   return MIMO_OK;
 }

@@ -13,33 +13,21 @@
 #include <type_traits>
 #include <vector>
 
+#include "host_util.h"
+#include "trial_kernel.h"
+#include "trial_launch.h"
 #include "host_tables.h"
 #include "probe.h"
 
 namespace {
-
-thread_local std::string g_perr;
-
-int pfail(int code, const std::string& m) {
-  g_perr = m;
-  return code;
+thread_local std::string g_perr;  // this library's message, behind mimo_probe_last_error()
 }
+namespace mimo {
+void set_error(const std::string& m) { g_perr = m; }
+}  // namespace mimo
+static_assert(MIMO_PROBE_EHIP == MIMO_EHIP, "MIMO_HIP_TRY returns the probe's code for a HIP error");
 
-#define P_TRY(expr)                                                                                        \
-  do {                                                                                                     \
-    hipError_t _e = (expr);                                                                                \
-    if (_e != hipSuccess) return pfail(MIMO_PROBE_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
-struct DBuf {
-  void* p = nullptr;
-  hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
-  ~DBuf() {
-    if (p) (void)hipFree(p);
-  }
-  template <typename T>
-  T* as() { return reinterpret_cast<T*>(p); }
-};
+namespace {
 
 using namespace mimo;
 
@@ -113,19 +101,19 @@ int run_fft(int masked, int pa_kind, double sat, double p, double toi, int n_row
   const std::vector<C> tw = instance_table<R>(F, T);
   DBuf dtw, din, dout;
   const size_t bytes = sizeof(C) * (size_t)F * n_rows;
-  P_TRY(dtw.alloc(sizeof(C) * tw.size()));
-  P_TRY(din.alloc(bytes));
-  P_TRY(dout.alloc(bytes));
-  P_TRY(hipMemcpy(dtw.p, tw.data(), sizeof(C) * tw.size(), hipMemcpyHostToDevice));
-  P_TRY(hipMemcpy(din.p, in, bytes, hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(dtw.alloc(sizeof(C) * tw.size()));
+  MIMO_HIP_TRY(din.alloc(bytes));
+  MIMO_HIP_TRY(dout.alloc(bytes));
+  MIMO_HIP_TRY(hipMemcpy(dtw.p, tw.data(), sizeof(C) * tw.size(), hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(hipMemcpy(din.p, in, bytes, hipMemcpyHostToDevice));
   // the PA parameters as engine.hip fill_point forms them
   const R sat_r = (R)sat, sqrt_sat = (R)std::sqrt(std::max(sat, 0.0)), inv_sat = sat > 0 ? (R)(1.0 / sat) : R(0);
   if (n_rows > 0)
     hipLaunchKernelGGL((probe_fft_kernel<R, F, T, NBUF>), dim3((unsigned)n_rows), dim3(T), 0, 0, din.as<C>(),
                        dout.as<C>(), dtw.as<C>(), masked, pa_kind, sat_r, sqrt_sat, inv_sat, (R)p, (R)toi);
-  P_TRY(hipGetLastError());
-  P_TRY(hipDeviceSynchronize());
-  P_TRY(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
+  MIMO_HIP_TRY(hipGetLastError());
+  MIMO_HIP_TRY(hipDeviceSynchronize());
+  MIMO_HIP_TRY(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
   return MIMO_PROBE_OK;
 }
 
@@ -165,11 +153,11 @@ int by_variant(int prec, int variant, const FftArgs& a) {
       if (variant == 3) return fft_or_info<float, F, alt_team_size(F), 2>(a);
     }
   }
-  return pfail(MIMO_PROBE_ENOINST, "no such FFT instance");
+  return fail(MIMO_PROBE_ENOINST, "no such FFT instance");
 }
 
 int by_size(int prec, int F, int variant, const FftArgs& a) {
-  if (prec != 0 && prec != 1) return pfail(MIMO_PROBE_EINVAL, "prec must be 0 (float64) or 1 (float32)");
+  if (prec != 0 && prec != 1) return fail(MIMO_PROBE_EINVAL, "prec must be 0 (float64) or 1 (float32)");
   switch (F) {
     case 128: return by_variant<128>(prec, variant, a);
     case 256: return by_variant<256>(prec, variant, a);
@@ -178,7 +166,7 @@ int by_size(int prec, int F, int variant, const FftArgs& a) {
     case 2048: return by_variant<2048>(prec, variant, a);
     case 4096: return by_variant<4096>(prec, variant, a);
     case 8192: return by_variant<8192>(prec, variant, a);
-    default: return pfail(MIMO_PROBE_EINVAL, "F must be a power of two in [128, 8192]");
+    default: return fail(MIMO_PROBE_EINVAL, "F must be a power of two in [128, 8192]");
   }
 }
 
@@ -233,10 +221,10 @@ int run_pa(int cold_out, int pa_kind, double sat, double p, double toi, int64_t 
   const int64_t n_tiles = (n + kPaP - 1) / kPaP;
   const size_t padded = sizeof(C) * (size_t)n_tiles * kPaP, bytes = sizeof(C) * (size_t)n;
   DBuf din, dout;
-  P_TRY(din.alloc(padded));
-  P_TRY(dout.alloc(padded));
-  P_TRY(hipMemset(din.p, 0, padded ? padded : 1));  // the last tile's tail: zeros (in bounds, defined)
-  P_TRY(hipMemcpy(din.p, in, bytes, hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(din.alloc(padded));
+  MIMO_HIP_TRY(dout.alloc(padded));
+  MIMO_HIP_TRY(hipMemset(din.p, 0, padded ? padded : 1));  // the last tile's tail: zeros (in bounds, defined)
+  MIMO_HIP_TRY(hipMemcpy(din.p, in, bytes, hipMemcpyHostToDevice));
   const R sat_r = (R)sat, sqrt_sat = (R)std::sqrt(std::max(sat, 0.0)), inv_sat = sat > 0 ? (R)(1.0 / sat) : R(0);
   const unsigned blocks = (unsigned)((n_tiles + kPaT - 1) / kPaT);
   if (blocks > 0) {
@@ -247,9 +235,9 @@ int run_pa(int cold_out, int pa_kind, double sat, double p, double toi, int64_t 
       hipLaunchKernelGGL((probe_pa_kernel<R, false>), dim3(blocks), dim3(kPaT), 0, 0, din.as<C>(), dout.as<C>(), n_tiles,
                          pa_kind, sat_r, sqrt_sat, inv_sat, (R)p, (R)toi);
   }
-  P_TRY(hipGetLastError());
-  P_TRY(hipDeviceSynchronize());
-  P_TRY(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
+  MIMO_HIP_TRY(hipGetLastError());
+  MIMO_HIP_TRY(hipDeviceSynchronize());
+  MIMO_HIP_TRY(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
   return MIMO_PROBE_OK;
 }
 
@@ -306,7 +294,7 @@ const char* mimo_probe_last_error(void) { return g_perr.c_str(); }
 
 int32_t mimo_probe_fft_info(int32_t prec, int32_t F, int32_t variant, int32_t* team, uint32_t* zero_mask,
                             int32_t* fft_kind) {
-  if (!team || !zero_mask || !fft_kind) return pfail(MIMO_PROBE_EINVAL, "null output");
+  if (!team || !zero_mask || !fft_kind) return fail(MIMO_PROBE_EINVAL, "null output");
   FftArgs a{};
   a.team = team;
   a.zero_mask = zero_mask;
@@ -316,11 +304,11 @@ int32_t mimo_probe_fft_info(int32_t prec, int32_t F, int32_t variant, int32_t* t
 
 int32_t mimo_probe_fft(int32_t prec, int32_t F, int32_t variant, int32_t masked, int32_t pa_kind, double sat, double p,
                        double toi, int32_t n_rows, const void* in_freq, void* out_freq) {
-  if (n_rows < 0 || n_rows > 65535) return pfail(MIMO_PROBE_EINVAL, "n_rows must be in [0, 65535]");
-  if (!in_freq || !out_freq) return pfail(MIMO_PROBE_EINVAL, "null array");
-  if (pa_kind < PA_NONE || pa_kind > PA_TOI) return pfail(MIMO_PROBE_EINVAL, "unknown PA kind");
-  if ((pa_kind == PA_SOFTLIM || pa_kind == PA_RAPP) && !(sat > 0)) return pfail(MIMO_PROBE_EINVAL, "sat must be > 0");
-  if (pa_kind == PA_RAPP && !(p > 0)) return pfail(MIMO_PROBE_EINVAL, "p must be > 0");
+  if (n_rows < 0 || n_rows > 65535) return fail(MIMO_PROBE_EINVAL, "n_rows must be in [0, 65535]");
+  if (!in_freq || !out_freq) return fail(MIMO_PROBE_EINVAL, "null array");
+  if (pa_kind < PA_NONE || pa_kind > PA_TOI) return fail(MIMO_PROBE_EINVAL, "unknown PA kind");
+  if ((pa_kind == PA_SOFTLIM || pa_kind == PA_RAPP) && !(sat > 0)) return fail(MIMO_PROBE_EINVAL, "sat must be > 0");
+  if (pa_kind == PA_RAPP && !(p > 0)) return fail(MIMO_PROBE_EINVAL, "p must be > 0");
   FftArgs a{};
   a.masked = masked ? 1 : 0;
   a.pa_kind = pa_kind;
@@ -334,44 +322,44 @@ int32_t mimo_probe_fft(int32_t prec, int32_t F, int32_t variant, int32_t masked,
 }
 
 int32_t mimo_probe_math(int32_t fn, int64_t n, const void* in, double* out0, double* out1) {
-  if (fn < 0 || fn > 7) return pfail(MIMO_PROBE_EINVAL, "fn must be in [0, 7]");
-  if (n < 0 || n > (int64_t)1 << 28) return pfail(MIMO_PROBE_EINVAL, "n must be in [0, 2^28]");
-  if (!in || !out0) return pfail(MIMO_PROBE_EINVAL, "null array");
+  if (fn < 0 || fn > 7) return fail(MIMO_PROBE_EINVAL, "fn must be in [0, 7]");
+  if (n < 0 || n > (int64_t)1 << 28) return fail(MIMO_PROBE_EINVAL, "n must be in [0, 2^28]");
+  if (!in || !out0) return fail(MIMO_PROBE_EINVAL, "null array");
   const size_t in_bytes = (size_t)n * (fn <= 1 ? sizeof(uint32_t) : sizeof(double)), out_bytes = (size_t)n * sizeof(double);
   const std::vector<double2> lut = lut64_table();
   DBuf dlut, din, d0, d1;
-  P_TRY(dlut.alloc(sizeof(double2) * lut.size()));
-  P_TRY(din.alloc(in_bytes));
-  P_TRY(d0.alloc(out_bytes));
-  if (out1) P_TRY(d1.alloc(out_bytes));
-  P_TRY(hipMemcpy(dlut.p, lut.data(), sizeof(double2) * lut.size(), hipMemcpyHostToDevice));
-  P_TRY(hipMemcpy(din.p, in, in_bytes, hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(dlut.alloc(sizeof(double2) * lut.size()));
+  MIMO_HIP_TRY(din.alloc(in_bytes));
+  MIMO_HIP_TRY(d0.alloc(out_bytes));
+  if (out1) MIMO_HIP_TRY(d1.alloc(out_bytes));
+  MIMO_HIP_TRY(hipMemcpy(dlut.p, lut.data(), sizeof(double2) * lut.size(), hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(hipMemcpy(din.p, in, in_bytes, hipMemcpyHostToDevice));
   const unsigned blocks = (unsigned)((n + kMathT - 1) / kMathT);
   if (blocks > 0)
     hipLaunchKernelGGL(probe_math_kernel, dim3(blocks), dim3(kMathT), 0, 0, fn, LutSrc{dlut.as<double2>()}, din.p, n,
                        d0.as<double>(), out1 ? d1.as<double>() : nullptr);
-  P_TRY(hipGetLastError());
-  P_TRY(hipDeviceSynchronize());
-  P_TRY(hipMemcpy(out0, d0.p, out_bytes, hipMemcpyDeviceToHost));
-  if (out1) P_TRY(hipMemcpy(out1, d1.p, out_bytes, hipMemcpyDeviceToHost));
+  MIMO_HIP_TRY(hipGetLastError());
+  MIMO_HIP_TRY(hipDeviceSynchronize());
+  MIMO_HIP_TRY(hipMemcpy(out0, d0.p, out_bytes, hipMemcpyDeviceToHost));
+  if (out1) MIMO_HIP_TRY(hipMemcpy(out1, d1.p, out_bytes, hipMemcpyDeviceToHost));
   return MIMO_PROBE_OK;
 }
 
 int32_t mimo_probe_pa(int32_t prec, int32_t cold_out, int32_t pa_kind, double sat, double p, double toi, int64_t n,
                       const void* in_iq, void* out_iq) {
-  if (prec != 0 && prec != 1) return pfail(MIMO_PROBE_EINVAL, "prec must be 0 (float64) or 1 (float32)");
-  if (n < 0 || n > (int64_t)1 << 28) return pfail(MIMO_PROBE_EINVAL, "n must be in [0, 2^28]");
-  if (!in_iq || !out_iq) return pfail(MIMO_PROBE_EINVAL, "null array");
-  if (pa_kind < PA_NONE || pa_kind > PA_TOI) return pfail(MIMO_PROBE_EINVAL, "unknown PA kind");
-  if ((pa_kind == PA_SOFTLIM || pa_kind == PA_RAPP) && !(sat > 0)) return pfail(MIMO_PROBE_EINVAL, "sat must be > 0");
-  if (pa_kind == PA_RAPP && !(p > 0)) return pfail(MIMO_PROBE_EINVAL, "p must be > 0");
+  if (prec != 0 && prec != 1) return fail(MIMO_PROBE_EINVAL, "prec must be 0 (float64) or 1 (float32)");
+  if (n < 0 || n > (int64_t)1 << 28) return fail(MIMO_PROBE_EINVAL, "n must be in [0, 2^28]");
+  if (!in_iq || !out_iq) return fail(MIMO_PROBE_EINVAL, "null array");
+  if (pa_kind < PA_NONE || pa_kind > PA_TOI) return fail(MIMO_PROBE_EINVAL, "unknown PA kind");
+  if ((pa_kind == PA_SOFTLIM || pa_kind == PA_RAPP) && !(sat > 0)) return fail(MIMO_PROBE_EINVAL, "sat must be > 0");
+  if (pa_kind == PA_RAPP && !(p > 0)) return fail(MIMO_PROBE_EINVAL, "p must be > 0");
   return prec == 0 ? run_pa<double>(cold_out, pa_kind, sat, p, toi, n, in_iq, out_iq)
                    : run_pa<float>(cold_out, pa_kind, sat, p, toi, n, in_iq, out_iq);
 }
 
 int32_t mimo_probe_alpha_fit(double g0sq, double* amono19, double* apoly9, double* xlim) {
-  if (!(g0sq > 0) || !std::isfinite(g0sq)) return pfail(MIMO_PROBE_EINVAL, "g0sq must be finite and > 0");
-  if (!amono19 || !apoly9 || !xlim) return pfail(MIMO_PROBE_EINVAL, "null output");
+  if (!(g0sq > 0) || !std::isfinite(g0sq)) return fail(MIMO_PROBE_EINVAL, "g0sq must be finite and > 0");
+  if (!amono19 || !apoly9 || !xlim) return fail(MIMO_PROBE_EINVAL, "null output");
   const AlphaFit f = fit_alpha(g0sq);
   for (int i = 0; i < 19; ++i) amono19[i] = f.amono[i];
   for (int i = 0; i < 9; ++i) apoly9[i] = f.apoly[i];
@@ -380,13 +368,13 @@ int32_t mimo_probe_alpha_fit(double g0sq, double* amono19, double* apoly9, doubl
 }
 
 int32_t mimo_probe_table(int32_t kind, int32_t prec, int32_t F, void* buf, int64_t* n) {
-  if (!n) return pfail(MIMO_PROBE_EINVAL, "null length");
-  if (prec != 0 && prec != 1) return pfail(MIMO_PROBE_EINVAL, "prec must be 0 (float64) or 1 (float32)");
+  if (!n) return fail(MIMO_PROBE_EINVAL, "null length");
+  if (prec != 0 && prec != 1) return fail(MIMO_PROBE_EINVAL, "prec must be 0 (float64) or 1 (float32)");
   if (kind == 4) {
-    if (prec != 0) return pfail(MIMO_PROBE_ENOINST, "lut64 is a float64 table");
+    if (prec != 0) return fail(MIMO_PROBE_ENOINST, "lut64 is a float64 table");
     return give_table(lut64_table(), buf, n);
   }
-  if (!known_size(F)) return pfail(MIMO_PROBE_EINVAL, "F must be a power of two in [128, 8192]");
+  if (!known_size(F)) return fail(MIMO_PROBE_EINVAL, "F must be a power of two in [128, 8192]");
   const bool f64 = prec == 0;
   switch (kind) {
     case 0:
@@ -396,26 +384,26 @@ int32_t mimo_probe_table(int32_t kind, int32_t prec, int32_t F, void* buf, int64
       }
       return give_table(team_twiddles(F, team_size(F), TwToF32{}), buf, n);
     case 1:
-      if (f64) return pfail(MIMO_PROBE_ENOINST, "the alternative team is float32 only");
+      if (f64) return fail(MIMO_PROBE_ENOINST, "the alternative team is float32 only");
       return give_table(team_twiddles(F, alt_team_size(F), TwToF32{}), buf, n);
     case 2:
-      if (!f64) return pfail(MIMO_PROBE_ENOINST, "the wave-split FFT's table is float64 only");
+      if (!f64) return fail(MIMO_PROBE_ENOINST, "the wave-split FFT's table is float64 only");
       if (!wave_fft_used(F, team_size64(F), true))
-        return pfail(MIMO_PROBE_ENOINST, "no wave-split FFT at this size and precision");
+        return fail(MIMO_PROBE_ENOINST, "no wave-split FFT at this size and precision");
       return give_table(wave_twiddles(F, team_size64(F), TwToF64{}), buf, n);
     case 3:
       if (!f64 || !split_fft_used(F, team_size64(F), true))
-        return pfail(MIMO_PROBE_ENOINST, "no split FFT at this size and precision");
+        return fail(MIMO_PROBE_ENOINST, "no split FFT at this size and precision");
       return give_table(split_twiddles(F, team_size64(F)), buf, n);
     default:
-      return pfail(MIMO_PROBE_EINVAL, "kind must be in [0, 4]");
+      return fail(MIMO_PROBE_EINVAL, "kind must be in [0, 4]");
   }
 }
 
 int32_t mimo_probe_xaddr(int32_t F, const uint32_t* words_in, uint32_t* words, uint32_t* sites, int32_t* info) {
-  if (!words || !sites || !info) return pfail(MIMO_PROBE_EINVAL, "null output");
+  if (!words || !sites || !info) return fail(MIMO_PROBE_EINVAL, "null output");
   if (!known_size(F) || !wave_fft_used(F, team_size64(F), true))
-    return pfail(MIMO_PROBE_ENOINST, "no wave-split FFT at this size");
+    return fail(MIMO_PROBE_ENOINST, "no wave-split FFT at this size");
   return F == 1024 ? xaddr_of<1024>(words_in, words, sites, info) : xaddr_of<2048>(words_in, words, sites, info);
 }
 

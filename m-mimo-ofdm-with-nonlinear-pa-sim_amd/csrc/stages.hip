@@ -10,19 +10,19 @@
 #include <vector>
 
 #include "../../include/mimo_engine.h"
+#include "host_util.h"
 #include "alpha_fit.h"
 #include "philox.h"
+#include "qam.h"
 #include "softbits.h"
 
 namespace {
 
-int sfail(int code, const std::string& m);
-
-#define S_TRY(expr)                                                                               \
-  do {                                                                                            \
-    hipError_t _e = (expr);                                                                       \
-    if (_e != hipSuccess) return sfail(MIMO_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
+using mimo::fail;
+using mimo::DBuf;
+// the trial kernel's slicer and inverse Gray code (qam.h)
+using mimo::gray_inv;
+using mimo::slice_axis;
 
 bool pow2(long v) { return v > 0 && (v & (v - 1)) == 0; }
 int qam_l(int M) {
@@ -44,32 +44,6 @@ const char* bad_ofdm(long F, long S, long cp, int64_t batch) {
   return nullptr;
 }
 
-// RAII device buffer
-struct DBuf {
-  void* p = nullptr;
-  hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
-  ~DBuf() {
-    if (p) (void)hipFree(p);
-  }
-  template <typename T>
-  T* as() { return reinterpret_cast<T*>(p); }
-};
-
-__device__ __forceinline__ uint32_t gray(uint32_t i) { return i ^ (i >> 1); }
-__device__ __forceinline__ uint32_t gray_inv(uint32_t g) {
-  g ^= g >> 1; g ^= g >> 2; g ^= g >> 4; g ^= g >> 8;
-  return g;
-}
-// Per-axis slicer with the reference's lowest-label tie-break (modulation.py:75-76).
-__device__ __forceinline__ uint32_t slice_axis_d(double x, int L) {
-  const double q = (x + (double)L) * 0.5;
-  const double fi = floor(q);
-  long i = (long)fi;
-  if (q == fi && i > 0 && i < L) i = gray((uint32_t)(i - 1)) < gray((uint32_t)i) ? i - 1 : i;
-  i = i < 0 ? 0 : (i > L - 1 ? L - 1 : i);
-  return gray((uint32_t)i);
-}
-
 __global__ void k_qam_map(int L, int hb, const int32_t* lab, int64_t n, double2* out) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const uint32_t l = (uint32_t)lab[i];
@@ -80,7 +54,7 @@ __global__ void k_qam_map(int L, int hb, const int32_t* lab, int64_t n, double2*
 
 __global__ void k_qam_slice(int L, int hb, const double2* in, int64_t n, int32_t* lab) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    lab[i] = (int32_t)((slice_axis_d(in[i].x, L) << hb) | slice_axis_d(in[i].y, L));
+    lab[i] = (int32_t)((slice_axis<double>(in[i].x, L) << hb) | slice_axis<double>(in[i].y, L));
 }
 
 // soft_decoding (modulation.py:29-59)
@@ -254,164 +228,154 @@ __global__ void k_sub(int64_t n, const double2* a, const double2* b, double2* ou
 dim3 grid_for(int64_t n) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 4096))); }
 
 int fft_device(int N, int64_t batch, int inverse, const double2* din, double2* dout) {
-  if (bad_fft(N)) return sfail(MIMO_EINVAL, kBadFft);
+  if (bad_fft(N)) return fail(MIMO_EINVAL, kBadFft);
   int logN = 0;
   while ((1 << logN) < N) ++logN;
   const size_t lds = sizeof(double2) * N;
-  S_TRY(hipFuncSetAttribute((const void*)k_fft_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  MIMO_HIP_TRY(hipFuncSetAttribute((const void*)k_fft_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   if (batch > 0) hipLaunchKernelGGL(k_fft_rows, dim3((unsigned)batch), dim3(256), lds, 0, N, logN, inverse, din, dout);
-  S_TRY(hipGetLastError());
+  MIMO_HIP_TRY(hipGetLastError());
   return MIMO_OK;
 }
 
-}  // namespace
-
-namespace mimo {
-void set_error(const std::string& m);  // engine.hip: one thread-local message for mimo_last_error()
-}
-namespace {
-int sfail(int code, const std::string& m) {
-  mimo::set_error(m);
-  return code;
-}
 }  // namespace
 
 extern "C" {
 
 int32_t mimo_qam_map(int32_t M, const int32_t* labels, int64_t n, double* out_iq) {
   const int L = qam_l(M);
-  if (!L) return sfail(MIMO_EINVAL, kBadQam);
-  if (n < 0) return sfail(MIMO_EINVAL, "n must be >= 0");
+  if (!L) return fail(MIMO_EINVAL, kBadQam);
+  if (n < 0) return fail(MIMO_EINVAL, "n must be >= 0");
   if (n == 0) return MIMO_OK;
   int hb = 0;
   while ((1 << hb) < L) ++hb;
   DBuf dl, dout;
-  S_TRY(dl.alloc(n * sizeof(int32_t)));
-  S_TRY(dout.alloc(n * sizeof(double2)));
-  S_TRY(hipMemcpy(dl.p, labels, n * sizeof(int32_t), hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(dl.alloc(n * sizeof(int32_t)));
+  MIMO_HIP_TRY(dout.alloc(n * sizeof(double2)));
+  MIMO_HIP_TRY(hipMemcpy(dl.p, labels, n * sizeof(int32_t), hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_qam_map, grid_for(n), dim3(256), 0, 0, L, hb, dl.as<int32_t>(), n, dout.as<double2>());
-  S_TRY(hipGetLastError());
-  S_TRY(hipMemcpy(out_iq, dout.p, n * sizeof(double2), hipMemcpyDeviceToHost));
+  MIMO_HIP_TRY(hipGetLastError());
+  MIMO_HIP_TRY(hipMemcpy(out_iq, dout.p, n * sizeof(double2), hipMemcpyDeviceToHost));
   return MIMO_OK;
 }
 
 int32_t mimo_qam_slice(int32_t M, const double* in_iq, int64_t n, int32_t* labels_out) {
   const int L = qam_l(M);
-  if (!L) return sfail(MIMO_EINVAL, kBadQam);
-  if (n < 0) return sfail(MIMO_EINVAL, "n must be >= 0");
+  if (!L) return fail(MIMO_EINVAL, kBadQam);
+  if (n < 0) return fail(MIMO_EINVAL, "n must be >= 0");
   if (n == 0) return MIMO_OK;
   int hb = 0;
   while ((1 << hb) < L) ++hb;
   DBuf din, dl;
-  S_TRY(din.alloc(n * sizeof(double2)));
-  S_TRY(dl.alloc(n * sizeof(int32_t)));
-  S_TRY(hipMemcpy(din.p, in_iq, n * sizeof(double2), hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(din.alloc(n * sizeof(double2)));
+  MIMO_HIP_TRY(dl.alloc(n * sizeof(int32_t)));
+  MIMO_HIP_TRY(hipMemcpy(din.p, in_iq, n * sizeof(double2), hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_qam_slice, grid_for(n), dim3(256), 0, 0, L, hb, din.as<double2>(), n, dl.as<int32_t>());
-  S_TRY(hipGetLastError());
-  S_TRY(hipMemcpy(labels_out, dl.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  MIMO_HIP_TRY(hipGetLastError());
+  MIMO_HIP_TRY(hipMemcpy(labels_out, dl.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
   return MIMO_OK;
 }
 
 int32_t mimo_qam_llr(int32_t M, const double* in_iq, int64_t n, const double* noise_var, double* llr_out) {
   const int L = qam_l(M);
-  if (!L) return sfail(MIMO_EINVAL, kBadQam);
-  if (n < 0) return sfail(MIMO_EINVAL, "n must be >= 0");
+  if (!L) return fail(MIMO_EINVAL, kBadQam);
+  if (n < 0) return fail(MIMO_EINVAL, "n must be >= 0");
   if (n == 0) return MIMO_OK;
   int hb = 0;
   while ((1 << hb) < L) ++hb;
   const int nb = 2 * hb;
   DBuf din, dnv, dout;
-  S_TRY(din.alloc(n * sizeof(double2)));
-  S_TRY(dnv.alloc(n * sizeof(double)));
-  S_TRY(dout.alloc(n * nb * sizeof(double)));
-  S_TRY(hipMemcpy(din.p, in_iq, n * sizeof(double2), hipMemcpyHostToDevice));
-  S_TRY(hipMemcpy(dnv.p, noise_var, n * sizeof(double), hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(din.alloc(n * sizeof(double2)));
+  MIMO_HIP_TRY(dnv.alloc(n * sizeof(double)));
+  MIMO_HIP_TRY(dout.alloc(n * nb * sizeof(double)));
+  MIMO_HIP_TRY(hipMemcpy(din.p, in_iq, n * sizeof(double2), hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(hipMemcpy(dnv.p, noise_var, n * sizeof(double), hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_qam_llr, grid_for(n), dim3(256), 0, 0, M, L, hb, nb, din.as<double2>(), n, dnv.as<double>(),
                      dout.as<double>());
-  S_TRY(hipGetLastError());
-  S_TRY(hipMemcpy(llr_out, dout.p, n * nb * sizeof(double), hipMemcpyDeviceToHost));
+  MIMO_HIP_TRY(hipGetLastError());
+  MIMO_HIP_TRY(hipMemcpy(llr_out, dout.p, n * nb * sizeof(double), hipMemcpyDeviceToHost));
   return MIMO_OK;
 }
 
 int32_t mimo_qam_softbits(int32_t M, const double* in_iq, int64_t n, double* out) {
   const int L = qam_l(M);
-  if (!L) return sfail(MIMO_EINVAL, kBadQam);
-  if (n < 0) return sfail(MIMO_EINVAL, "n must be >= 0");
+  if (!L) return fail(MIMO_EINVAL, kBadQam);
+  if (n < 0) return fail(MIMO_EINVAL, "n must be >= 0");
   if (n == 0) return MIMO_OK;
   int hb = 0;
   while ((1 << hb) < L) ++hb;
   const int nb = 2 * hb;
   DBuf din, dout;
-  S_TRY(din.alloc(n * sizeof(double2)));
-  S_TRY(dout.alloc(n * nb * sizeof(double)));
-  S_TRY(hipMemcpy(din.p, in_iq, n * sizeof(double2), hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(din.alloc(n * sizeof(double2)));
+  MIMO_HIP_TRY(dout.alloc(n * nb * sizeof(double)));
+  MIMO_HIP_TRY(hipMemcpy(din.p, in_iq, n * sizeof(double2), hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_qam_softbits, grid_for(n), dim3(256), 0, 0, L, hb, din.as<double2>(), n, dout.as<double>());
-  S_TRY(hipGetLastError());
-  S_TRY(hipMemcpy(out, dout.p, n * nb * sizeof(double), hipMemcpyDeviceToHost));
+  MIMO_HIP_TRY(hipGetLastError());
+  MIMO_HIP_TRY(hipMemcpy(out, dout.p, n * nb * sizeof(double), hipMemcpyDeviceToHost));
   return MIMO_OK;
 }
 
 int32_t mimo_fft(int32_t N, int64_t batch, int32_t inverse, const double* in_iq, double* out_iq) {
   // checked before anything is allocated (the size below multiplies N and batch)
-  if (bad_fft(N)) return sfail(MIMO_EINVAL, kBadFft);
-  if (batch < 0) return sfail(MIMO_EINVAL, "batch must be >= 0");
+  if (bad_fft(N)) return fail(MIMO_EINVAL, kBadFft);
+  if (batch < 0) return fail(MIMO_EINVAL, "batch must be >= 0");
   if (batch == 0) return MIMO_OK;
   DBuf din, dout;
   const size_t bytes = (size_t)N * batch * sizeof(double2);
-  S_TRY(din.alloc(bytes));
-  S_TRY(dout.alloc(bytes));
-  S_TRY(hipMemcpy(din.p, in_iq, bytes, hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(din.alloc(bytes));
+  MIMO_HIP_TRY(dout.alloc(bytes));
+  MIMO_HIP_TRY(hipMemcpy(din.p, in_iq, bytes, hipMemcpyHostToDevice));
   if (int rc = fft_device(N, batch, inverse, din.as<double2>(), dout.as<double2>())) return rc;
-  S_TRY(hipMemcpy(out_iq, dout.p, bytes, hipMemcpyDeviceToHost));
+  MIMO_HIP_TRY(hipMemcpy(out_iq, dout.p, bytes, hipMemcpyDeviceToHost));
   return MIMO_OK;
 }
 
 int32_t mimo_ofdm_tx(int32_t F, int32_t S, int32_t cp, int64_t batch, const double* sym_iq, double* td_iq) {
-  if (const char* m = bad_ofdm(F, S, cp, batch)) return sfail(MIMO_EINVAL, m);
+  if (const char* m = bad_ofdm(F, S, cp, batch)) return fail(MIMO_EINVAL, m);
   if (batch == 0) return MIMO_OK;
   DBuf ds, dfd, dtd, dout;
-  S_TRY(ds.alloc(batch * S * sizeof(double2)));
-  S_TRY(dfd.alloc(batch * F * sizeof(double2)));
-  S_TRY(dtd.alloc(batch * F * sizeof(double2)));
-  S_TRY(dout.alloc(batch * (F + cp) * sizeof(double2)));
-  S_TRY(hipMemcpy(ds.p, sym_iq, batch * S * sizeof(double2), hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(ds.alloc(batch * S * sizeof(double2)));
+  MIMO_HIP_TRY(dfd.alloc(batch * F * sizeof(double2)));
+  MIMO_HIP_TRY(dtd.alloc(batch * F * sizeof(double2)));
+  MIMO_HIP_TRY(dout.alloc(batch * (F + cp) * sizeof(double2)));
+  MIMO_HIP_TRY(hipMemcpy(ds.p, sym_iq, batch * S * sizeof(double2), hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_to_bins, grid_for(batch * F), dim3(256), 0, 0, F, S, batch, ds.as<double2>(), dfd.as<double2>());
   if (int rc = fft_device(F, batch, 1, dfd.as<double2>(), dtd.as<double2>())) return rc;
   hipLaunchKernelGGL(k_add_cp, grid_for(batch * (F + cp)), dim3(256), 0, 0, F, cp, batch, dtd.as<double2>(),
                      dout.as<double2>());
-  S_TRY(hipGetLastError());
-  S_TRY(hipMemcpy(td_iq, dout.p, batch * (F + cp) * sizeof(double2), hipMemcpyDeviceToHost));
+  MIMO_HIP_TRY(hipGetLastError());
+  MIMO_HIP_TRY(hipMemcpy(td_iq, dout.p, batch * (F + cp) * sizeof(double2), hipMemcpyDeviceToHost));
   return MIMO_OK;
 }
 
 int32_t mimo_ofdm_rx(int32_t F, int32_t S, int32_t cp, int64_t batch, const double* td_iq, double* sym_iq) {
-  if (const char* m = bad_ofdm(F, S, cp, batch)) return sfail(MIMO_EINVAL, m);
+  if (const char* m = bad_ofdm(F, S, cp, batch)) return fail(MIMO_EINVAL, m);
   if (batch == 0) return MIMO_OK;
   DBuf din, dtd, dfd, ds;
-  S_TRY(din.alloc(batch * (F + cp) * sizeof(double2)));
-  S_TRY(dtd.alloc(batch * F * sizeof(double2)));
-  S_TRY(dfd.alloc(batch * F * sizeof(double2)));
-  S_TRY(ds.alloc(batch * S * sizeof(double2)));
-  S_TRY(hipMemcpy(din.p, td_iq, batch * (F + cp) * sizeof(double2), hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(din.alloc(batch * (F + cp) * sizeof(double2)));
+  MIMO_HIP_TRY(dtd.alloc(batch * F * sizeof(double2)));
+  MIMO_HIP_TRY(dfd.alloc(batch * F * sizeof(double2)));
+  MIMO_HIP_TRY(ds.alloc(batch * S * sizeof(double2)));
+  MIMO_HIP_TRY(hipMemcpy(din.p, td_iq, batch * (F + cp) * sizeof(double2), hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_drop_cp, grid_for(batch * F), dim3(256), 0, 0, F, cp, batch, din.as<double2>(), dtd.as<double2>());
   if (int rc = fft_device(F, batch, 0, dtd.as<double2>(), dfd.as<double2>())) return rc;
   hipLaunchKernelGGL(k_from_bins, grid_for(batch * S), dim3(256), 0, 0, F, S, batch, dfd.as<double2>(), ds.as<double2>());
-  S_TRY(hipGetLastError());
-  S_TRY(hipMemcpy(sym_iq, ds.p, batch * S * sizeof(double2), hipMemcpyDeviceToHost));
+  MIMO_HIP_TRY(hipGetLastError());
+  MIMO_HIP_TRY(hipMemcpy(sym_iq, ds.p, batch * S * sizeof(double2), hipMemcpyDeviceToHost));
   return MIMO_OK;
 }
 
 int32_t mimo_pa(int32_t kind, double sat, double p, double toi, const double* in_iq, int64_t n, double* out_iq) {
-  if (kind < MIMO_PA_NONE || kind > MIMO_PA_TOI) return sfail(MIMO_EINVAL, "unknown PA kind");
-  if (n < 0) return sfail(MIMO_EINVAL, "n must be >= 0");
+  if (kind < MIMO_PA_NONE || kind > MIMO_PA_TOI) return fail(MIMO_EINVAL, "unknown PA kind");
+  if (n < 0) return fail(MIMO_EINVAL, "n must be >= 0");
   if (n == 0) return MIMO_OK;
   DBuf din, dout;
-  S_TRY(din.alloc(n * sizeof(double2)));
-  S_TRY(dout.alloc(n * sizeof(double2)));
-  S_TRY(hipMemcpy(din.p, in_iq, n * sizeof(double2), hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(din.alloc(n * sizeof(double2)));
+  MIMO_HIP_TRY(dout.alloc(n * sizeof(double2)));
+  MIMO_HIP_TRY(hipMemcpy(din.p, in_iq, n * sizeof(double2), hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_pa, grid_for(n), dim3(256), 0, 0, kind, sat, p, toi, din.as<double2>(), n, dout.as<double2>());
-  S_TRY(hipGetLastError());
-  S_TRY(hipMemcpy(out_iq, dout.p, n * sizeof(double2), hipMemcpyDeviceToHost));
+  MIMO_HIP_TRY(hipGetLastError());
+  MIMO_HIP_TRY(hipMemcpy(out_iq, dout.p, n * sizeof(double2), hipMemcpyDeviceToHost));
   return MIMO_OK;
 }
 
@@ -424,88 +388,88 @@ __global__ void k_calc_alpha(const double* g2, const double* tab, double* out) {
 }
 
 int32_t mimo_calc_alpha(const double* ibo_db, int64_t n, double* out) {
-  if (n < 0) return sfail(MIMO_EINVAL, "n < 0");
+  if (n < 0) return fail(MIMO_EINVAL, "n < 0");
   if (n == 0) return MIMO_OK;
-  if (n > (1 << 30)) return sfail(MIMO_EINVAL, "n too large");
+  if (n > (1 << 30)) return fail(MIMO_EINVAL, "n too large");
   std::vector<double> g2(n);
   for (int64_t i = 0; i < n; ++i) g2[i] = std::pow(10.0, ibo_db[i] / 10.0);  // gamma^2, modulation.py:186
   const std::vector<double> tab = mimo::alpha_segment_table();
   DBuf dg, dt, dout;
-  S_TRY(dg.alloc(n * sizeof(double)));
-  S_TRY(dt.alloc(tab.size() * sizeof(double)));
-  S_TRY(dout.alloc(n * sizeof(double)));
-  S_TRY(hipMemcpy(dg.p, g2.data(), n * sizeof(double), hipMemcpyHostToDevice));
-  S_TRY(hipMemcpy(dt.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(dg.alloc(n * sizeof(double)));
+  MIMO_HIP_TRY(dt.alloc(tab.size() * sizeof(double)));
+  MIMO_HIP_TRY(dout.alloc(n * sizeof(double)));
+  MIMO_HIP_TRY(hipMemcpy(dg.p, g2.data(), n * sizeof(double), hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(hipMemcpy(dt.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_calc_alpha, dim3((unsigned)n), dim3(64), 0, 0, dg.as<double>(), dt.as<double>(), dout.as<double>());
-  S_TRY(hipGetLastError());
-  S_TRY(hipMemcpy(out, dout.p, n * sizeof(double), hipMemcpyDeviceToHost));
+  MIMO_HIP_TRY(hipGetLastError());
+  MIMO_HIP_TRY(hipMemcpy(out, dout.p, n * sizeof(double), hipMemcpyDeviceToHost));
   return MIMO_OK;
 }
 
 int32_t mimo_mrt_precode(int32_t A, int32_t K, const double* h_iq, double* p_iq) {
-  if (A < 1) return sfail(MIMO_EINVAL, "n_ant must be >= 1");
-  if (K < 0) return sfail(MIMO_EINVAL, "n_cols must be >= 0");
+  if (A < 1) return fail(MIMO_EINVAL, "n_ant must be >= 1");
+  if (K < 0) return fail(MIMO_EINVAL, "n_cols must be >= 0");
   if (K == 0) return MIMO_OK;
   DBuf dh, dp;
   const size_t bytes = (size_t)A * K * sizeof(double2);
-  S_TRY(dh.alloc(bytes));
-  S_TRY(dp.alloc(bytes));
-  S_TRY(hipMemcpy(dh.p, h_iq, bytes, hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(dh.alloc(bytes));
+  MIMO_HIP_TRY(dp.alloc(bytes));
+  MIMO_HIP_TRY(hipMemcpy(dh.p, h_iq, bytes, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_mrt, grid_for(K), dim3(256), 0, 0, A, K, dh.as<double2>(), dp.as<double2>());
-  S_TRY(hipGetLastError());
-  S_TRY(hipMemcpy(p_iq, dp.p, bytes, hipMemcpyDeviceToHost));
+  MIMO_HIP_TRY(hipGetLastError());
+  MIMO_HIP_TRY(hipMemcpy(p_iq, dp.p, bytes, hipMemcpyDeviceToHost));
   return MIMO_OK;
 }
 
 int32_t mimo_combine(int32_t A, int64_t K, const double* h_iq, const double* y_iq, double* out_iq) {
-  if (A < 1) return sfail(MIMO_EINVAL, "n_ant must be >= 1");
-  if (K < 0) return sfail(MIMO_EINVAL, "n must be >= 0");
+  if (A < 1) return fail(MIMO_EINVAL, "n_ant must be >= 1");
+  if (K < 0) return fail(MIMO_EINVAL, "n must be >= 0");
   if (K == 0) return MIMO_OK;
   DBuf dh, dy, dout;
   const size_t bytes = (size_t)A * K * sizeof(double2);
-  S_TRY(dh.alloc(bytes));
-  S_TRY(dy.alloc(bytes));
-  S_TRY(dout.alloc(K * sizeof(double2)));
-  S_TRY(hipMemcpy(dh.p, h_iq, bytes, hipMemcpyHostToDevice));
-  S_TRY(hipMemcpy(dy.p, y_iq, bytes, hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(dh.alloc(bytes));
+  MIMO_HIP_TRY(dy.alloc(bytes));
+  MIMO_HIP_TRY(dout.alloc(K * sizeof(double2)));
+  MIMO_HIP_TRY(hipMemcpy(dh.p, h_iq, bytes, hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(hipMemcpy(dy.p, y_iq, bytes, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_combine, grid_for(K), dim3(256), 0, 0, A, K, dh.as<double2>(), dy.as<double2>(), dout.as<double2>());
-  S_TRY(hipGetLastError());
-  S_TRY(hipMemcpy(out_iq, dout.p, K * sizeof(double2), hipMemcpyDeviceToHost));
+  MIMO_HIP_TRY(hipGetLastError());
+  MIMO_HIP_TRY(hipMemcpy(out_iq, dout.p, K * sizeof(double2), hipMemcpyDeviceToHost));
   return MIMO_OK;
 }
 
 int32_t mimo_awgn(uint64_t seed, uint64_t counter, int64_t n, double noise_std, const double* in_iq, double* out_iq) {
-  if (n < 0) return sfail(MIMO_EINVAL, "n must be >= 0");
+  if (n < 0) return fail(MIMO_EINVAL, "n must be >= 0");
   if (n == 0) return MIMO_OK;
   DBuf din, dout;
-  S_TRY(din.alloc(n * sizeof(double2)));
-  S_TRY(dout.alloc(n * sizeof(double2)));
-  S_TRY(hipMemcpy(din.p, in_iq, n * sizeof(double2), hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(din.alloc(n * sizeof(double2)));
+  MIMO_HIP_TRY(dout.alloc(n * sizeof(double2)));
+  MIMO_HIP_TRY(hipMemcpy(din.p, in_iq, n * sizeof(double2), hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_awgn, grid_for(n), dim3(256), 0, 0, seed, counter, n, noise_std, din.as<double2>(),
                      dout.as<double2>());
-  S_TRY(hipGetLastError());
-  S_TRY(hipMemcpy(out_iq, dout.p, n * sizeof(double2), hipMemcpyDeviceToHost));
+  MIMO_HIP_TRY(hipGetLastError());
+  MIMO_HIP_TRY(hipMemcpy(out_iq, dout.p, n * sizeof(double2), hipMemcpyDeviceToHost));
   return MIMO_OK;
 }
 
 int32_t mimo_count_bit_errors(const int64_t* a, const int64_t* b, int64_t n, int64_t* out) {
-  if (n < 0) return sfail(MIMO_EINVAL, "n must be >= 0");
+  if (n < 0) return fail(MIMO_EINVAL, "n must be >= 0");
   if (n == 0) {
     *out = 0;
     return MIMO_OK;
   }
   DBuf da, db, dc;
-  S_TRY(da.alloc(n * sizeof(int64_t)));
-  S_TRY(db.alloc(n * sizeof(int64_t)));
-  S_TRY(dc.alloc(sizeof(unsigned long long)));
-  S_TRY(hipMemcpy(da.p, a, n * sizeof(int64_t), hipMemcpyHostToDevice));
-  S_TRY(hipMemcpy(db.p, b, n * sizeof(int64_t), hipMemcpyHostToDevice));
-  S_TRY(hipMemset(dc.p, 0, sizeof(unsigned long long)));
+  MIMO_HIP_TRY(da.alloc(n * sizeof(int64_t)));
+  MIMO_HIP_TRY(db.alloc(n * sizeof(int64_t)));
+  MIMO_HIP_TRY(dc.alloc(sizeof(unsigned long long)));
+  MIMO_HIP_TRY(hipMemcpy(da.p, a, n * sizeof(int64_t), hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(hipMemcpy(db.p, b, n * sizeof(int64_t), hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(hipMemset(dc.p, 0, sizeof(unsigned long long)));
   hipLaunchKernelGGL(k_count, grid_for(n), dim3(256), 0, 0, da.as<int64_t>(), db.as<int64_t>(), n,
                      dc.as<unsigned long long>());
-  S_TRY(hipGetLastError());
+  MIMO_HIP_TRY(hipGetLastError());
   unsigned long long c = 0;
-  S_TRY(hipMemcpy(&c, dc.p, sizeof c, hipMemcpyDeviceToHost));
+  MIMO_HIP_TRY(hipMemcpy(&c, dc.p, sizeof c, hipMemcpyDeviceToHost));
   *out = (int64_t)c;
   return MIMO_OK;
 }
@@ -518,40 +482,41 @@ int32_t mimo_cnc_receive_ex(int32_t M, int32_t F, int32_t S, int32_t pa_kind, do
                             double alpha, const int32_t* iters, int32_t n_iters, const double* in_sc_iq,
                             int32_t* labels_out, double* corrected_iq_out) {
   const int L = qam_l(M);
-  if (!L) return sfail(MIMO_EINVAL, kBadQam);
-  if (bad_fft(F)) return sfail(MIMO_EINVAL, kBadFft);
-  if (bad_sub_carr(F, S)) return sfail(MIMO_EINVAL, "n_sub_carr must be even and in [2, n_fft - 2]");
-  if (pa_kind < MIMO_PA_NONE || pa_kind > MIMO_PA_TOI) return sfail(MIMO_EINVAL, "unknown PA kind");
-  if (alpha == 0 || !std::isfinite(alpha)) return sfail(MIMO_EINVAL, "alpha must be finite and non-zero");
-  if (n_iters < 1) return sfail(MIMO_EINVAL, "empty iteration list");
+  if (!L) return fail(MIMO_EINVAL, kBadQam);
+  if (bad_fft(F)) return fail(MIMO_EINVAL, kBadFft);
+  if (bad_sub_carr(F, S)) return fail(MIMO_EINVAL, "n_sub_carr must be even and in [2, n_fft - 2]");
+  if (pa_kind < MIMO_PA_NONE || pa_kind > MIMO_PA_TOI) return fail(MIMO_EINVAL, "unknown PA kind");
+  if (alpha == 0 || !std::isfinite(alpha)) return fail(MIMO_EINVAL, "alpha must be finite and non-zero");
+  if (n_iters < 1) return fail(MIMO_EINVAL, "empty iteration list");
   int hb = 0;
   while ((1 << hb) < L) ++hb;
   int max_it = 0;
   for (int i = 0; i < n_iters; ++i) {
-    if (iters[i] < 0 || (i && iters[i] <= iters[i - 1])) return sfail(MIMO_EINVAL, "iterations must be sorted, unique, >= 0");
+    if (iters[i] < 0 || (i && iters[i] <= iters[i - 1])) return fail(MIMO_EINVAL, "iterations must be sorted, unique, >= 0");
     max_it = iters[i];
   }
   DBuf dz, dd, dv, dlab, dsym, dfd, dtd, dfd2;
-  S_TRY(dz.alloc(S * sizeof(double2)));
-  S_TRY(dd.alloc(S * sizeof(double2)));
-  S_TRY(dv.alloc(S * sizeof(double2)));
-  S_TRY(dlab.alloc(S * sizeof(int32_t)));
-  S_TRY(dsym.alloc(S * sizeof(double2)));
-  S_TRY(dfd.alloc(F * sizeof(double2)));
-  S_TRY(dtd.alloc(F * sizeof(double2)));
-  S_TRY(dfd2.alloc(F * sizeof(double2)));
-  S_TRY(hipMemcpy(dz.p, in_sc_iq, S * sizeof(double2), hipMemcpyHostToDevice));
-  S_TRY(hipMemset(dd.p, 0, S * sizeof(double2)));
+  MIMO_HIP_TRY(dz.alloc(S * sizeof(double2)));
+  MIMO_HIP_TRY(dd.alloc(S * sizeof(double2)));
+  MIMO_HIP_TRY(dv.alloc(S * sizeof(double2)));
+  MIMO_HIP_TRY(dlab.alloc(S * sizeof(int32_t)));
+  MIMO_HIP_TRY(dsym.alloc(S * sizeof(double2)));
+  MIMO_HIP_TRY(dfd.alloc(F * sizeof(double2)));
+  MIMO_HIP_TRY(dtd.alloc(F * sizeof(double2)));
+  MIMO_HIP_TRY(dfd2.alloc(F * sizeof(double2)));
+  MIMO_HIP_TRY(hipMemcpy(dz.p, in_sc_iq, S * sizeof(double2), hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(hipMemset(dd.p, 0, S * sizeof(double2)));
   int out_i = 0;
   for (int it = 0; it <= max_it; ++it) {
     hipLaunchKernelGGL(k_sub, grid_for(S), dim3(256), 0, 0, (int64_t)S, dz.as<double2>(), dd.as<double2>(), dv.as<double2>());
     hipLaunchKernelGGL(k_qam_slice, grid_for(S), dim3(256), 0, 0, L, hb, dv.as<double2>(), (int64_t)S, dlab.as<int32_t>());
-    S_TRY(hipGetLastError());
+    MIMO_HIP_TRY(hipGetLastError());
     if (out_i < n_iters && iters[out_i] == it) {
       if (labels_out)
-        S_TRY(hipMemcpy(labels_out + (size_t)out_i * S, dlab.p, S * sizeof(int32_t), hipMemcpyDeviceToHost));
+        MIMO_HIP_TRY(hipMemcpy(labels_out + (size_t)out_i * S, dlab.p, S * sizeof(int32_t), hipMemcpyDeviceToHost));
       if (corrected_iq_out)
-        S_TRY(hipMemcpy(corrected_iq_out + (size_t)out_i * 2 * S, dv.p, S * sizeof(double2), hipMemcpyDeviceToHost));
+        MIMO_HIP_TRY(hipMemcpy(corrected_iq_out + (size_t)out_i * 2 * S, dv.p, S * sizeof(double2),
+                               hipMemcpyDeviceToHost));
       ++out_i;
     }
     if (it == max_it) break;
@@ -564,16 +529,16 @@ int32_t mimo_cnc_receive_ex(int32_t M, int32_t F, int32_t S, int32_t pa_kind, do
     hipLaunchKernelGGL(k_from_bins, grid_for(S), dim3(256), 0, 0, F, S, (int64_t)1, dfd2.as<double2>(), dv.as<double2>());
     hipLaunchKernelGGL(k_cnc_update, grid_for(S), dim3(256), 0, 0, S, L, hb, 1.0 / alpha, dv.as<double2>(),
                        dlab.as<int32_t>(), dd.as<double2>());
-    S_TRY(hipGetLastError());
+    MIMO_HIP_TRY(hipGetLastError());
   }
-  S_TRY(hipDeviceSynchronize());
+  MIMO_HIP_TRY(hipDeviceSynchronize());
   return MIMO_OK;
 }
 
 int32_t mimo_cnc_receive(int32_t M, int32_t F, int32_t S, int32_t pa_kind, double sat, double p, double toi,
                          double alpha, const int32_t* iters, int32_t n_iters, const double* in_sc_iq,
                          int32_t* labels_out) {
-  if (!labels_out) return sfail(MIMO_EINVAL, "null labels_out");
+  if (!labels_out) return fail(MIMO_EINVAL, "null labels_out");
   return mimo_cnc_receive_ex(M, F, S, pa_kind, sat, p, toi, alpha, iters, n_iters, in_sc_iq, labels_out, nullptr);
 }
 

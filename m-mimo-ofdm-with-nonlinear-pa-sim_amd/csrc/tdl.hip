@@ -10,11 +10,10 @@
 #include <cmath>
 #include <cstring>
 
+#include "host_util.h"
 #include "philox.h"
 
 namespace mimo {
-void set_error(const std::string& m);  // engine.hip: one thread-local message for mimo_last_error()
-
 namespace {
 
 constexpr int kTdlThreads = 256;
@@ -180,67 +179,47 @@ hipError_t launch_tdl(hipStream_t st, const TdlHost& prof, const double* blob, c
 
 }  // namespace mimo
 
-namespace {
-
-int tfail(int code, const std::string& m) {
-  mimo::set_error(m);
-  return code;
-}
-
-struct TBuf {  // a device allocation of the seam's, released with the call
-  void* p = nullptr;
-  ~TBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
-
-#define T_TRY(expr)                                                                                \
-  do {                                                                                             \
-    hipError_t _e = (expr);                                                                        \
-    if (_e != hipSuccess) return tfail(MIMO_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
-}  // namespace
+using mimo::fail;
 
 extern "C" int32_t mimo_tdl_channels(const mimo_tdl* prof, int32_t n_ant, int32_t n_fft, uint64_t seed,
                                      uint64_t first_trial, int64_t n, double* h_out, double* taps_out) {
   if (n_fft < 2 || n_fft > 8192 || (n_fft & (n_fft - 1)))
-    return tfail(MIMO_EINVAL, "n_fft must be a power of two in [2, 8192]");
-  if (n_ant < 1 || n_ant > 4096) return tfail(MIMO_EINVAL, "n_ant must be in [1, 4096]");
-  if (n < 0) return tfail(MIMO_EINVAL, "n must be >= 0");
+    return fail(MIMO_EINVAL, "n_fft must be a power of two in [2, 8192]");
+  if (n_ant < 1 || n_ant > 4096) return fail(MIMO_EINVAL, "n_ant must be in [1, 4096]");
+  if (n < 0) return fail(MIMO_EINVAL, "n must be >= 0");
   mimo::TdlHost host;
   std::string err;
-  if (!mimo::tdl_prepare(prof, n_ant, n_fft, &host, &err)) return tfail(MIMO_EINVAL, err);
+  if (!mimo::tdl_prepare(prof, n_ant, n_fft, &host, &err)) return fail(MIMO_EINVAL, err);
   if (n == 0) return MIMO_OK;
-  if (!h_out) return tfail(MIMO_EINVAL, "null h_out");
+  if (!h_out) return fail(MIMO_EINVAL, "null h_out");
   const std::vector<double> blob = host.blob();
   const size_t per_trial = (size_t)n_ant * (size_t)n_fft, L = (size_t)host.n_taps;
   // trials of one launch: at most 256 MiB of responses
   const int64_t chunk = std::max<int64_t>(1, (int64_t)((256u << 20) / (per_trial * sizeof(double2))));
   const int64_t nb_max = std::min(n, chunk);
-  TBuf d_blob, d_seg, d_h, d_taps;
-  T_TRY(hipMalloc(&d_blob.p, blob.size() * sizeof(double)));
-  T_TRY(hipMalloc(&d_seg.p, sizeof(mimo::TdlSeg) + 2 * sizeof(uint32_t)));
-  T_TRY(hipMalloc(&d_h.p, (size_t)nb_max * per_trial * sizeof(double2)));
-  if (taps_out) T_TRY(hipMalloc(&d_taps.p, (size_t)nb_max * n_ant * L * sizeof(double2)));
-  T_TRY(hipMemcpy(d_blob.p, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice));
+  mimo::DBuf d_blob, d_seg, d_h, d_taps;  // the seam's device allocations, released with the call
+  MIMO_HIP_TRY(hipMalloc(&d_blob.p, blob.size() * sizeof(double)));
+  MIMO_HIP_TRY(hipMalloc(&d_seg.p, sizeof(mimo::TdlSeg) + 2 * sizeof(uint32_t)));
+  MIMO_HIP_TRY(hipMalloc(&d_h.p, (size_t)nb_max * per_trial * sizeof(double2)));
+  if (taps_out) MIMO_HIP_TRY(hipMalloc(&d_taps.p, (size_t)nb_max * n_ant * L * sizeof(double2)));
+  MIMO_HIP_TRY(hipMemcpy(d_blob.p, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice));
   for (int64_t done = 0; done < n; done += chunk) {
     const int64_t nb = std::min(chunk, n - done);
     struct {
       mimo::TdlSeg seg;
       uint32_t start[2];
     } tab{{seed, first_trial + (uint64_t)done}, {0u, (uint32_t)nb}};
-    T_TRY(hipMemcpy(d_seg.p, &tab, sizeof tab, hipMemcpyHostToDevice));
+    MIMO_HIP_TRY(hipMemcpy(d_seg.p, &tab, sizeof tab, hipMemcpyHostToDevice));
     const char* seg_base = static_cast<const char*>(d_seg.p);
-    T_TRY(mimo::launch_tdl(nullptr, host, static_cast<const double*>(d_blob.p),
-                           reinterpret_cast<const mimo::TdlSeg*>(seg_base),
-                           reinterpret_cast<const uint32_t*>(seg_base + sizeof(mimo::TdlSeg)), 1, (uint32_t)nb, 0,
-                           static_cast<double2*>(d_h.p), nullptr, static_cast<double2*>(d_taps.p)));
-    T_TRY(hipMemcpy(h_out + (size_t)done * per_trial * 2, d_h.p, (size_t)nb * per_trial * sizeof(double2),
-                    hipMemcpyDeviceToHost));
+    MIMO_HIP_TRY(mimo::launch_tdl(nullptr, host, static_cast<const double*>(d_blob.p),
+                                  reinterpret_cast<const mimo::TdlSeg*>(seg_base),
+                                  reinterpret_cast<const uint32_t*>(seg_base + sizeof(mimo::TdlSeg)), 1, (uint32_t)nb,
+                                  0, static_cast<double2*>(d_h.p), nullptr, static_cast<double2*>(d_taps.p)));
+    MIMO_HIP_TRY(hipMemcpy(h_out + (size_t)done * per_trial * 2, d_h.p, (size_t)nb * per_trial * sizeof(double2),
+                           hipMemcpyDeviceToHost));
     if (taps_out)
-      T_TRY(hipMemcpy(taps_out + (size_t)done * n_ant * L * 2, d_taps.p, (size_t)nb * n_ant * L * sizeof(double2),
-                      hipMemcpyDeviceToHost));
+      MIMO_HIP_TRY(hipMemcpy(taps_out + (size_t)done * n_ant * L * 2, d_taps.p,
+                             (size_t)nb * n_ant * L * sizeof(double2), hipMemcpyDeviceToHost));
   }
   return MIMO_OK;
 }

@@ -1,7 +1,7 @@
 // Defines launch_trial<F, R, MODE> (trial_launch.h), and with it instantiates the fused trial kernel,
 // for one FFT size, arithmetic type and run mode: compiled once per -DINST_F=<size> -DINST_F64=<0|1>,
 // and once more per size with -DINST_F64=1 -DINST_MODE=<1 measure | 2 spectrum | 3 beam | 4 envelope |
-// 5 soft | 6 coded> (trial_kernel.h MIMO_MODE_*; 0, plain, by default).
+// 5 soft | 6 coded> (trial_params.h MIMO_MODE_*; 0, plain, by default).
 #include <type_traits>
 
 #ifndef INST_F
@@ -17,6 +17,7 @@
 #error "the measure, spectrum, beam, envelope, soft and coded instances are float64 only"
 #endif
 
+#include "trial_kernel.h"
 #include "trial_launch.h"
 
 namespace mimo {

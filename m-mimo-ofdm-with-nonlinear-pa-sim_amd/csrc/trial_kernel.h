@@ -38,841 +38,32 @@
 #include "team_fft.h"
 #include "wave_fft.h"
 #include "split_fft.h"
+// The kernel's contract and components.  Keep the order: out-of-line device functions (pa.h
+// pa_rapp_general) are emitted in the order of their definitions, and tools/isa_identity.py
+// compares builds line for line.
+#include "trial_params.h"
+#include "slots.h"
+#include "team_sum.h"
+#include "pa.h"
+#include "qam.h"
+#include "channel.h"
 
 namespace mimo {
 
-enum PaKind : int { PA_NONE = 0, PA_SOFTLIM = 1, PA_RAPP = 2, PA_TOI = 3 };
-enum ChanKind : int { CH_RAYLEIGH = 1, CH_LOS = 2, CH_TWOPATH = 3, CH_TABLE = 4 };
-enum RxKind : int { RX_CNC = 1, RX_MCNC = 2 };
-
-// The run mode of an instance: trial_kernel's first template argument (macros, since the Makefile
-// hands one to each trial_inst.hip object as -DINST_MODE=<mode>).  The six row modes are float64 only.
-#define MIMO_MODE_PLAIN 0  // the counts alone
-#define MIMO_MODE_MEAS 1
-#define MIMO_MODE_SPEC 2
-#define MIMO_MODE_BEAM 3
-#define MIMO_MODE_ENV 4
-#define MIMO_MODE_SOFT 5
-#define MIMO_MODE_CODED 6
-
-// What a mode's kernel takes behind TrialParams, each argument with its true type: the buffer its
-// instances fill (kModeOut; the sections below have the layouts) and the mode's scale (kModeScale).
-// (A tuple, since the kernel takes its members as arguments of their own: one struct of the two
-// would be passed by reference and read at the kernel's entry, and an empty stand-in would move the
-// implicit arguments.)  TrialParams itself stays the stride of the per-point table, and its layout is
-// tuned (see csi_seed).
-template <int MODE>
-using ModeArgs = std::conditional_t<
-    MODE == MIMO_MODE_PLAIN, std::tuple<>,                                                // nothing
-    std::conditional_t<MODE == MIMO_MODE_CODED, std::tuple<int8_t*, double>,              // channel values, 32 / rho_max
-                       std::conditional_t<MODE == MIMO_MODE_ENV || MODE == MIMO_MODE_SOFT,
-                                          std::tuple<double*, double>,                    // rows, the bin scale
-                                          std::tuple<double*>>>>;                         // measure, spectrum: rows; beam: cells
-constexpr int kModeOut = 0, kModeScale = 1;
-
-// Measure instances (MIMO_MODE_MEAS): the same trial, the same
-// counts, and per trial a row of kMeasFixed + n_idx power sums over the valid in-band slots
-// (include/mimo_engine.h mimo_engine_measure_points: Es, Ez0, Re C, Im C, Ed0, then Ee_i per
-// counter index).  The row pointer is an argument of those instances alone (ModeArgs), and the plain
-// instances compile to the code they had (profiles/r08/measure/isa_diff.txt).
-constexpr int kMeasFixed = 5;  // MIMO_MEAS_FIXED
-
-// Spectrum instances (MIMO_MODE_SPEC): the same trial, the same
-// counts, and per trial a row of F + kSpecFixed doubles from the main array pass alone
-// (include/mimo_engine.h mimo_engine_spectrum_points): psd[k] = sum_a |Y_a[k]|^2 for every FFT
-// bin k (numpy.fft order, ortho transform pair), then Ex = sum_a sum_band |X_a|^2 and Re / Im of
-// C = sum_a sum_band Y_a conj(X_a).  After the forward transform register m of frequency thread
-// tf holds bin tf + T m in every FFT kind (plain and wave-split teams: tf = t; the F 8192 split
-// FFT: tf = 2 vt + g, so bin 2 (vt + 256 m) + g -- csrc/probe.hip writes its outputs by the same
-// statement).  psd accumulator: a read-modify-write of the thread's own P cells of the trial's
-// row once per antenna (antenna 0 stores), in antenna order, no atomics and no synchronisation;
-// the rows of the teams in flight stay L2-resident.  (One form for all sizes: from F 256 up the
-// instances sit at their register cap with scratch already -- 168 VGPRs up to F 2048, 256 from
-// F 4096 -- so P more f64 registers would spill to the same memory.)  As for the measure
-// instances the row pointer is an extra argument of those instances alone.
-constexpr int kSpecFixed = 3;  // MIMO_SPEC_FIXED
-
-// Beam instances (MIMO_MODE_BEAM): the same trial, the same
-// counts, and the main array pass hands every antenna's chain to the beamforming kernel
-// (beam.hip; include/mimo_engine.h mimo_engine_beam_points) through a per-launch buffer of
-// complex128 cells: [grid.x][A][F] of the chain output's registers d (Y_a = d / sqrt(F)), then
-// [grid.x][A][F] of the precoder input where Slots::scatter placed it (X_a = d sqrt(F), 0 off
-// band).  Register m of frequency thread tf is bin tf + T m before the inverse and after the
-// forward transform (the spectrum instances' statement).  Plain 16-byte stores, every cell
-// written once per launch; the buffer pointer is an extra argument of those instances alone.
-
-// Envelope instances (MIMO_MODE_ENV): the same trial, the same
-// counts, and per trial a row of 2 kEnvBins + kEnvFixed doubles from the main array pass alone
-// (include/mimo_engine.h mimo_engine_envelope_points): the histograms of |x_a[n]|^2 and |y_a[n]|^2
-// over every antenna's F time samples -- d between the inverse transform and pa_block is x_a (the
-// precoder input carries 1 / sqrt(F), so the unnormalised inverse is the ortho one), d after it
-// y_a -- then Pin = sum |x|^2, Pout = sum |y|^2 and Re / Im of sum y conj(x).  Bins (env_bin):
-// eight linear sub-bins per octave read off the bits of pw scale.  Counters: uint32 in a per-team
-// LDS histogram, zeroed before the pass, one ds_add_u32 per sample and side, stored to the row as
-// doubles once after the pass (plain stores, no global atomics).  MIMO_ENV_SUBH (tuning.h) copies of
-// the histogram, one per lane residue, spread the lanes that meet in the few bins around the mean.
-// x is held across pa_block in a copy of d (4 P VGPRs; the instances up to F 2048 are therefore
-// built for 2 waves / SIMD, tuning.h MIMO_ENV_W64_2048: at the plain instances' 168 VGPRs the copy
-// spills and costs more than the resident team).  The row pointer and the bin scale are extra
-// arguments of those instances alone.
-constexpr int kEnvBins = 128;   // MIMO_ENV_BINS
-constexpr int kEnvFixed = 4;    // MIMO_ENV_FIXED
-// bin of a sample power: clamp((bits(pw scale) >> 49) - 8088, 0, 127), 8088 = (1023 - 12) << 3
-// (pw scale >= 0: bits >> 49 is the high word >> 17; 0 lands in bin 0, +inf in bin 127)
-__device__ __forceinline__ int env_bin(double pw, double scale) {
-  const int b = (__double2hiint(pw * scale) >> 17) - 8088;
-  return b < 0 ? 0 : (b > kEnvBins - 1 ? kEnvBins - 1 : b);
-}
-
-// Soft instances (MIMO_MODE_SOFT): the same trial, the same
-// counts, and per trial a row of n_idx kSoftBins doubles (include/mimo_engine.h
-// mimo_engine_soft_points): for every counter index the histogram of the 2 hb bit reliabilities of
-// every valid slot, taken on the value that index slices -- the clean run's z_c, an iteration's
-// z - dist -- by softbits.h soft_axis / soft_bin (max-log soft bit of each Gray bit of each axis,
-// signed by the transmitted bit, 256 linear bins over +-rho_max).  Only where the index is recorded
-// (a uniform branch): one ds_add_u32 per reliability into a per-team LDS histogram of kSoftBins
-// uint32 (1 KiB), which the team stores as doubles to row[idx kSoftBins + ...] after `record` and
-// zeroes again (plain stores, every cell written once, no global atomics).  All of it sits in the
-// receiver phase, outside the antenna loop.  The row pointer and the bin scale 128 / rho_max are
-// extra arguments of those instances alone.
-
-// Coded instances (MIMO_MODE_CODED): the same trial, the same counts, and per trial and recorded
-// counter index the quantised reliability c (softbits.h coded_value: an odd integer in [-63, 63],
-// include/mimo_engine.h mimo_engine_coded_points) of every Gray bit of every valid slot, taken on the
-// value that index slices, as one int8 at chan[(block n_idx + idx) S 2 hb + j S + k]: bit j of
-// sub-carrier k, the I axis MSB first, then Q.  Plain byte stores from the receiver phase, every cell
-// written once, no LDS and no barrier on top of the plain instance's.  The LDPC decoder (ldpc.hip)
-// reads the buffer after the launch.  The buffer and the scale 32 / rho_max are extra arguments of
-// those instances alone.
-
-constexpr int kMaxCsiAnt = 512;  // CSI-error runs: antennas (dynamic LDS per team, A doubles; engine.hip checks)
-constexpr uint32_t kFixedCsiTrial = 0xFFFFFFFFu;  // CSI stream counter of fixed-channel runs (oracle/sim.py draws)
-// The measured alternatives of the choices below (channel pipeline on / off per precision,
-// register diet from F 8192, raw-word pipeline, alpha by library exp / erfc, shfl vs DPP
-// sums) are in DESIGN.md §3 and profiles/r02/ab/; the losing variants were removed.
-
-template <typename R>
-struct TrialParams {
-  using C = cx<R>;
-  uint64_t seed;
-  uint64_t first_trial;
-  uint32_t* counts;              // [n_trials][n_idx]
-  const C* tw;                   // team-FFT stage twiddles of (F, T) (team_fft.h fft_tw_off)
-  const C* tw_wave;              // wave-split FFT twiddles of (F, T) (wave_fft.h), or null
-  const R* ant_rel;              // [A]  d0 / d_a      (Rayleigh FSPL, relative)
-  const R* f_rel;                // [S]  fc / f_k      (f_k float32-quantised as in the reference)
-  const double* f_over_c;        // [S]  f_k / c       (LoS / two-path phases)
-  const double* tx_pos;          // [A*3]
-  const double2* lut;            // [kLut64] fp64 ln / sincos tables (real.h; fp64 instances only)
-  const C* chan_tab;             // CH_TABLE: in-band channels [entries][A][S] (sub-carrier order k), see chan_period
-  int n_ant, n_sc, qam_l, half_bits;
-  uint32_t label_mask;
-  int pa_kind, cnc_pa_kind;
-  R sat_tx, sqrt_sat_tx, inv_sat_tx, rapp_p, toi_tx;
-  R sat_cnc, sqrt_sat_cnc, inv_sat_cnc, toi_cnc, inv_alpha_cnc;
-  R alpha_c;                     // 10^(IBO/10) S / A : gamma_a^2 = alpha_c / vk_pow[a]
-  // alpha(gamma_a^2) as a degree-8 polynomial in x = vk_pow[a] A / S - 1 on |x| <= alpha_xlim
-  // (host Chebyshev fit, ~1e-7 relative); the exact formula outside (engine.hip fit_alpha).
-  // fp32 instances only: the fp64 instances always evaluate the exact formula.
-  R apoly[9];
-  R inv_vk0, alpha_xlim;
-  R inv_vk0_f;                   // inv_vk0 F (the fp64 register-diet array pass sums vk / F)
-  // fp64 instances: alpha(gamma_a^2) as a degree-18 polynomial in x on |x| <= alpha_xlim
-  // (the host's Chebyshev interpolant at 64 nodes in long double, as monomials: Horner,
-  // <= 1.6e-16 relative; the singularity of alpha(g0^2 / (1 + x)) at x = -1 is 4
-  // half-widths away), the exact formula outside.
-  double amono64[19];
-  R es_over_snr;                 // Es / 10^(SNR/10)
-  R csi_a, csi_b;                // sqrt(1 - eps^2), eps
-  R inv_sqrt_f;
-  int receiver;
-  int max_iter;                  // largest iteration index to run (CNC / MCNC)
-  uint32_t rec_mask;             // bit i: record iteration i
-  int incl_clean, n_idx;
-  double rx_x0, rx_z, rx_var, d0; // LoS / two-path geometry
-  uint32_t ablate;               // diagnostic builds only (-DMIMO_ABLATION), see ABL_* below
-  // Multi-point launches (mimo_engine_run_points): the kernel argument carries the table;
-  // block b runs trial points[i].first_trial + b - point_start[i] of point i, where
-  // point_start[i] <= b < point_start[i + 1].  The per-point parameters (PA, AGC, noise,
-  // seed ...) are read from points[i] through the constant address space (scalar loads).
-  const TrialParams* points;     // [n_points] (device)
-  const uint32_t* point_start;   // [n_points + 1] block offsets (device)
-  int n_points;
-  uint32_t chan_period;          // 0, or the channel-replay period (mimo_config.chan_replay_period);
-                                 // CH_TABLE: the entries of chan_tab (trial i reads entry i mod
-                                 // chan_period), or 0: one entry per block of the launch
-  // Last, so that the fields the antenna loop reloads keep their 16-byte alignment (the
-  // scalar loads pair them as s_load_dwordx4; inserted after `seed` it cost the F 4096
-  // instance 1 %, profiles/r04/misc/).
-  uint64_t csi_seed;             // CH_TABLE + CSI: key of the one shared estimate (mimo_config.csi_seed)
-};
-
-// Ablation switches for cost breakdowns.  Compiled in only with -DMIMO_ABLATION
-// (libmimo_engine_ablation.so); the production kernel has none of these branches.
-enum : uint32_t { ABL_RNG = 1, ABL_FFT = 2, ABL_PASS1 = 4, ABL_PA = 8, ABL_XCHG = 16 };
 // ISA inspection only (tools/stage_hist.py): a comment in the assembly naming the loop.
 #ifdef MIMO_ISA_MARKERS
 #define MIMO_ISA_MARK(name) asm volatile("; MIMO_MARK " name)
 #else
 #define MIMO_ISA_MARK(name) ((void)0)
 #endif
-#ifdef MIMO_ABLATION
-#define MIMO_ABL(p, bit) (((p).ablate & (bit)) != 0)
-#elif defined(MIMO_STATIC_ABLATE)  // ISA inspection only (tools/stage_hist.py): stages compiled out
-#define MIMO_ABL(p, bit) ((MIMO_STATIC_ABLATE & (bit)) != 0)
-#else
-#define MIMO_ABL(p, bit) false
-#endif
 
-// ---------------------------------------------------------------- slot geometry
-// ALIGNED: S % (4T) == 0 and S < F.  Slot s < HALF is the positive band (bin
-// n = t + T s, k = n + S/2 - 1; thread 0 slot 0 is bin S/2 instead of DC); slot s >= HALF
-// is the negative band (bin F - S/2 + t + T (s - HALF), k = t + T (s - HALF)).
-// Generic: slot s = register s, valid iff its bin is in band.
-template <int F, int T, int NSLOT, bool ALIGNED>
-struct Slots {
-  static constexpr int P = F / T;
-  static constexpr int HALF = NSLOT / 2;
-  static constexpr int m_of(int s) { return ALIGNED ? (s < HALF ? s : P - NSLOT + s) : s; }
-  // Registers the scatter leaves zero in every thread: the out-of-band middle
-  // (HALF + 1 .. P - HALF - 1; register HALF holds thread 0's bin S/2).  Generic: none.
-  static constexpr uint32_t zero_mask() {
-    uint32_t m = 0;
-    if (ALIGNED)
-      for (int r = HALF + 1; r < P - HALF; ++r) m |= 1u << r;
-    return m;
-  }
-
-  static __device__ __forceinline__ int k_of(int s, int t, int S, bool& valid) {
-    if constexpr (ALIGNED) {
-      valid = true;
-      if (s < HALF) {
-        const int n = (s == 0 && t == 0) ? (S >> 1) : t + T * s;
-        return n + (S >> 1) - 1;
-      }
-      return t + T * (s - HALF);
-    } else {
-      const int n = t + T * s;
-      const int lo = F - (S >> 1);
-      valid = (n >= 1 && n <= (S >> 1)) || n >= lo;
-      return !valid ? 0 : (n >= lo ? n - lo : n + (S >> 1) - 1);  // 0 keeps table reads in bounds
-    }
-  }
-
-  template <class C>
-  static __device__ __forceinline__ void scatter(C (&d)[P], const C (&x)[NSLOT], bool t0) {
-    using R = real_of<C>;
-#pragma unroll
-    for (int m = 0; m < P; ++m) d[m] = czero<R>();
-#pragma unroll
-    for (int s = 0; s < NSLOT; ++s) {
-      if constexpr (ALIGNED) {
-        if (s == 0) {
-          // thread 0's slot 0 is bin S/2 (register HALF), the others' bin t (register 0):
-          // two multiplies by 0 / 1 per component instead of four 32-bit selects
-          const R m1 = t0 ? R(1) : R(0), m0 = R(1) - m1;
-          d[0] = cscale(x[0], m0);
-          d[HALF] = cscale(x[0], m1);
-          continue;
-        }
-      }
-      d[m_of(s)] = x[s];
-    }
-  }
-
-  template <class C>
-  static __device__ __forceinline__ C gather(const C (&d)[P], int s, bool t0) {
-    if constexpr (ALIGNED) {
-      if (s == 0) return t0 ? d[HALF] : d[0];
-    }
-    return d[m_of(s)];
-  }
-};
-
-// ---------------------------------------------------------------- small helpers
-// Opaque copy: stops LICM from hoisting thread-invariant derived values (slot->k maps,
-// Philox round-0 products, QAM points, table loads) out of the antenna loop, which
-// would keep dozens of VGPRs live across it and spill.  Re-deriving them is cheap.
-template <typename V>
-__device__ __forceinline__ V opaque(V v) {
-  asm volatile("" : "+v"(v));
-  return v;
+// bin of a sample power (the envelope instances, trial_params.h MIMO_MODE_ENV):
+// clamp((bits(pw scale) >> 49) - 8088, 0, 127), 8088 = (1023 - 12) << 3
+// (pw scale >= 0: bits >> 49 is the high word >> 17; 0 lands in bin 0, +inf in bin 127)
+__device__ __forceinline__ int env_bin(double pw, double scale) {
+  const int b = (__double2hiint(pw * scale) >> 17) - 8088;
+  return b < 0 ? 0 : (b > kEnvBins - 1 ? kEnvBins - 1 : b);
 }
-template <typename R>
-__device__ __forceinline__ R wave_sum(R v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// Wave sum delivered in lane 63 only (other lanes hold partial sums): DPP adds on the
-// VALU instead of the six dependent ds_bpermute round trips of __shfl_xor.  Per row of
-// 16 lanes: pair / quad swaps and the half-row / row mirrors give every lane its row sum;
-// row_bcast:15 then row_bcast:31 fold rows 0-2 into row 3.  (fp64: both halves moved.)
-// mov_dpp leaves the lanes of disabled rows undefined (no zero-initialised "old" operand,
-// one v_mov fewer per step): after the row_bcast:15 step rows 0 and 2 hold garbage, which
-// no later step reads (row_bcast:31 reads lane 31, row 1) and lane 63 never sees.
-template <int CTRL, int ROW_MASK = 0xF>
-__device__ __forceinline__ float dpp_add(float v) {
-  const int s = __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xF, false);
-  return v + __builtin_bit_cast(float, s);
-}
-template <int CTRL, int ROW_MASK = 0xF>
-__device__ __forceinline__ double dpp_add(double v) {
-  const uint64_t u = __builtin_bit_cast(uint64_t, v);
-  const int lo = __builtin_amdgcn_mov_dpp((int)(uint32_t)u, CTRL, ROW_MASK, 0xF, false);
-  const int hi = __builtin_amdgcn_mov_dpp((int)(uint32_t)(u >> 32), CTRL, ROW_MASK, 0xF, false);
-  return v + __builtin_bit_cast(double, ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
-}
-template <typename R>
-__device__ __forceinline__ R wave_sum_lane63(R v) {
-  v = dpp_add<0xB1>(v);        // quad_perm [1,0,3,2]
-  v = dpp_add<0x4E>(v);        // quad_perm [2,3,0,1]
-  v = dpp_add<0x141>(v);       // row_half_mirror
-  v = dpp_add<0x140>(v);       // row_mirror
-  v = dpp_add<0x142, 0xA>(v);  // row_bcast:15 into rows 1 and 3
-  v = dpp_add<0x143, 0xC>(v);  // row_bcast:31 into rows 2 and 3
-  return v;
-}
-
-// Team-wide sum; every thread gets the result.  Two barriers.
-template <int T, typename R>
-__device__ __forceinline__ R team_sum(R v, R* red) {
-  if constexpr (T == 64) {
-    return wave_sum(v);
-  } else {
-    v = wave_sum_lane63(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 63) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    R s = R(0);
-#pragma unroll
-    for (int i = 0; i < T / 64; ++i) s += red[i];
-    return s;
-  }
-}
-
-// Bussgang gain, modulation.py:178-189, from gamma^2.
-__device__ __forceinline__ float alpha_of_gamma2(float g2) {
-  const float g = __builtin_sqrtf(g2);
-  return 1.0f - __expf(-g2) + 0.88622692545275801f * g * erfcf(g);
-}
-__device__ __forceinline__ double alpha_of_gamma2(double g2) {
-  const double g = __builtin_sqrt(g2);
-  return 1.0 - exp(-g2) + 0.88622692545275801 * g * erfc(g);
-}
-
-// PA on one time-domain sample (distortion.py:9-19, 102-113, 202-211).
-// Soft limiter: min(1, sqrt(sat) rsq(pw)) -- the reference's branch |x|^2 > sat, then
-// x sqrt(sat / |x|^2), up to rounding at |x|^2 = sat (fp64: -0.4 % against the branch).
-// fp64 gains stay within 4 units of 2^-52 of the exact formulas (tests/test_gpu_probe_math.py):
-// the soft limiter's rsq by one third-order step (real.h rsq_h1), the general-hardness Rapp
-// gain with both powers on a base in [1, 2] (below).
-template <class C, typename R = real_of<C>>
-__device__ __forceinline__ C pa_apply(int kind, C x, R sat, R sqrt_sat, R inv_sat, R rapp_p, R toi) {
-  const R pw = fmar(x.x, x.x, x.y * x.y);
-  R sc = R(1);
-  if (kind == PA_SOFTLIM) {
-    if constexpr (sizeof(R) == 4) sc = minr(1.0f, sqrt_sat * rsq_r(pw));
-    else sc = fmin(R(1), sqrt_sat * rsq_h1(pw));  // rsq(0) = inf -> NaN -> fmin picks 1
-  } else if (kind == PA_RAPP) {
-    // 1 / (1 + (pw/sat)^p)^(1/(2p))
-    const R u = pw * inv_sat;
-    if constexpr (sizeof(R) == 8) {
-      // fp64 (cold path): exp2(-(1 / 2p) log2(1 + exp2(p log2 u))) loses ~0.5 |log2 u| ulp to
-      // the rounding of p log2 u and of 1 / 2p (8.8 and 11.6 units of 2^-52 at p = 5 and 2.5,
-      // u up to 10^6).  Above u = 1 the gain is u^(-1/2) (1 + u^-p)^(-1/2p) instead, so the
-      // rounded exponent -1 / 2p only ever meets a base in [1, 2].
-      const bool big = u > R(1);
-      const R v = u > R(0) ? pow(u, big ? -rapp_p : rapp_p) : R(0);
-      const R g = pow(R(1) + v, -(R(0.5) / rapp_p));
-      sc = big ? g / __builtin_sqrt(u) : g;
-    } else {
-      const R up = u > R(0) ? exp2_r(rapp_p * log2_r(u)) : R(0);
-      sc = exp2_r(-(R(0.5) / rapp_p) * log2_r(R(1) + up));
-    }
-  } else if (kind == PA_TOI) {
-    sc = R(1) - toi * pw;
-  }
-  return mkc(x.x * sc, x.y * sc);
-}
-
-// Cold path out of line: the general-hardness Rapp gain (library pow).  Inlined,
-// its f64 constants were hoisted into the loop preheader and spilled to scratch once per
-// trial (~90 KB of writes per trial at config 2, profiles/r03/pmc); out of line they stay
-// in the call.  Measured with the exact-alpha fallback (now alpha_fit.h's segment table,
-// which has no constants to hoist) outlined as well: config 2 -2.5 %, CSI -2.7 %, LoS
-// -2.3 %, two-path -3.0 %, F 8192 -0.4 %; F 4096 +1.6 % (profiles/r03/ab_s/).
-template <class C, typename R = real_of<C>>
-__device__ __attribute__((noinline)) C pa_rapp_general(C x, R inv_sat, R rapp_p) {
-  return pa_apply(PA_RAPP, x, R(0), R(0), inv_sat, rapp_p, R(0));
-}
-
-// y^(-1/N) for y >= 1 (the Rapp gain at integer hardness, N = 2p).  fp32: hardware
-// log / exp.  fp64: the fp32 hardware value z as the seed (~2^-22) and one third-order
-// step z (1 - e)^(-1/N) ~ z (1 + e/N + (N+1) e^2 / (2 N^2)), e = 1 - y z^N (error
-// ~2^-60, below the fp64 rounding): 7 f64 ops + 2 fp32 transcendentals instead of the
-// library log2 + exp2 (~60 instructions).
-template <int N>
-__device__ __forceinline__ float rpow_neg_inv(float y) {
-  return __builtin_amdgcn_exp2f((-1.0f / N) * __builtin_amdgcn_logf(y));
-}
-template <int N>
-__device__ __forceinline__ double rpow_neg_inv(double y) {
-  static_assert(N == 4 || N == 6, "integer Rapp hardness 2 or 3");
-  const double z = (double)rpow_neg_inv<N>((float)y);
-  const double z2 = z * z;
-  const double zn = N == 4 ? z2 * z2 : z2 * z2 * z2;
-  const double e = fma(-y, zn, 1.0);
-  const double c = e * fma(e, (N + 1.0) / (2.0 * N * N), 1.0 / N);
-  return fma(z, c, z);
-}
-
-// Rapp with an integer hardness: (pw/sat)^p by multiplication (config 5 uses p = 3), then
-// (1 + (pw/sat)^p)^(-1/(2p)) by rpow_neg_inv.
-template <int IP, int P, class C, typename R = real_of<C>>
-__device__ __forceinline__ void rapp_int(C (&d)[P], R inv_sat) {
-#pragma unroll
-  for (int m = 0; m < P; ++m) {
-    const R u = fmar(d[m].x, d[m].x, d[m].y * d[m].y) * inv_sat;
-    R up = u;
-#pragma unroll
-    for (int i = 1; i < IP; ++i) up *= u;
-    const R sc = rpow_neg_inv<2 * IP>(R(1) + up);
-    d[m] = mkc(d[m].x * sc, d[m].y * sc);
-  }
-}
-
-// PA on all P samples of a thread: one uniform branch on the kind, then a straight loop.
-template <bool COLD_OUT, int P, class C, typename R = real_of<C>>
-__device__ __forceinline__ void pa_block(int kind, C (&d)[P], R sat, R sqrt_sat, R inv_sat, R rapp_p, R toi) {
-#ifdef MIMO_DIAG_PA_SOFTLIM_ONLY  // ISA inspection only (tools/one_inst.hip): no other PA kinds
-  kind = PA_SOFTLIM;
-#endif
-  if (kind == PA_SOFTLIM) {
-#pragma unroll
-    for (int m = 0; m < P; ++m) d[m] = pa_apply(PA_SOFTLIM, d[m], sat, sqrt_sat, inv_sat, rapp_p, toi);
-  } else if (kind == PA_RAPP && rapp_p == R(3)) {
-    rapp_int<3>(d, inv_sat);
-  } else if (kind == PA_RAPP && rapp_p == R(2)) {
-    rapp_int<2>(d, inv_sat);
-  } else if (kind == PA_RAPP) {
-#pragma unroll
-    for (int m = 0; m < P; ++m) {
-      if constexpr (COLD_OUT) d[m] = pa_rapp_general(d[m], inv_sat, rapp_p);
-      else d[m] = pa_apply(PA_RAPP, d[m], sat, sqrt_sat, inv_sat, rapp_p, toi);
-    }
-  } else if (kind == PA_TOI) {
-#pragma unroll
-    for (int m = 0; m < P; ++m) d[m] = pa_apply(PA_TOI, d[m], sat, sqrt_sat, inv_sat, rapp_p, toi);
-  }
-}
-
-// Per-axis hard slicer == argmin |z - C| over the Gray-ordered constellation with the
-// reference's first-index (lowest label) tie-break (modulation.py:75-76,138-146).
-__device__ __forceinline__ uint32_t gray(uint32_t i) { return i ^ (i >> 1); }
-__device__ __forceinline__ uint32_t gray_inv(uint32_t g) {
-  g ^= g >> 1;
-  g ^= g >> 2;
-  g ^= g >> 4;
-  g ^= g >> 8;
-  return g;
-}
-template <typename R>
-__device__ __forceinline__ uint32_t slice_axis(R x, int L) {
-  const R q = (x + (R)L) * R(0.5);
-  const R fi = floor_r(q);
-  int i = (int)fi;
-  if (q == fi && i > 0 && i < L) {  // exact midpoint between levels i-1 and i
-    i = gray((uint32_t)(i - 1)) < gray((uint32_t)i) ? i - 1 : i;
-  }
-  i = i < 0 ? 0 : (i > L - 1 ? L - 1 : i);
-  return gray((uint32_t)i);
-}
-template <class C>
-__device__ __forceinline__ uint32_t slice(C z, int L, int hb) {
-  return (slice_axis(z.x, L) << hb) | slice_axis(z.y, L);
-}
-template <typename R>
-__device__ __forceinline__ cx<R> qam_point(uint32_t label, int L, int hb) {
-  const uint32_t ii = gray_inv(label >> hb), iq = gray_inv(label & ((1u << hb) - 1u));
-  return mkc((R)(2 * (int)ii - (L - 1)), (R)(2 * (int)iq - (L - 1)));
-}
-// The same point as two int16 lattice levels in one word (I high, Q low): the register
-// diet keeps these per slot and rebuilds the point per antenna in 2 shifts + 2 converts
-// instead of the two inverse Gray codes (~20 integer ops).
-__device__ __forceinline__ uint32_t qam_levels(uint32_t label, int L, int hb) {
-  const int ii = 2 * (int)gray_inv(label >> hb) - (L - 1), iq = 2 * (int)gray_inv(label & ((1u << hb) - 1u)) - (L - 1);
-  return ((uint32_t)ii << 16) | ((uint32_t)iq & 0xFFFFu);
-}
-// Two slots per word for the register diet: int8 lattice levels (|level| <= L - 1 <= 63 for
-// M <= 4096), slot 2 i + h in bits 16 h .. 16 h + 15 of word i (I high byte): half the VGPRs
-// of one word per slot, and the same 2 extracts + 2 converts (v_bfe_i32) to rebuild.
-__device__ __forceinline__ uint32_t qam_levels8(uint32_t label, int L, int hb) {
-  const int ii = 2 * (int)gray_inv(label >> hb) - (L - 1), iq = 2 * (int)gray_inv(label & ((1u << hb) - 1u)) - (L - 1);
-  return (((uint32_t)ii & 0xFFu) << 8) | ((uint32_t)iq & 0xFFu);
-}
-template <typename R, int H>
-__device__ __forceinline__ cx<R> levels_point8(uint32_t w) {
-  // sign-extending extracts of bits 16 H + 8 .. + 15 (I) and 16 H .. + 7 (Q)
-  return mkc((R)((int)(w << (16 - 16 * H)) >> 24), (R)((int)(w << (24 - 16 * H)) >> 24));
-}
-template <typename R>
-__device__ __forceinline__ cx<R> levels_point(uint32_t v) {
-  return mkc((R)((int)v >> 16), (R)(int)(int16_t)(v & 0xFFFFu));
-}
-
-// ---------------------------------------------------------------- channel generation
-// sin / cos of a channel phase in revolutions: fp32 hardware (v_sin / v_cos take
-// revolutions), fp64 the table form (real.h sincos_rev_lut).
-__device__ __forceinline__ void sincos_phase(float r, float& sn, float& cs) {
-  sn = sin_rev(r);
-  cs = cos_rev(r);
-}
-__device__ __forceinline__ void sincos_phase(double r, double& sn, double& cs) {
-  sincos_rev_lut(r, sn, cs);
-}
-
-template <typename R, int F, int T, int NSLOT, bool ALIGNED, int CH, bool UNI_EXTRA = false>
-struct Channel {
-  // philox.h UNI rounds (the rounds whose words are uniform across the team on the SALU): the
-  // fp64 wave-split instances (F <= 2048), and UNI_EXTRA (the F 4096 CSI instance, below)
-  static constexpr bool kUni = sizeof(R) == 8 && (wave_fft_used(F, T, true) || UNI_EXTRA);
-  using SL = Slots<F, T, NSLOT, ALIGNED>;
-  using C = cx<R>;
-  using Params = TrialParams<R>;
-
-  // CN(0,1) draws of one stream for the thread's slots (pairs resolved in-thread when aligned).
-  // c = bm_c(scale^2) scales the draws (box_muller).
-  static __device__ __forceinline__ void normals(Key key, uint32_t trial, uint32_t stream, uint32_t aux, int t, int S,
-                                                 C (&z)[NSLOT], R c = bm_c<R>(R(1))) {
-    if constexpr (ALIGNED) {
-      // Pair indices in closed form (pair_of() applied to the aligned slot map):
-      //   positive band, slots j and j + Q: q = S/4 - 1 + t + T j, except thread 0 /
-      //   j = 0 (bins S/2 and S/4): q = S/2 - 1 with the two draws swapped;
-      //   negative band, slots HALF + j and HALF + j + Q: q = t + T j.
-      constexpr int Q = SL::HALF / 2;
-      const bool t0 = (t == 0);
-      const int qp = (S >> 2) - 1 + t;
-#pragma unroll
-      for (int j = 0; j < Q; ++j) {
-        C z1, z2;
-        const bool sw = (j == 0) && t0;
-        cn_pair<kUni>(key, sw ? (uint32_t)((S >> 1) - 1) : (uint32_t)(qp + T * j), trial, stream, aux, z1, z2, c, sw);
-        z[j] = z1;
-        z[j + Q] = z2;
-        cn_pair<kUni>(key, (uint32_t)(t + T * j), trial, stream, aux, z1, z2, c);
-        z[SL::HALF + j] = z1;
-        z[SL::HALF + j + Q] = z2;
-      }
-    } else {
-#pragma unroll
-      for (int s = 0; s < NSLOT; ++s) {
-        bool v;
-        const int k = SL::k_of(s, t, S, v);
-        z[s] = czero<R>();
-        if (v) {
-          uint32_t q;
-          int slot;
-          pair_of(k, S, q, slot);
-          C z1, z2;
-          cn_pair<kUni>(key, q, trial, stream, aux, z1, z2, c);
-          z[s] = slot == 0 ? z1 : z2;
-        }
-      }
-    }
-  }
-
-  // One Philox call's worth of normals() (aligned instances): chunk c = 2 j + band fills
-  // slots (j, j + Q) of the positive band (band 0) or (HALF + j, HALF + j + Q) of the
-  // negative band (band 1).  normals() == all 2 Q chunks.
-  static constexpr int kChunks = ALIGNED ? SL::HALF : 0;
-  static __device__ __forceinline__ void normals_chunk(int c, Key key, uint32_t trial, uint32_t stream, uint32_t aux,
-                                                       int t, int S, C (&z)[NSLOT], R cs) {
-    if constexpr (ALIGNED) {
-      constexpr int Q = SL::HALF / 2;
-      const int j = c >> 1;
-      C z1, z2;
-      if ((c & 1) == 0) {
-        const bool sw = (j == 0) && (t == 0);
-        cn_pair<kUni>(key, sw ? (uint32_t)((S >> 1) - 1) : (uint32_t)((S >> 2) - 1 + t + T * j), trial, stream, aux, z1, z2,
-                cs, sw);
-        z[j] = z1;
-        z[j + Q] = z2;
-      } else {
-        cn_pair<kUni>(key, (uint32_t)(t + T * j), trial, stream, aux, z1, z2, cs);
-        z[SL::HALF + j] = z1;
-        z[SL::HALF + j + Q] = z2;
-      }
-    }
-  }
-
-  // |H|^2 of antenna a at the thread's slots (Rayleigh, FSPL factor f_rel left out as in
-  // gen<false>): the same draws as gen(), magnitudes only.
-  template <class PP>
-  static __device__ __forceinline__ void power(const PP& p, Key key, uint32_t trial, int a, int t,
-                                               R (&e2)[NSLOT]) {
-    const int S = p.n_sc;
-    const R sa = p.ant_rel[a];
-    const R c = bm_c<R>(sa * sa);
-    if constexpr (ALIGNED) {
-      constexpr int Q = SL::HALF / 2;
-      const bool t0 = (t == 0);
-      const int qp = (S >> 2) - 1 + t;
-#pragma unroll
-      for (int j = 0; j < Q; ++j) {
-        R p1, p2;
-        const bool sw = (j == 0) && t0;
-        cn_pair_pow<kUni>(key, sw ? (uint32_t)((S >> 1) - 1) : (uint32_t)(qp + T * j), trial, ST_CHAN, (uint32_t)a, p1, p2,
-                    c, sw);
-        e2[j] = p1;
-        e2[j + Q] = p2;
-        cn_pair_pow<kUni>(key, (uint32_t)(t + T * j), trial, ST_CHAN, (uint32_t)a, p1, p2, c);
-        e2[SL::HALF + j] = p1;
-        e2[SL::HALF + j + Q] = p2;
-      }
-    } else {
-#pragma unroll
-      for (int s = 0; s < NSLOT; ++s) {
-        bool v;
-        const int k = SL::k_of(s, t, S, v);
-        e2[s] = R(0);
-        if (v) {
-          uint32_t q;
-          int slot;
-          pair_of(k, S, q, slot);
-          R p1, p2;
-          cn_pair_pow<kUni>(key, q, trial, ST_CHAN, (uint32_t)a, p1, p2, c);
-          e2[s] = slot == 0 ? p1 : p2;
-        }
-      }
-    }
-  }
-
-  // power() summed over the antennas in place (pass 1 of the aligned fp64 instances, tuning.h
-  // P1_HOIST / P1_SUMS3): acc[.][slot] takes antenna a's term of every slot.
-  // SUMS3: the logs stay in real.h ln_unit_parts' three terms, acc[0..2][s] += c (tab, poly, e)
-  // (ln_sum() assembles them once per trial); else acc[0][s] += c ln u as power() and its caller.
-  // SWAP = false: no pair swap, and q0 is the first call's counter for j = 0, formed by the caller
-  // once per trial (S/2 - 1 for thread 0, else S/4 - 1 + t): thread 0's sums of slots 0 and Q
-  // then sit in each other's place, which the caller puts right once after the loop.
-  // LN_DEG: the degree of the logs' series (real.h ln_unit; tuning.h MIMO_P1_LN_DEG).
-  template <bool SUMS3, bool SWAP, int LN_DEG, class PP>
-  static __device__ __forceinline__ void power_acc(const PP& p, Key key, uint32_t trial, int a, int t, uint32_t q0,
-                                                   R (&acc)[SUMS3 ? 3 : 1][NSLOT]) {
-    static_assert(ALIGNED && sizeof(R) == 8, "aligned fp64 instances");
-    constexpr int Q = SL::HALF / 2;
-    const int S = p.n_sc;
-    const R sa = p.ant_rel[a];
-    const R c = bm_c<R>(sa * sa);
-    const bool t0 = (t == 0);
-    const int qp = (S >> 2) - 1 + t;
-    auto add = [&](int s, uint32_t w0) __attribute__((always_inline)) {
-      if constexpr (SUMS3) {
-        R tab, poly, de;
-        ln_unit_parts<-32, LN_DEG>((double)w0 + 0.5, tab, poly, de);
-        acc[0][s] = fmar(c, tab, acc[0][s]);
-        acc[1][s] = fmar(c, poly, acc[1][s]);
-        acc[2][s] = fmar(c, de, acc[2][s]);
-      } else {
-        acc[0][s] += c * bm_log<LN_DEG>(w0, R(0));
-      }
-    };
-#pragma unroll
-    for (int j = 0; j < Q; ++j) {
-      const bool sw = SWAP && (j == 0) && t0;
-      uint32_t q = (uint32_t)(qp + T * j);
-      if (j == 0) q = SWAP ? (t0 ? (uint32_t)((S >> 1) - 1) : q) : q0;
-      uint4 w = philox4x32_10<kUni>(make_uint4(q, trial, ST_CHAN, (uint32_t)a), key);
-      add(j, sw ? w.z : w.x);
-      add(j + Q, sw ? w.x : w.z);
-      w = philox4x32_10<kUni>(make_uint4((uint32_t)(t + T * j), trial, ST_CHAN, (uint32_t)a), key);
-      add(SL::HALF + j, w.x);
-      add(SL::HALF + j + Q, w.z);
-    }
-  }
-
-  // Polar form of normals() (aligned instances): rho^2 = c ln u1 and the angle word w1 of
-  // every slot's draw (the draw is rho e^{j 2 pi w1 2^-32}, box_muller), no sqrt / sin / cos.
-  // fn(slot, rho^2, angle word) per slot, one Philox call (two slots) at a time.
-  template <class Fn>
-  static __device__ __forceinline__ void polar(Key key, uint32_t trial, uint32_t stream, uint32_t aux, int t, int S, R c,
-                                               const Fn& fn) {
-    static_assert(ALIGNED, "aligned slot map");
-    constexpr int Q = SL::HALF / 2;
-    const bool t0 = (t == 0);
-    const int qp = (S >> 2) - 1 + t;
-#pragma unroll
-    for (int j = 0; j < Q; ++j) {
-      const bool sw = (j == 0) && t0;
-      uint4 w = philox4x32_10<kUni>(make_uint4(sw ? (uint32_t)((S >> 1) - 1) : (uint32_t)(qp + T * j), trial, stream, aux),
-                                    key);
-      fn(j, c * bm_log(sw ? w.z : w.x, R(0)), sw ? w.w : w.y);
-      fn(j + Q, c * bm_log(sw ? w.x : w.z, R(0)), sw ? w.y : w.w);
-      w = philox4x32_10<kUni>(make_uint4((uint32_t)(t + T * j), trial, stream, aux), key);
-      fn(SL::HALF + j, c * bm_log(w.x, R(0)), w.y);
-      fn(SL::HALF + j + Q, c * bm_log(w.z, R(0)), w.w);
-    }
-  }
-
-  // normals() with a per-slot scale folded into the Box-Muller radius: z = (rho w_s) e^{j phi}
-  // and rw = rho w_s (aligned instances) -- one multiply per draw instead of two.
-  // LN_DEG, SIN_DEG: the degrees of the draws' series (real.h ln_unit, sincos_lut; tuning.h
-  // MIMO_BM_LN_DEG, MIMO_BM_SIN_DEG).
-  template <int LN_DEG = 6, int SIN_DEG = 7>
-  static __device__ __forceinline__ void normals_w(Key key, uint32_t trial, uint32_t stream, uint32_t aux, int t, int S,
-                                                   R c, const R (&w)[NSLOT], C (&z)[NSLOT], R (&rw)[NSLOT]) {
-    static_assert(ALIGNED, "aligned slot map");
-    constexpr int Q = SL::HALF / 2;
-    const bool t0 = (t == 0);
-    const int qp = (S >> 2) - 1 + t;
-    auto draw = [&](int s, uint32_t w0, uint32_t w1) __attribute__((always_inline)) {
-      rw[s] = sqrt_n1(c * bm_log<LN_DEG>(w0, R(0))) * w[s];
-      R sn, cs;
-      sincos_lut<SIN_DEG>(w1, sn, cs);
-      z[s] = mkc(rw[s] * cs, rw[s] * sn);
-    };
-#pragma unroll
-    for (int j = 0; j < Q; ++j) {
-      const bool sw = (j == 0) && t0;
-      uint4 u = philox4x32_10<kUni>(make_uint4(sw ? (uint32_t)((S >> 1) - 1) : (uint32_t)(qp + T * j), trial, stream, aux),
-                                    key);
-      draw(j, sw ? u.z : u.x, sw ? u.w : u.y);
-      draw(j + Q, sw ? u.x : u.z, sw ? u.y : u.w);
-      u = philox4x32_10<kUni>(make_uint4((uint32_t)(t + T * j), trial, stream, aux), key);
-      draw(SL::HALF + j, u.x, u.y);
-      draw(SL::HALF + j + Q, u.z, u.w);
-    }
-  }
-
-  // |H|^2 of antenna a at the thread's slots for the closed-form channels (gen<false>'s
-  // magnitudes, for pass 1's MRT norms): LoS |a1 e^{j phi1}|^2 = a1^2 -- no phase at all;
-  // two-path |a1 e^{j phi1} - a2 e^{j phi2}|^2 = (a1 - a2)^2 + 4 a1 a2 sin^2((phi1 - phi2) / 2)
-  // -- one sine of the half path difference instead of two sine / cosine pairs, in the
-  // cancellation-free form: a2 / a1 = d_los / d_sec is within ~1e-3 of 1 for the reference's
-  // geometry, so at a reflection null (aligned across a ULA) the true value sits near
-  // (a1 - a2)^2 ~ 1e-7 a1^2, below the rounding of a1^2 + a2^2 - 2 a1 a2 cos in fp32.  The
-  // difference a1 - a2 is formed in fp64 and the half phase reduced to [-1/4, 1/4] rev first.
-  template <class PP>
-  static __device__ __forceinline__ void power_closed(const PP& p, int a, int t, const double (&rx)[3],
-                                                      R (&e2)[NSLOT]) {
-    static_assert(CH == CH_LOS || CH == CH_TWOPATH, "closed-form channels");
-    const int S = p.n_sc;
-    const double tx = p.tx_pos[3 * a], ty = p.tx_pos[3 * a + 1], tz = p.tx_pos[3 * a + 2];
-    const double dx = tx - rx[0], dy = ty - rx[1], dz = tz - rx[2];
-    const double d_los = sqrt(dx * dx + dy * dy + dz * dz);
-    const R att_los = (R)(p.d0 / d_los);
-    if constexpr (CH == CH_LOS) {
-#pragma unroll
-      for (int s = 0; s < NSLOT; ++s) {
-        bool v;
-        SL::k_of(s, t, S, v);
-        e2[s] = v ? att_los * att_los : R(0);
-      }
-    } else {
-      const double hz = tz + rx[2];
-      const double d_sec = sqrt(dx * dx + dy * dy + hz * hz);
-      const double g_sec = p.d0 / d_sec;
-      const R d12 = (R)(p.d0 / d_los - g_sec);
-      const R a4 = R(4) * att_los * (R)g_sec;
-      const R d12sq = d12 * d12;
-      const double dd = d_los - d_sec;
-#pragma unroll
-      for (int s = 0; s < NSLOT; ++s) {
-        bool v;
-        const int k = SL::k_of(s, t, S, v);
-        R e = R(0);
-        if (v) {
-          double ph = dd * p.f_over_c[k];
-          ph -= rint(ph);  // [-1/2, 1/2] rev: the half phase keeps its relative precision
-          R sn, cs;
-          sincos_phase((R)(0.5 * ph), sn, cs);
-          e = fmar(a4 * sn, sn, d12sq);
-        }
-        e2[s] = e;
-      }
-    }
-  }
-
-  // True channel of antenna a at the thread's slots (relative scale: common factors
-  // cancel in MRT, AGC and the SNR normalisation).  FREL = false leaves out the
-  // per-sub-carrier FSPL factor fc/f_k, which the kernel then applies once per trial
-  // (it cancels in the MRT precoder; see the kernel's AWGN step).
-  template <bool FREL, class PP>
-  static __device__ __forceinline__ void gen(const PP& p, Key key, uint32_t trial, int a, int t,
-                                             const double (&rx)[3], C (&h)[NSLOT]) {
-    const int S = p.n_sc;
-    if constexpr (CH == CH_RAYLEIGH) {
-      const R sa = p.ant_rel[a];
-      if (MIMO_ABL(p, ABL_RNG)) {
-#pragma unroll
-        for (int s = 0; s < NSLOT; ++s)
-          h[s] = mkc(sa + R(1e-3) * (R)((a + s + t) & 7), R(0.5) - R(1e-3) * (R)((a * s) & 3));
-      } else {
-        normals(key, trial, ST_CHAN, (uint32_t)a, t, S, h, bm_c<R>(sa * sa));  // ant_rel folded in
-      }
-      if constexpr (FREL) {
-#pragma unroll
-        for (int s = 0; s < NSLOT; ++s) {
-          bool v;
-          const int k = SL::k_of(s, t, S, v);
-          h[s] = cscale(h[s], v ? p.f_rel[k] : R(0));
-        }
-      }
-    } else if constexpr (CH == CH_TABLE) {
-      // the caller's channel (Link.simulate reroll_chan=False), entry `trial` of the bank (the
-      // kernel's ch_trial): coalesced loads of the in-band row (f_rel is 1 for table engines:
-      // nothing is factored out).  The bank holds at most 2^27 values: the index fits 32 bits.
-      const size_t row = ((size_t)trial * (size_t)p.n_ant + (size_t)a) * (size_t)S;
-#pragma unroll
-      for (int s = 0; s < NSLOT; ++s) {
-        bool v;
-        const int k = SL::k_of(s, t, S, v);
-        h[s] = v ? p.chan_tab[row + k] : czero<R>();
-      }
-    } else {
-      const double tx = p.tx_pos[3 * a], ty = p.tx_pos[3 * a + 1], tz = p.tx_pos[3 * a + 2];
-      const double dx = tx - rx[0], dy = ty - rx[1], dz = tz - rx[2];
-      const double d_los = sqrt(dx * dx + dy * dy + dz * dz);
-      const R att_los = (R)(p.d0 / d_los);
-      double d_sec = 0.0;
-      R att_sec = R(0);
-      if constexpr (CH == CH_TWOPATH) {
-        // channel.py:138-147: elevation from the mirrored geometry, d_sec = tz/sin(el) +
-        // rz/sin(el) with el = atan((tz + rz) / horiz), i.e. the mirrored path length
-        // sqrt(horiz^2 + (tz + rz)^2) (no fp64 atan / sin; equal to ~1e-16 relative)
-        const double hz = tz + rx[2];
-        d_sec = sqrt(dx * dx + dy * dy + hz * hz);
-        att_sec = (R)(p.d0 / d_sec);
-      }
-#pragma unroll
-      for (int s = 0; s < NSLOT; ++s) {
-        bool v;
-        const int k = SL::k_of(s, t, S, v);
-        C hv = czero<R>();
-        if (v) {
-          const double foc = p.f_over_c[k];
-          const R fr = FREL ? p.f_rel[k] : R(1);
-          double ph = d_los * foc;
-          ph -= floor(ph);
-          const R a1 = att_los * fr;
-          R sn, cs;
-          sincos_phase((R)ph, sn, cs);
-          hv = mkc(a1 * cs, a1 * sn);
-          if constexpr (CH == CH_TWOPATH) {
-            double ph2 = d_sec * foc;
-            ph2 -= floor(ph2);
-            const R a2 = att_sec * fr;
-            sincos_phase((R)ph2, sn, cs);
-            hv.x -= a2 * cs;
-            hv.y -= a2 * sn;
-          }
-        }
-        h[s] = hv;
-      }
-    }
-  }
-};
 
 // ---------------------------------------------------------------- the kernel
 // The instance's FFT.  fp64 up to F 2048 on two or more waves: the wave-split FFT (wave_fft.h).

@@ -2,7 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "trial_kernel.h"
+#include "trial_params.h"
 
 namespace mimo {
 
@@ -34,7 +34,7 @@ struct InstanceKey {
 // The launcher of the instances of one FFT size, arithmetic type and mode (MIMO_MODE_*), defined by
 // the trial_inst.hip object built for them: *found = the key names one of its instances.
 // attr != null: return the instance's attributes (static LDS ...) instead of launching it.
-// m: the kernel's mode arguments (trial_kernel.h ModeArgs).
+// m: the kernel's mode arguments (trial_params.h ModeArgs).
 template <int F, typename R, int MODE>
 hipError_t launch_trial(const InstanceKey& k, dim3 grid, hipStream_t st, const TrialParams<R>& p, bool* found,
                         hipFuncAttributes* attr, const ModeArgs<MODE>& m) = delete;

@@ -77,11 +77,11 @@
 // ---- the series of the Rayleigh channel draws in the fp64 wave-split instances (real.h
 // ln_unit / sincos_lut DEG; every other caller -- noise, CSI, the team-FFT sizes, the probe --
 // keeps the full series).  Bounds: tests/test_draw_series_cpu.py.
-// P1_LN_DEG (6 | 4): log1p's last power in pass 1's weighted log sum (Channel::power_acc).  The
+// P1_LN_DEG (6 | 4): log1p's last power in pass 1's weighted log sum (channel.h power_acc).  The
 // t^5 and t^6 terms are below 2e-16 each where the sum of ~64 has a spacing of 1.4e-14: against
 // the long-double sum 4.14 units of the last place at most with either degree.  -8 VALU per
 // antenna-wave.
-// BM_LN_DEG (6 | 5): the same in the array pass's radius (Channel::normals_w), under sqrt_n1's
+// BM_LN_DEG (6 | 5): the same in the array pass's radius (channel.h normals_w), under sqrt_n1's
 // own 2^-47.8: per draw 1.69 units of the last place at most to t^5, 1.00 to t^6 (t^4: 1,617, so
 // not there).  -4 VALU.
 // BM_SIN_DEG (7 | 5): the sine's last term in normals_w's sincos_lut.  -4 VALU.

@@ -192,7 +192,7 @@ def mcnc_receive(cfg, iters, z, const, p, h_prop, agc_vec, pp, gain):
     return out
 
 
-FIXED_CSI_TRIAL = 0xFFFFFFFF  # CSI stream counter of fixed-channel runs (csrc/trial_kernel.h kFixedCsiTrial)
+FIXED_CSI_TRIAL = 0xFFFFFFFF  # CSI stream counter of fixed-channel runs (csrc/trial_params.h kFixedCsiTrial)
 
 
 def draws(cfg: SimConfig, seed: int, trials):

@@ -1,5 +1,5 @@
 """The float64 primitives of csrc/real.h (table-driven ln / sincos, Newton square roots, the
-integer-hardness Rapp root) and pa_block of csrc/trial_kernel.h on the device, through
+integer-hardness Rapp root) and pa_block of csrc/pa.h on the device, through
 libmimo_probe, against long double -- at the bounds the code comments state:
 
   ln_unit <= 1.3 ulp; sincos_lut, sincos_rev_lut <= 1.5 x 2^-53 absolute (next to a zero of
@@ -198,7 +198,7 @@ def test_pa_block_float64(name, kind, p, cold_out):
     rapp3 1.23, rapp4 1.37, rapp5 1.40, rapp2.5 1.45, toi 1.34.  The first measurement had the
     soft limiter at 17.5 (one Newton step on the v_rsq_f64 seed) and the general-hardness Rapp
     gain at 8.8 (p = 5) and 11.6 (p = 2.5; exp2 / log2 with the rounding of p log2 u): fixed in
-    real.h rsq_h1 and trial_kernel.h pa_apply."""
+    real.h rsq_h1 and pa.h pa_apply."""
     worst = 0.0
     for x, sat, toi in (pa_inputs(0), sat_edge_inputs(0)):
         got = pu.pa(0, cold_out, kind, x, sat, p, toi)

@@ -81,7 +81,9 @@ def test_qam_map_sizes(M, n):
 def test_qam_slice_round_trip_ties_and_clamp(M):
     """Every label's own point; every even-integer lattice point of [-L-2, L+2]^2 (all two- and
     four-way ties of the constellation, and the ring outside it); points far outside, signed
-    zeros and denormals -- against the brute-force argmin with its lowest-label tie-break."""
+    zeros and denormals -- against the brute-force argmin with its lowest-label tie-break.
+    Then +-2^40 and +-1e300 on either axis, where the slicer's floor no longer fits its integer
+    (and the brute force's squared distances overflow): the corner labels, written out by hand."""
     import _engine
     const = rm.gray_qam_constellation(M)
     L = int(np.sqrt(M))
@@ -94,6 +96,15 @@ def test_qam_slice_round_trip_ties_and_clamp(M):
                    1e3, -1e3, 1e6, -1e6, 999999.5, -999999.5])
     edge = (ax[:, None] + 1j * ax[None, :]).reshape(-1)
     assert np.array_equal(_engine.qam_slice(M, edge), rm.detect_labels(const, edge))
+    # An axis label is the Gray code of the level's index: 0 for the lowest level 1 - L, and
+    # gray(L - 1) = L / 2 for the highest, L - 1.  The label is (I's << hb) | Q's.
+    hb, top = L.bit_length() - 1, L // 2
+    for big in (2.0 ** 40, 1e300):
+        far = np.array([big + 1j * big, big - 1j * big, -big + 1j * big, -big - 1j * big,
+                        big + 1j * (1 - L), -big + 1j * (L - 1), (1 - L) + 1j * big, (L - 1) - 1j * big])
+        want = [(top << hb) | top, top << hb, top, 0,
+                top << hb, top, top, top << hb]
+        assert np.array_equal(_engine.qam_slice(M, far), want), big
 
 
 @pytest.mark.parametrize("n", SIZES)

@@ -1,7 +1,7 @@
 """Per-stage VALU opcode classes of the fused kernel's loops, from the ISA.
 
 Compiles one trial_kernel instance (tools/one_inst.hip, -S, soft limiter only) once as is
-and once per stage compiled out (-DMIMO_STATIC_ABLATE=<ABL_* bit>, trial_kernel.h), takes
+and once per stage compiled out (-DMIMO_STATIC_ABLATE=<ABL_* bit>, trial_params.h), takes
 the static instruction mix of the array-pass loop (the loop with the most Philox products)
 and of pass 1, and attributes the differences to the stages:
 
