@@ -11,7 +11,11 @@ CNC iterations 0, 1, 2 and the clean column.  One MCNC case at the bench shape: 
 run the antenna loop without alpha.  One run_points launch of two IBO points: alpha's polynomial
 differs per team.  One measure call at the bench shape within tests/measure_ref.py's bounds:
 alpha's last bits move with the order of its sum, so the rows are held to those bounds and not
-compared bit for bit.
+compared bit for bit.  These are the smallest shapes that reach the changed code, all of them aligned
+Rayleigh: the other float64 instances of the two sizes, which carry the same series cuts and alpha
+wave -- generic bands, LoS, two-path and table channels, CSI, every row mode -- run in
+tests/test_gpu_wave_split_instances.py (the matrix of tests/wave_split_cases.py, on the geometry of
+SHAPES["F1024"]).
 
 One case per switch at its other value (a switch never changes counts): a variant library built by
     make -C csrc variant VOUT=../../abl/lib_<SWITCH>_<value>.so VFLAGS=-D<SWITCH>=<value>

@@ -11,7 +11,10 @@ CNC iterations 0, 1, 2 and the clean column.  One MCNC case at the bench shape: 
 reuse the words held since the main pass.  LoS cases at both sizes: another Channel, the same
 transforms.  (The plain Rayleigh instance of F 1024 is one of those that keep re-deriving, since
 its scratch would grow, csrc/trial_kernel.h xaddr_inst_ok: at F 1024 it is the LoS case that runs
-the held addresses of the two-wave team.)
+the held addresses of the two-wave team.)  These shapes are the smallest that reach the changed code,
+not all the instances it was compiled into: every other float64 instance of the two sizes -- generic
+bands, two-path and table channels, CSI, the six row modes, held or re-deriving -- runs in
+tests/test_gpu_wave_split_instances.py (the matrix of tests/wave_split_cases.py).
 
 Switch parity: for each switch a variant library with it off,
     make -C csrc variant VOUT=../../abl/lib_<SWITCH>_0.so VFLAGS=-D<SWITCH>=0
