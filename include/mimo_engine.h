@@ -23,6 +23,8 @@
  *     mimo_engine_set_channel_bank  a table engine's bank of channel matrices, one per trial (snapshots)
  *     mimo_engine_set_tdl           the power-delay profile of a tapped-delay-line Rayleigh channel, drawn
  *                                   per trial on the device (frequency-selective fading)
+ *     mimo_engine_set_rays          the same engine on a ray-cluster profile: every tap a sum of rays with
+ *                                   caller-given steering vectors (spatially correlated taps, specular rays)
  *     mimo_engine_run_points    <- the drivers' grid loops over (IBO, Eb/N0), one launch
  *                                  for many points   main_mp_miso_cnc_constant_ber_req_ebn0_vs_ibo.py:100-215
  *   fine seams (float64 stage kernels, caller-owned host arrays)
@@ -39,6 +41,7 @@
  *     mimo_combine              <- Miso*Fd.propagate                   channel.py:74-89,277-292
  *     mimo_awgn                 <- Awgn.process                        noise.py:45-83
  *     mimo_tdl_channels            the TDL engine's channel realisations (no reference entry point)
+ *     mimo_rays_channels           ... and those of its ray-cluster profile
  *     mimo_count_bit_errors     <- utilities.count_mismatched_bits     utilities.py:94-104
  *     mimo_cnc_receive          <- CncReceiver.receive                 corrector.py:52-112
  *     mimo_cnc_receive_ex       <- CncReceiver.receive(return_bits=False) corrector.py:80-84
@@ -473,6 +476,51 @@ enum { MIMO_TDL_MAX_TAPS = 64 };
 int32_t mimo_engine_set_tdl(mimo_engine* e, const mimo_tdl* prof);
 int32_t mimo_tdl_channels(const mimo_tdl* prof, int32_t n_ant, int32_t n_fft, uint64_t seed, uint64_t first_trial,
                           int64_t n, double* h_out, double* taps_out);
+/* Ray-cluster channel (MIMO_CH_TDL engines): the TDL channel with every tap a sum of rays, so that
+ * the taps are correlated over the array.  Ray r has a caller-given steering vector steer[.][r]
+ * over the antennas, belongs to tap ray_tap[r], and carries one complex gain per trial that all
+ * antennas share: complex normal (diffuse) or of unit modulus (specular).  Tap l has the transmit
+ * correlation R_l = S_l diag(ray_amp^2) S_l^H over its diffuse rays; one specular ray next to
+ * diffuse ones makes it Rician; a single specular ray is a plane or spherical wave at a delay.
+ *  Gains: ray r < R in trial i under the key seed:
+ *   (w0, w1, ., .) = Philox4x32-10 of counter (r, i mod 2^32, 8, 0)  (stream 8; 7 is the TDL taps'),
+ *   u1 = (w0 + 0.5) 2^-32, u2 = w1 2^-32,
+ *   diffuse:   c_r = ray_amp[r] sqrt(-ln u1) exp(j 2 pi u2)     (the TDL tap's formula)
+ *   specular:  c_r = ray_amp[r] exp(j 2 pi u2);
+ *   the gain does not depend on the antenna.
+ *  Taps: g[a][l] = sum over the rays r of tap l of c_r steer[a][r], each complex product four fused
+ *   multiply-adds onto an accumulator that starts at 0, and the products added in the fixed order
+ *   csrc/tdl.h documents (16 interleaved partial sums in ascending r, then a fixed binary tree); a
+ *   tap of one ray with steer = 1 + 0j is the gain bit for bit.
+ *  Response: H[a][n] = sum_l g[a][l] W[(n delays[l]) mod n_fft], exactly as for mimo_tdl.
+ *  Engine: mimo_engine_set_rays is valid on a MIMO_CH_TDL engine only, copies the profile and makes
+ *   no HIP call (the next run uploads the tables); whichever of mimo_engine_set_tdl and
+ *   mimo_engine_set_rays was called last is the engine's profile.  Everything else about a TDL
+ *   engine holds: the table instances, block b reads entry b, the mimo_bank_capacity split,
+ *   csi_eps >= 0 refused, mimo_engine_last_chan_ms; a float32 engine stores the float64 response
+ *   rounded to nearest.
+ *  MIMO_EINVAL before any HIP call, with a message naming the field: an engine that is not
+ *   MIMO_CH_TDL; a null profile, delays, ray_tap, ray_amp or steer; n_taps outside [1, 64] or n_rays
+ *   outside [n_taps, 1024]; delays that break mimo_tdl's rule; a ray_tap that is not non-decreasing
+ *   from 0 to n_taps - 1 in steps of 0 or 1; a ray_amp that is not finite and > 0; a ray_kind other
+ *   than 0 or 1; a steer value that is not finite (the message names the antenna and the ray).
+ *  mimo_rays_channels is the fine seam, by the engine's own kernel: h_out, taps_out, n_fft, n_ant and
+ *   n as for mimo_tdl_channels; gains_out, optional, is [n][n_rays] complex.
+ * (Added within ABI 8: a library without them is reported by name.) */
+typedef struct mimo_rays {
+  int32_t n_taps;            /* L, 1 ... 64 */
+  const int32_t* delays;     /* [L] as in mimo_tdl */
+  int32_t n_rays;            /* R, L ... 1024 (MIMO_RAYS_MAX) */
+  const int32_t* ray_tap;    /* [R] tap of ray r: non-decreasing, ray_tap[0] = 0, steps of 0 or 1,
+                                ray_tap[R-1] = L-1 (every tap has a ray, a tap's rays are contiguous) */
+  const double* ray_amp;     /* [R] finite and > 0 */
+  const uint8_t* ray_kind;   /* [R] 0 diffuse, 1 specular; NULL = all diffuse */
+  const double* steer;       /* [n_ant][R] complex (re, im), all finite */
+} mimo_rays;
+enum { MIMO_RAYS_MAX = 1024 };
+int32_t mimo_engine_set_rays(mimo_engine* e, const mimo_rays* prof);
+int32_t mimo_rays_channels(const mimo_rays* prof, int32_t n_ant, int32_t n_fft, uint64_t seed, uint64_t first_trial,
+                           int64_t n, double* h_out, double* taps_out, double* gains_out);
 /* Device time of the trial kernels of the last run, in ms (HIP events on the engine stream). */
 double mimo_engine_last_kernel_ms(const mimo_engine* e);
 /* ... and of the beamforming kernels of the last beam call (0 after any other call). */

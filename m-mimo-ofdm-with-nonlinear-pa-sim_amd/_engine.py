@@ -101,6 +101,47 @@ class TdlProfile(ctypes.Structure):
                          ant_amp=self.amp_arr.ctypes.data_as(_dp) if self.amp_arr is not None else None)
 
 
+class RayProfile(ctypes.Structure):
+    """mimo_rays: a ray-cluster profile.  ``RayProfile(delays, ray_tap, ray_amp, steer, ray_kind=None)``:
+    whole-sample tap ``delays``, the tap of every ray (non-decreasing from 0 in steps of 0 or 1),
+    the rays' amplitudes, their steering vectors ``steer`` [n_ant, R] complex and, optionally, their
+    kinds (0 diffuse, 1 specular; None: all diffuse).  The arrays stay with the object; the rules are
+    the library's to check."""
+    _fields_ = [("n_taps", ctypes.c_int32), ("delays", _i32p), ("n_rays", ctypes.c_int32), ("ray_tap", _i32p),
+                ("ray_amp", _dp), ("ray_kind", ctypes.POINTER(ctypes.c_uint8)), ("steer", _dp)]
+
+    def __init__(self, delays, ray_tap, ray_amp, steer, ray_kind=None):
+        d, rt = np.asarray(delays), np.asarray(ray_tap)
+        if d.ndim != 1 or rt.ndim != 1:
+            raise ValueError("delays and ray_tap must be one-dimensional")
+        for name, v in (("delays", d), ("ray_tap", rt)):
+            if v.size and (np.any(v != np.floor(v)) or v.min() < -2 ** 31 or v.max() >= 2 ** 31):
+                raise ValueError(f"{name} must be whole numbers that fit int32")
+        if np.asarray(ray_amp).shape != rt.shape:
+            raise ValueError("ray_amp must hold one amplitude per ray")
+        st = np.asarray(steer)
+        if st.ndim != 2 or st.shape[1] != rt.size:
+            raise ValueError("steer must be [n_ant, n_rays]")
+        self.n_ant = st.shape[0]
+        self.delays_arr = np.ascontiguousarray(d, dtype=np.int32)
+        self.tap_arr = np.ascontiguousarray(rt, dtype=np.int32)
+        self.amp_arr = np.ascontiguousarray(ray_amp, dtype=np.float64)
+        self.steer_arr = np.ascontiguousarray(st, dtype=np.complex128).view(np.float64)
+        self.kind_arr = None
+        if ray_kind is not None:
+            k = np.asarray(ray_kind)
+            if k.shape != rt.shape:
+                raise ValueError("ray_kind must hold one kind per ray")
+            if k.size and (np.any(k != np.floor(k)) or k.min() < 0 or k.max() > 255):
+                raise ValueError("ray_kind must be 0 (diffuse) or 1 (specular)")
+            self.kind_arr = np.ascontiguousarray(k, dtype=np.uint8)
+        super().__init__(n_taps=int(d.size), delays=self.delays_arr.ctypes.data_as(_i32p), n_rays=int(rt.size),
+                         ray_tap=self.tap_arr.ctypes.data_as(_i32p), ray_amp=self.amp_arr.ctypes.data_as(_dp),
+                         ray_kind=(self.kind_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+                                   if self.kind_arr is not None else None),
+                         steer=self.steer_arr.ctypes.data_as(_dp))
+
+
 SYMBOLS = {
     "mimo_abi_version": (ctypes.c_int32, []),
     "mimo_last_error": (ctypes.c_char_p, []),
@@ -144,6 +185,9 @@ SYMBOLS = {
     "mimo_engine_set_tdl": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(TdlProfile)]),
     "mimo_tdl_channels": (ctypes.c_int32, [ctypes.POINTER(TdlProfile), ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
                                            ctypes.c_uint64, ctypes.c_int64, _dp, _dp]),
+    "mimo_engine_set_rays": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(RayProfile)]),
+    "mimo_rays_channels": (ctypes.c_int32, [ctypes.POINTER(RayProfile), ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
+                                            ctypes.c_uint64, ctypes.c_int64, _dp, _dp, _dp]),
     "mimo_engine_last_chan_ms": (ctypes.c_double, [ctypes.c_void_p]),
     "mimo_ldpc_decode": (ctypes.c_int32, [ctypes.POINTER(LdpcCode), _i8p, ctypes.c_int64, _i16p]),
     "mimo_engine_last_kernel_ms": (ctypes.c_double, [ctypes.c_void_p]),
@@ -189,6 +233,7 @@ ENV_WIDTH = 2 * ENV_BINS + ENV_FIXED
 SOFT_BINS = 256  # include/mimo_engine.h MIMO_SOFT_BINS
 CODED_FIXED = 4  # include/mimo_engine.h MIMO_CODED_FIXED
 TDL_MAX_TAPS = 64  # include/mimo_engine.h MIMO_TDL_MAX_TAPS
+RAYS_MAX = 1024    # include/mimo_engine.h MIMO_RAYS_MAX
 
 
 def lib():
@@ -1004,6 +1049,16 @@ class Engine:
         prof = TdlProfile(delays, powers, ant_amp)
         _check(self._L.mimo_engine_set_tdl(self._h, ctypes.byref(prof)))
 
+    def set_rays(self, delays, ray_tap, ray_amp, steer, ray_kind=None):
+        """The ray-cluster profile of a ``channel="tdl"`` engine (mimo_engine_set_rays): tap
+        ``delays``, the tap and amplitude of every ray, ``steer`` [n_ant, R] complex and, optionally,
+        the rays' kinds (0 diffuse, 1 specular).  Copied; it replaces a ``set_tdl`` profile and the
+        other way round."""
+        prof = RayProfile(delays, ray_tap, ray_amp, steer, ray_kind)
+        if prof.n_ant != self.n_ant:
+            raise ValueError("steer must be [n_ant, n_rays]")
+        _check(self._L.mimo_engine_set_rays(self._h, ctypes.byref(prof)))
+
     @property
     def decode_kernel_ms(self):
         """Device time of the decoder kernels of the last coded call (0 after any other call)."""
@@ -1127,6 +1182,24 @@ def tdl_channels(delays, powers, n_ant, n_fft, seed, first_trial, n, ant_amp=Non
                                    int(first_trial) & 0xFFFFFFFFFFFFFFFF, n, _ptr(h.view(np.float64), ctypes.c_double),
                                    _ptr(g.view(np.float64), ctypes.c_double) if taps else None))
     return (h, g) if taps else h
+
+
+def rays_channels(delays, ray_tap, ray_amp, steer, n_fft, seed, first_trial, n, ray_kind=None, taps=False, gains=False):
+    """The realisations of a ray-cluster profile on host arrays (mimo_rays_channels), by the engine's
+    own generator: trials ``first_trial ... first_trial + n - 1`` under the key ``seed``; ``n_ant`` is
+    ``steer``'s first dimension.  -> H [n, n_ant, n_fft] complex (numpy.fft bin order); with
+    ``taps=True`` and / or ``gains=True`` a tuple (H[, taps [n, n_ant, L]][, gains [n, R]])."""
+    prof = RayProfile(delays, ray_tap, ray_amp, steer, ray_kind)
+    n, n_ant = int(n), prof.n_ant
+    h = np.zeros((max(n, 0), n_ant, n_fft), np.complex128)
+    g = np.zeros((max(n, 0), n_ant, prof.n_taps), np.complex128) if taps else None
+    c = np.zeros((max(n, 0), prof.n_rays), np.complex128) if gains else None
+    _check(lib().mimo_rays_channels(ctypes.byref(prof), n_ant, int(n_fft), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                    int(first_trial) & 0xFFFFFFFFFFFFFFFF, n, _ptr(h.view(np.float64), ctypes.c_double),
+                                    _ptr(g.view(np.float64), ctypes.c_double) if taps else None,
+                                    _ptr(c.view(np.float64), ctypes.c_double) if gains else None))
+    out = (h,) + ((g,) if taps else ()) + ((c,) if gains else ())
+    return out if len(out) > 1 else h
 
 
 def fft(x, inverse=False):

@@ -5,7 +5,8 @@ GPU.  Channel matrices are closed-form geometry (LoS / two-path) or PCG64 draws
 (Rayleigh, reference semantics) computed on the host when a caller asks for them; the
 Link hot path does not use them -- it regenerates the per-trial channel on the device.
 QuaDRiGa / random-paths channels need MATLAB or a NumPy-1 API and are out of scope;
-``MisoTdlFd`` is the frequency-selective channel in their place (a tapped-delay-line profile).
+``MisoTdlFd`` is the frequency-selective channel in their place (a tapped-delay-line profile), and
+``MisoRaysFd`` the sum of paths ``MisoRandomPathsFd`` stands for: taps that are sums of rays.
 """
 from __future__ import annotations
 
@@ -13,6 +14,7 @@ import numpy as np
 from numpy import ndarray
 
 import _engine
+import utilities
 
 SPEED_OF_LIGHT = 299792458.0  # scipy.constants.c
 
@@ -198,6 +200,92 @@ class MisoTdlFd:
         self.channel_mat_fd = _engine.tdl_channels(self.delays, self.powers, self.n_inputs, self.fd_samp_size,
                                                    self.seed, self.n_drawn, 1,
                                                    ant_amp=None if skip_attenuation else self.ant_amp)[0]
+        self.n_drawn += 1
+
+    def propagate(self, in_sig_mat: ndarray, sum_signals: bool = True) -> ndarray:
+        return _propagate(self.channel_mat_fd, in_sig_mat, sum_signals)
+
+
+class MisoRaysFd:
+    """Ray-cluster channel: ``MisoTdlFd`` with every tap a sum of rays towards point scatterers, so
+    that the taps are correlated over the array (``include/mimo_engine.h``, mimo_rays) -- what the
+    reference's ``MisoRandomPathsFd`` stands for, with the reference classes' surface.
+
+    Ray ``r`` belongs to tap ``ray_tap[r]`` (non-decreasing from 0 in steps of 0 or 1) at the
+    whole-sample delay ``delays[ray_tap[r]]``, points at ``points[r]`` [R, 3] and has amplitude
+    ``ray_amp[r]``; ``ray_kind[r]`` is 0 for a diffuse ray (a complex-normal gain per realisation) or
+    1 for a specular one (unit modulus, uniform phase).  Its steering vector is
+    ``utilities.scatterer_steering`` at the centre frequency, bin 0 of the carrier grid, times
+    ``MisoTdlFd``'s per-antenna ``ant_amp``; ``skip_attenuation`` leaves that amplitude out.
+    ``utilities.ring_clusters`` makes a stand-in geometry.
+
+    The realisations come from the engine's own generator through the fine seam
+    (``_engine.rays_channels``): realisation ``i`` of this object is trial ``i`` under the key
+    ``seed``.  ``Link.simulate(reroll_chan=True)`` draws its per-trial channels on the device from the
+    same profile under the run's own seeds."""
+
+    def __init__(self, tx_transceivers, rx_transceiver, delays, ray_tap, ray_amp, points, ray_kind=None,
+                 seed: int = None):
+        self.n_inputs = len(tx_transceivers)
+        self.fd_samp_size = tx_transceivers[0].modem.n_fft
+        self.seed = 1234 if seed is None else seed
+        d, rt = np.asarray(delays), np.asarray(ray_tap)
+        amp, pts = np.asarray(ray_amp, dtype=np.float64), np.asarray(points, dtype=np.float64)
+        if d.ndim != 1 or not 1 <= d.size <= _engine.TDL_MAX_TAPS:
+            raise ValueError(f"the profile must have 1 ... {_engine.TDL_MAX_TAPS} taps")
+        if np.any(d != np.floor(d)):
+            raise ValueError("delays must be whole samples")
+        if d[0] < 0 or d[-1] >= self.fd_samp_size or np.any(np.diff(d) <= 0):
+            raise ValueError("delays must be strictly ascending in [0, n_fft)")
+        if rt.ndim != 1 or not d.size <= rt.size <= _engine.RAYS_MAX:
+            raise ValueError(f"the profile must have n_taps ... {_engine.RAYS_MAX} rays")
+        if np.any(rt != np.floor(rt)) or rt[0] != 0 or rt[-1] != d.size - 1 or not np.all(np.isin(np.diff(rt), (0, 1))):
+            raise ValueError("ray_tap must be non-decreasing from 0 to n_taps - 1 in steps of 0 or 1")
+        if amp.shape != rt.shape or not np.all(np.isfinite(amp)) or np.any(amp <= 0):
+            raise ValueError("ray_amp must hold one finite amplitude > 0 per ray")
+        if pts.shape != (rt.size, 3) or not np.all(np.isfinite(pts)):
+            raise ValueError("points must be [n_rays, 3] and finite")
+        if ray_kind is None:
+            kind = np.zeros(rt.size, np.uint8)
+        else:
+            kind = np.asarray(ray_kind)
+            if kind.shape != rt.shape or not np.all(np.isin(kind, (0, 1))):
+                raise ValueError("ray_kind must hold 0 (diffuse) or 1 (specular) per ray")
+        self.delays = d.astype(np.int32)
+        self.ray_tap = rt.astype(np.int32)
+        self.ray_amp = amp
+        self.ray_kind = kind.astype(np.uint8)
+        self.points = pts
+        f = carrier_freqs(rx_transceiver.modem.n_fft, rx_transceiver.carrier_spacing, rx_transceiver.center_freq)
+        tx, _, dist = _distances(tx_transceivers, rx_transceiver)
+        gains = np.asarray([t.tx_ant_gain_db for t in tx_transceivers], dtype=np.float64)
+        self.ant_amp = np.sqrt(np.power(10, (gains + rx_transceiver.rx_ant_gain_db) / 10)) * \
+            (SPEED_OF_LIGHT / (4 * np.pi * dist * f[0]))
+        self.steer_phase = utilities.scatterer_steering(tx, pts, f[0])  # [A, R], unit modulus
+        self.n_drawn = 0  # realisations drawn so far: the trial index of the next one
+        self.channel_mat_fd = None
+        self.set_channel_mat_fd()
+
+    def __str__(self):
+        return "rays"
+
+    def steer(self, skip_attenuation: bool = False) -> ndarray:
+        """The rays' steering vectors [A, R]: the phases, times ``ant_amp`` unless skipped."""
+        return self.steer_phase if skip_attenuation else self.steer_phase * self.ant_amp[:, None]
+
+    def set_channel_mat_fd(self, channel_mat_fd: ndarray = None, skip_attenuation: bool = False) -> None:
+        if channel_mat_fd is None:
+            self.reroll_channel_coeffs(skip_attenuation)
+        else:
+            self.channel_mat_fd = channel_mat_fd
+
+    def get_channel_mat_fd(self) -> ndarray:
+        return self.channel_mat_fd
+
+    def reroll_channel_coeffs(self, skip_attenuation: bool = False) -> None:
+        self.channel_mat_fd = _engine.rays_channels(self.delays, self.ray_tap, self.ray_amp, self.steer(skip_attenuation),
+                                                    self.fd_samp_size, self.seed, self.n_drawn, 1,
+                                                    ray_kind=self.ray_kind)[0]
         self.n_drawn += 1
 
     def propagate(self, in_sig_mat: ndarray, sum_signals: bool = True) -> ndarray:

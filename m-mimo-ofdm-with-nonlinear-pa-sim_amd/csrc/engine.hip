@@ -154,8 +154,12 @@ struct mimo_engine {
   bool tab_stale = false;
   // MIMO_CH_TDL: the profile (mimo_engine_set_tdl), its device tables (tdl.h TdlHost::blob) and
   // whether those are still to be uploaded.  The generator fills tab64 / tab32 launch by launch.
+  // The profile is a power-delay profile (tdl) or, after mimo_engine_set_rays, a ray-cluster one
+  // (rays, tdl_is_rays): whichever setter was called last.
   bool have_tdl = false;
   mimo::TdlHost tdl;
+  bool tdl_is_rays = false;
+  mimo::RaysHost rays;
   bool tdl_stale = false;
   Buf<double> tdl_blob;
   double last_chan_ms = 0.0;
@@ -661,7 +665,7 @@ int refresh_channel_tables(mimo_engine* e) {
     e->tab_stale = false;
   }
   if (e->tdl_stale) {
-    if (int rc = e->tdl_blob.upload(e->tdl.blob())) return rc;
+    if (int rc = e->tdl_blob.upload(e->tdl_is_rays ? e->rays.blob() : e->tdl.blob())) return rc;
     e->tdl_stale = false;
   }
   return MIMO_OK;
@@ -1002,10 +1006,14 @@ int run_launch(mimo_engine* e, const mimo::InstanceKey& key, const mimo::TrialPa
     // the bank entries of this launch's blocks, in device memory (tdl.hip), ahead of the trial kernel
     // on the same stream and timed on an event of its own
     MIMO_HIP_TRY(hipEventRecord(e->ev3, e->stream));
-    const hipError_t ge = mimo::launch_tdl(
-        e->stream, e->tdl, e->tdl_blob.p, reinterpret_cast<const mimo::TdlSeg*>(e->blob.p + o.tdl), kp.point_start,
-        (int)t.nseg, nb, e->cfg.n_sub_carr, sizeof(R) == 8 ? e->tab64.p : nullptr, sizeof(R) == 8 ? nullptr : e->tab32.p,
-        nullptr);
+    const mimo::TdlSeg* gsegs = reinterpret_cast<const mimo::TdlSeg*>(e->blob.p + o.tdl);
+    double2* g64 = sizeof(R) == 8 ? e->tab64.p : nullptr;
+    float2* g32 = sizeof(R) == 8 ? nullptr : e->tab32.p;
+    const hipError_t ge =
+        e->tdl_is_rays ? mimo::launch_rays(e->stream, e->rays, e->tdl_blob.p, gsegs, kp.point_start, (int)t.nseg, nb,
+                                           e->cfg.n_sub_carr, g64, g32, nullptr, nullptr)
+                       : mimo::launch_tdl(e->stream, e->tdl, e->tdl_blob.p, gsegs, kp.point_start, (int)t.nseg, nb,
+                                          e->cfg.n_sub_carr, g64, g32, nullptr);
     if (ge != hipSuccess) return fail(MIMO_EHIP, std::string("TDL generator kernel launch: ") + hipGetErrorString(ge));
   }
   MIMO_HIP_TRY(hipEventRecord(e->ev0, e->stream));
@@ -1096,7 +1104,8 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
     return fail(MIMO_EINVAL, "csi_eps >= 0 is not supported with a channel bank of n_bank > 1 (one estimate per table)");
   if (csi && tdl) return fail(MIMO_EINVAL, "csi_eps >= 0 is not supported on a MIMO_CH_TDL engine");
   if (tdl && !e->have_tdl)
-    return fail(MIMO_EINVAL, "a MIMO_CH_TDL engine needs a profile before it runs: mimo_engine_set_tdl was not called");
+    return fail(MIMO_EINVAL, "a MIMO_CH_TDL engine needs a profile before it runs: neither mimo_engine_set_tdl nor "
+                             "mimo_engine_set_rays was called");
   const mimo::InstanceKey key = select_instance(e, csi);
   if (int rc = ensure_device(e)) return rc;
   if (int rc = refresh_channel_tables(e)) return rc;
@@ -1413,6 +1422,21 @@ int32_t mimo_engine_set_tdl(mimo_engine* e, const mimo_tdl* prof) {
   std::string err;
   if (!mimo::tdl_prepare(prof, e->cfg.n_ant, e->cfg.n_fft, &host, &err)) return fail(MIMO_EINVAL, err);
   e->tdl = std::move(host);
+  e->tdl_is_rays = false;
+  e->have_tdl = true;
+  e->tdl_stale = true;
+  return MIMO_OK;
+}
+
+int32_t mimo_engine_set_rays(mimo_engine* e, const mimo_rays* prof) {
+  if (!e) return fail(MIMO_EINVAL, "null engine");
+  if (e->cfg.channel_kind != MIMO_CH_TDL)
+    return fail(MIMO_EINVAL, "channel_kind: a ray-cluster profile needs a MIMO_CH_TDL engine");
+  mimo::RaysHost host;
+  std::string err;
+  if (!mimo::rays_prepare(prof, e->cfg.n_ant, e->cfg.n_fft, &host, &err)) return fail(MIMO_EINVAL, err);
+  e->rays = std::move(host);
+  e->tdl_is_rays = true;
   e->have_tdl = true;
   e->tdl_stale = true;
   return MIMO_OK;

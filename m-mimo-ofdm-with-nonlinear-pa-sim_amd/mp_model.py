@@ -290,7 +290,7 @@ class Link:
         self.my_csi_noise = copy.deepcopy(noise_obj)
         self.csi_epsylon = csi_epsylon
         if not isinstance(chan_obj, (channel.MisoRayleighFd, channel.MisoLosFd, channel.MisoTwoPathFd,
-                                     channel.MisoTdlFd)):
+                                     channel.MisoTdlFd, channel.MisoRaysFd)):
             raise NotImplementedError(f"{type(chan_obj).__name__} is out of scope (MATLAB / NumPy-1 channels)")
         self.is_quadriga = False
         self.my_miso_chan = copy.deepcopy(chan_obj)
@@ -332,8 +332,8 @@ class Link:
             return "rayleigh"
         if isinstance(self.my_miso_chan, channel.MisoTwoPathFd):
             return "two_path"
-        if isinstance(self.my_miso_chan, channel.MisoTdlFd):
-            return "tdl"
+        if isinstance(self.my_miso_chan, (channel.MisoTdlFd, channel.MisoRaysFd)):
+            return "tdl"  # (a ray-cluster profile runs the TDL engine too)
         return "los"
 
     def _tdl_profile(self):
@@ -344,13 +344,21 @@ class Link:
         ch = self.my_miso_chan
         return ch.delays, ch.powers, ch.ant_amp / np.max(ch.ant_amp)
 
+    def _rays_profile(self):
+        """(delays, ray_tap, ray_amp, steer, ray_kind) of the ray-cluster channel object as the engine
+        takes them, the steering vectors relative to the strongest antenna's amplitude (see
+        ``_tdl_profile``)."""
+        ch = self.my_miso_chan
+        return ch.delays, ch.ray_tap, ch.ray_amp, ch.steer() / np.max(ch.ant_amp), ch.ray_kind
+
     def engine(self, reroll_chan: bool = True):
         """The configured GPU engine for the current grid point (created lazily, per process).
 
         ``reroll_chan=False`` (mp_model.py:190-206: every trial sees the channel object's
         current matrix) runs the table-channel instances on ``channel_mat_fd``.  A ``MisoTdlFd``
         channel with ``reroll_chan=True`` runs a TDL engine on the object's profile: an independent
-        realisation per trial, drawn on the device."""
+        realisation per trial, drawn on the device; a ``MisoRaysFd`` channel runs the same engine
+        on its ray-cluster profile (``Engine.set_rays``)."""
         kind = self._chan_kind()
         table = None
         prof = None
@@ -360,7 +368,8 @@ class Link:
         dev = self.device if self.device is not None else _default_device()
         acquire_device_slot(dev)  # best effort here; simulate() waits for a slot
         if kind == "tdl":
-            prof = self._tdl_profile()
+            rays = isinstance(self.my_miso_chan, channel.MisoRaysFd)
+            prof = self._rays_profile() if rays else self._tdl_profile()
         key = (dev, kind, bool(reroll_chan), self.is_mcnc, self.precision,
                None if table is None else hash(table.tobytes()),
                None if prof is None else hash(b"".join(np.ascontiguousarray(v).tobytes() for v in prof)))
@@ -374,7 +383,7 @@ class Link:
                 channel.carrier_freqs(m.n_fft, rx.carrier_spacing, rx.center_freq), reroll=reroll_chan, device=dev,
                 precision=self.precision, chan_table=table, csi_seed=self.csi_seed if table is not None else 0)
             if prof is not None:
-                self._engine.set_tdl(*prof)
+                (self._engine.set_rays if rays else self._engine.set_tdl)(*prof)
             self._engine_key = key
         self._push_point()
         return self._engine

@@ -42,10 +42,18 @@ BASELINE_C4 = dict(ibo=np.arange(0.0, 7.01, 0.5), ebn0=np.arange(0.0, 30.01, 0.5
                    n_ant=64, n_sc=2048, n_fft=4096, qam=64, cp=128, bits_sent_max=int(5e6), n_err_min=int(1e5))
 
 
-def make_channel(kind, tx_transceivers, rx_transceiver, tdl=(8, 4, 3.0)):
+RAYS_DEFAULT = (None, 20, 5.0, 300.0, None)  # clusters (None: tdl's taps), rays each, spread [deg], radius [m], K [dB]
+
+
+def make_channel(kind, tx_transceivers, rx_transceiver, tdl=(8, 4, 3.0), rays=RAYS_DEFAULT):
     """The channel object of ``kind``: "rayleigh" (seed 1234, as the reference's drivers), "los",
-    "two_path", or "tdl" -- a ``MisoTdlFd`` on the stand-in profile ``utilities.exp_pdp(*tdl)``
-    (taps, step in samples, decay in dB per tap)."""
+    "two_path", "tdl" -- a ``MisoTdlFd`` on the stand-in profile ``utilities.exp_pdp(*tdl)``
+    (taps, step in samples, decay in dB per tap) -- or "rays": a ``MisoRaysFd`` with one cluster per
+    tap of that profile (``rays[0]`` clusters in place of ``tdl[0]`` taps where given) on the stand-in
+    geometry ``utilities.ring_clusters``: ``rays[1]`` rays per cluster of rms spread ``rays[2]`` deg on
+    the circle of radius ``rays[3]`` at the user's height, the clusters' azimuths spread evenly over
+    the half-plane the user is in, and with ``rays[4]`` (a K factor in dB) a specular ray towards
+    the user."""
     import channel as ch_mod
     import utilities
     if kind == "rayleigh":
@@ -54,16 +62,27 @@ def make_channel(kind, tx_transceivers, rx_transceiver, tdl=(8, 4, 3.0)):
         delays, powers = utilities.exp_pdp(*tdl)
         return ch_mod.MisoTdlFd(tx_transceivers=tx_transceivers, rx_transceiver=rx_transceiver, delays=delays,
                                 powers_db=10 * np.log10(powers), seed=1234)
+    if kind == "rays":
+        n_cl, per, spread, radius, k_db = rays
+        delays, powers = utilities.exp_pdp(tdl[0] if n_cl is None else n_cl, tdl[1], tdl[2])
+        side = 1.0 if rx_transceiver.cord_y >= 0 else -1.0
+        az = side * 180.0 * (np.arange(len(delays)) + 0.5) / len(delays)
+        los = None if k_db is None else (rx_transceiver.cord_x, rx_transceiver.cord_y, rx_transceiver.cord_z)
+        ray_tap, ray_amp, ray_kind, points = utilities.ring_clusters(delays, powers, az, spread, per, radius,
+                                                                     z=rx_transceiver.cord_z, k_db=k_db, los_point=los)
+        return ch_mod.MisoRaysFd(tx_transceivers=tx_transceivers, rx_transceiver=rx_transceiver, delays=delays,
+                                 ray_tap=ray_tap, ray_amp=ray_amp, points=points, ray_kind=ray_kind, seed=1234)
     ch = ch_mod.MisoLosFd() if kind == "los" else ch_mod.MisoTwoPathFd()
     ch.calc_channel_mat(tx_transceivers=tx_transceivers, rx_transceiver=rx_transceiver, skip_attenuation=False)
     return ch
 
 
 def paper_link(channel="rayleigh", receiver="cnc", precision="f64", device=None, n_ant=64, n_sc=2048, n_fft=4096,
-               qam=64, cp=128, n_err_min=int(1e5), bits_sent_max=int(5e6), tdl=(8, 4, 3.0)):
+               qam=64, cp=128, n_err_min=int(1e5), bits_sent_max=int(5e6), tdl=(8, 4, 3.0), rays=RAYS_DEFAULT):
     """The reference drivers' Link (main_mp_miso_cnc_constant_ber_req_ebn0_vs_ibo.py:40-98):
     ULA at z = 15 m, RX at (212, 212, 1.5), 3.5 GHz / 15 kHz, soft limiter, seed-1234 Rayleigh
-    (``channel="tdl"``: the TDL channel on ``utilities.exp_pdp(*tdl)``)."""
+    (``channel="tdl"``: the TDL channel on ``utilities.exp_pdp(*tdl)``; ``channel="rays"``: that
+    profile's taps as clusters of rays, ``make_channel``'s ``rays``)."""
     import copy
 
     import antenna_array
@@ -80,7 +99,7 @@ def paper_link(channel="rayleigh", receiver="cnc", precision="f64", device=None,
                                  cord_y=212, cord_z=1.5, center_freq=int(3.5e9), carrier_spacing=int(15e3))
     arr = antenna_array.LinearArray(n_elements=n_ant, base_transceiver=tx, center_freq=int(3.5e9),
                                     wav_len_spacing=0.5, cord_x=0, cord_y=0, cord_z=15)
-    ch = make_channel(channel, arr.array_elements, rx, tdl)
+    ch = make_channel(channel, arr.array_elements, rx, tdl, rays)
     return mp_model.Link(mod_obj=mod, array_obj=arr, std_rx_obj=rx, chan_obj=ch, noise_obj=noise.Awgn(snr_db=10),
                          rx_loc_var=10.0, n_err_min=n_err_min, bits_sent_max=bits_sent_max,
                          is_mcnc=receiver == "mcnc", device=device, precision=precision)
@@ -111,7 +130,8 @@ def owned_points(n_points: int, rank: int, world: int, costs=None) -> list:
 # i.i.d. Rayleigh the distortion is not beamformed (~1/A of it reaches the user); over LoS /
 # two-path it is, and the CNC / MCNC iterations remove ~90 % of it.  Calibrated on the
 # committed one-GPU records of the 915-point grid (profiles/r05/grid/, tests/test_grid_balance.py).
-RESIDUAL_DISTORTION = {"rayleigh": None, "tdl": None, "los": 0.1, "two_path": 0.1}  # (tdl: not calibrated, as Rayleigh)
+RESIDUAL_DISTORTION = {"rayleigh": None, "tdl": None, "rays": None, "los": 0.1,
+                       "two_path": 0.1}  # (tdl, rays: not calibrated, as Rayleigh)
 
 
 def soft_limiter_sdr(ibo_db):
@@ -485,7 +505,8 @@ def _build_link(args, device):
                                  cord_y=212.0, cord_z=1.5, center_freq=int(3.5e9), carrier_spacing=int(15e3))
     arr = antenna_array.LinearArray(n_elements=args.n_ant, base_transceiver=tx, center_freq=int(3.5e9),
                                     wav_len_spacing=0.5, cord_x=0, cord_y=0, cord_z=15)
-    ch = make_channel(args.channel, arr.array_elements, rx, (args.tdl_taps, args.tdl_step, args.tdl_decay_db))
+    ch = make_channel(args.channel, arr.array_elements, rx, (args.tdl_taps, args.tdl_step, args.tdl_decay_db),
+                      (args.rays_clusters, args.rays_per_cluster, args.rays_spread_deg, args.rays_radius, args.rays_k_db))
     return mp_model.Link(mod_obj=mod, array_obj=arr, std_rx_obj=rx, chan_obj=ch, noise_obj=noise.Awgn(snr_db=10),
                          rx_loc_var=10.0, n_err_min=args.n_err_min, bits_sent_max=args.bits_sent_max,
                          is_mcnc=args.receiver == "mcnc", device=device)
@@ -521,12 +542,21 @@ def build_parser():
     ap.add_argument("--qam", type=int, default=64)
     ap.add_argument("--pa", choices=["softlim", "rapp"], default="softlim")
     ap.add_argument("--p-hardness", type=float, default=3.0)
-    ap.add_argument("--channel", choices=["rayleigh", "los", "two_path", "tdl"], default="rayleigh",
+    ap.add_argument("--channel", choices=["rayleigh", "los", "two_path", "tdl", "rays"], default="rayleigh",
                     help="tdl: a tapped-delay-line Rayleigh channel (frequency-selective) on the stand-in profile of "
-                         "--tdl-taps, --tdl-step and --tdl-decay-db (utilities.exp_pdp); every --grid runs on it")
+                         "--tdl-taps, --tdl-step and --tdl-decay-db (utilities.exp_pdp); every --grid runs on it.  "
+                         "rays: the same profile with every tap a cluster of rays (spatially correlated taps) on the "
+                         "stand-in geometry of the --rays-* options (utilities.ring_clusters); every --grid runs on it")
     ap.add_argument("--tdl-taps", type=int, default=8, help="--channel tdl: taps of the profile (1 ... 64)")
     ap.add_argument("--tdl-step", type=int, default=4, help="--channel tdl: tap spacing in whole samples")
     ap.add_argument("--tdl-decay-db", type=float, default=3.0, help="--channel tdl: decay per tap [dB]")
+    ap.add_argument("--rays-clusters", type=int, default=None,
+                    help="--channel rays: clusters, one per tap (default: --tdl-taps)")
+    ap.add_argument("--rays-per-cluster", type=int, default=20, help="--channel rays: rays of every cluster")
+    ap.add_argument("--rays-spread-deg", type=float, default=5.0, help="--channel rays: rms azimuth spread of a cluster")
+    ap.add_argument("--rays-radius", type=float, default=300.0, help="--channel rays: radius of the scatterers' circle [m]")
+    ap.add_argument("--rays-k-db", type=float, default=None,
+                    help="--channel rays: Rician K factor [dB] of a specular ray towards the user (default: none)")
     ap.add_argument("--receiver", choices=["cnc", "mcnc"], default="cnc")
     ap.add_argument("--ibo", type=str, default="0:8:0.5", help="start:stop:step (numpy arange)")
     ap.add_argument("--ebn0", type=str, default="10:22.1:0.5",

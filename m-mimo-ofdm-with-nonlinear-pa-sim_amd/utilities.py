@@ -150,6 +150,57 @@ def exp_pdp(n_taps: int, step: int, decay_db_per_tap: float):
     return (np.arange(n_taps) * step).astype(np.int32), p / np.sum(p)
 
 
+def scatterer_steering(tx_pos, points, freq: float) -> ndarray:
+    """Steering vectors of rays towards point scatterers (``channel.MisoRaysFd``,
+    ``_engine.Engine.set_rays``): ``exp(+2j pi freq |p_a - q_r| / c)`` for the antenna positions
+    ``tx_pos`` [A, 3] and the ``points`` [R, 3], as [A, R].  The phase convention is the LoS classes'
+    (``channel.MisoLosFd``): a ray towards a point is what ``MisoLosFd(skip_attenuation=True)`` gives
+    at ``freq`` for a receiver standing there."""
+    p = np.asarray(tx_pos, dtype=np.float64).reshape(-1, 3)
+    q = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    d = np.sqrt(np.sum((p[:, None, :] - q[None, :, :]) ** 2, axis=2))
+    return np.exp(2j * np.pi * (d * float(freq)) / 299792458.0)
+
+
+def ring_clusters(delays, powers, az_deg, spread_deg: float, rays_per_cluster: int, radius: float, z: float = 0.0,
+                  k_db: float = None, los_point=None):
+    """A stand-in geometry for the ray-cluster channel: one cluster of ``M = rays_per_cluster`` point
+    scatterers per tap on the horizontal circle of ``radius`` around the origin at height ``z``.
+    Cluster ``l`` sits at the azimuths ``az_deg[l] + o_m``, ``o_m = spread_deg (2 m - (M - 1))
+    sqrt(3 / (M^2 - 1))``: ``M`` equally spaced offsets within ``+-sqrt(3) spread_deg`` whose rms is
+    ``spread_deg`` exactly (the uniform distribution of that rms as ``M`` grows; ``M = 1``: offset 0).
+    Every ray of it is diffuse with amplitude ``sqrt(powers[l] / M)``.  With ``k_db`` (a Rician K
+    factor [dB], ``K = 10^(k_db / 10)``) one specular ray towards ``los_point`` joins tap 0 with
+    power ``K / (K + 1) sum(powers)`` and every diffuse power is scaled by ``1 / (K + 1)``: the total
+    stays ``sum(powers)``.
+    -> (ray_tap int32 [R], ray_amp [R], ray_kind uint8 [R], points [R, 3]), the specular ray first;
+    ``scatterer_steering(tx_pos, points, freq)`` gives the rays' steering vectors.  ``delays`` only
+    fixes the number of taps.  No standard's table: a stand-in for anyone who has none at hand."""
+    n_taps, m = len(np.asarray(delays).reshape(-1)), int(rays_per_cluster)
+    p = np.asarray(powers, dtype=np.float64).reshape(-1)
+    az = np.asarray(az_deg, dtype=np.float64).reshape(-1)
+    if n_taps < 1 or p.size != n_taps or az.size != n_taps:
+        raise ValueError("delays, powers and az_deg must hold one value per tap")
+    if m < 1:
+        raise ValueError("rays_per_cluster must be >= 1")
+    if not np.isfinite(spread_deg) or spread_deg < 0 or not radius > 0:
+        raise ValueError("spread_deg must be finite and >= 0, radius > 0")
+    if (k_db is None) != (los_point is None):
+        raise ValueError("k_db and los_point go together")
+    off = np.zeros(1) if m == 1 else float(spread_deg) * (2 * np.arange(m) - (m - 1)) * np.sqrt(3.0 / (m * m - 1))
+    k = 0.0 if k_db is None else 10.0 ** (float(k_db) / 10)
+    ray_tap = np.repeat(np.arange(n_taps), m)
+    ray_amp = np.repeat(np.sqrt(p / (k + 1) / m), m)
+    ray_kind = np.zeros(n_taps * m, np.uint8)
+    points = circle_probes((az[:, None] + off[None, :]).reshape(-1), radius, z)
+    if k_db is not None:
+        ray_tap = np.concatenate(([0], ray_tap))
+        ray_amp = np.concatenate(([np.sqrt(k / (k + 1) * p.sum())], ray_amp))
+        ray_kind = np.concatenate((np.ones(1, np.uint8), ray_kind))
+        points = np.concatenate((np.asarray(los_point, dtype=np.float64).reshape(1, 3), points))
+    return ray_tap.astype(np.int32), ray_amp, ray_kind, points
+
+
 def save_to_csv(data_lst: list, filename: str, directory: str = "figs/csv_results") -> None:
     """One row per vector, ``csv.writer.writerows`` (utilities.py:342-352); the reference
     writes to ``figs/csv_results`` relative to the working directory."""
