@@ -20,6 +20,8 @@
  *                                  per counter index (BICM GMI / achievable rate per CNC / MCNC iteration)
  *     mimo_engine_coded_points     the same trials with the bit and frame errors of an LDPC-coded link after
  *                                  a layered min-sum decoder, per counter index (coded BER / FER per iteration)
+ *     mimo_engine_turbo_points     the same trials with the decoder in the CNC loop: the LDPC decoder's
+ *                                  decisions, not hard slices, re-synthesise the distortion (errors per pass)
  *     mimo_engine_set_channel_bank  a table engine's bank of channel matrices, one per trial (snapshots)
  *     mimo_engine_set_tdl           the power-delay profile of a tapped-delay-line Rayleigh channel, drawn
  *                                   per trial on the device (frequency-selective fading)
@@ -33,6 +35,7 @@
  *     mimo_qam_llr              <- soft_decoding                       modulation.py:29-59
  *     mimo_qam_softbits            the soft mode's max-log soft bit lambda (no reference entry point)
  *     mimo_ldpc_decode             the coded mode's LDPC decoder on caller-given channel values
+ *     mimo_engine_cnc_step         the turbo mode's step kernel on caller-given received vectors and decisions
  *     mimo_ofdm_tx / _rx        <- _tx_ofdm_symbol / _rx_ofdm_symbol   modulation.py:248-293
  *     mimo_fft                  <- utilities.to_freq/time_domain       utilities.py:311-339
  *     mimo_pa                   <- SoftLimiter/Rapp/ThirdOrderNonLin.process  distortion.py
@@ -420,6 +423,59 @@ int32_t mimo_engine_coded_points(mimo_engine* e, int32_t n_points, const mimo_po
                                  int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
                                  uint32_t* per_trial, const mimo_ldpc_code* code, double rho_max, double* coded_out,
                                  double* per_trial_coded, int8_t* per_trial_chan);
+/* Turbo mode (float64 engines with MIMO_RX_CNC; any channel kind, CSI error or PA at the transmitter):
+ * the same trials, the same counts in the same order as mimo_engine_run_points, and per trial the
+ * errors of the coded mode's LDPC-coded link in n_passes passes of a CNC receiver whose distortion
+ * estimate is re-synthesised from the decoder's decisions instead of hard slices (decoder-in-the-loop
+ * CNC).  The receiver's PA model is the point's cnc_pa_kind and its parameters, exactly as the fused
+ * CNC loop uses them.  Everything is integer after the coded mode's one floor.  The code, rho_max, the
+ * channel-value rule c = 2 clamp(floor(rho scale), -32, 31) + 1, the bit stream p = j S + k, the
+ * codeword interleaving (bit n of codeword w at n n_cw + w), the decoder and the four cells are
+ * those of mimo_engine_coded_points, unchanged.  n_passes in [1, 16].
+ *  v_0 = z, the value CNC iteration 0 slices: r + sigma n scaled by 1 / g, in-band, in label order k.
+ *  For pass q = 0 ... n_passes - 1:
+ *   1. c_q is the stream of channel values of v_q, rho signed by the transmitted bits.
+ *   2. The n_cw codewords are decoded to L_q; cells [q][0..3] are the coded mode's four cells on c_q, L_q.
+ *   3. If q is the last pass, stop.  Else the decided bit of stream position p is b_tx XOR [L_q < 0] for
+ *      p < n_cw N (the decoder's decision; L = 0 counts as non-negative) and b_tx XOR [c_q < 0] on the
+ *      undecoded tail (the demapper's decision).  The decided label l_hat[k] has bit j of the stream
+ *      as bit j of the label, MSB first: the I axis, then the Q axis.  s_hat = const[l_hat].
+ *   4. dist = FFT(PA_cnc(IFFT(up(s_hat)))) / alpha_cnc - s_hat, both transforms ortho, up placing the
+ *      symbols in the in-band bins: the CNC step of corrector.py:84-110 with s_hat in place of the slice.
+ *   5. v_{q+1} = z - dist.
+ *  Row of a trial: n_passes * MIMO_CODED_FIXED doubles, all integers.  Pass 0's cells are the coded
+ *  mode's cells at CNC iteration 0, exactly.  If pass q decodes every frame correctly and the stream
+ *  has no tail, the decisions are the transmitted labels and the rows of passes q + 1 and q + 2 are equal.
+ * iters / incl_clean select the counts alone, as in every mode.
+ * turbo_out: [n_points][n_passes * 4] totals (ADDED to; integers held exactly in doubles).
+ * per_trial_turbo: optional [sum n_trials][n_passes * 4].  per_trial_chan: optional
+ * [sum n_trials][n_passes][S log2 M] int8, c_q of every stream position.  per_trial_z: optional
+ * [sum n_trials][S] complex128 (re, im), z.  The buffers of one launch count against one budget,
+ * MIMO_TURBO_BUFFER_BYTES: per trial 16 S bytes of z, S log2 M bytes of channel values (times
+ * n_passes only when per_trial_chan is asked for) and S log2 M bytes of decisions, so a turbo
+ * launch holds floor(2^28 / (16 S + (1 or n_passes) S log2 M + S log2 M)) trials, or fewer
+ * (MIMO_MAX_LAUNCH_TRIALS); per-trial results do not depend on the split.
+ * mimo_engine_last_decode_ms covers the whole pass loop (step kernels and decoders).
+ * MIMO_EINVAL, before any HIP call, with a message naming the field: every rule of the coded call;
+ * a float32 engine; an engine whose receiver is not MIMO_RX_CNC; n_passes outside [1, 16]; a null
+ * turbo_out.  (Added within ABI 8: a library without it is reported by name.) */
+#define MIMO_TURBO_MAX_PASSES 16
+#define MIMO_TURBO_BUFFER_BYTES (256u << 20)
+int32_t mimo_turbo_width(int32_t n_passes); /* MIMO_CODED_FIXED * n_passes; host only */
+int32_t mimo_engine_turbo_points(mimo_engine* e, int32_t n_points, const mimo_point* points, const uint64_t* seeds,
+                                 const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters,
+                                 int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
+                                 uint32_t* per_trial, const mimo_ldpc_code* code, double rho_max, int32_t n_passes,
+                                 double* turbo_out, double* per_trial_turbo, int8_t* per_trial_chan,
+                                 double* per_trial_z);
+/* The seam of the turbo mode: steps 4 and 5 above by the production step kernel, with the engine's
+ * tables and the point's derived parameters, on n caller-given vectors z_iq [n][S] complex128 (re, im)
+ * and decided labels [n][S] in [0, M); v_out [n][S] complex128 = z - dist.  n in [0, 1048576] (2^20, one
+ * launch; n = 0 touches nothing).  Float64 engines with MIMO_RX_CNC.  MIMO_EINVAL before any HIP call: a
+ * float32 or MCNC engine, a null or invalid point, n outside that range, a null array, a label
+ * outside [0, M).  (Added within ABI 8.) */
+int32_t mimo_engine_cnc_step(mimo_engine* e, const mimo_point* point, const double* z_iq, const int32_t* labels,
+                             int64_t n, double* v_out);
 /* Channel bank (MIMO_CH_TABLE engines): many channel matrices on the device, one per trial.
  * tables is [n_bank][n_ant][n_fft] complex, each entry in chan_table's layout.  From then on trial i
  * (the absolute index, first_trial + offset) of mimo_engine_run and of every *_points call uses
@@ -525,7 +581,8 @@ int32_t mimo_rays_channels(const mimo_rays* prof, int32_t n_ant, int32_t n_fft, 
 double mimo_engine_last_kernel_ms(const mimo_engine* e);
 /* ... and of the beamforming kernels of the last beam call (0 after any other call). */
 double mimo_engine_last_beam_ms(const mimo_engine* e);
-/* ... and of the decoder kernels of the last coded call (0 after any other call). */
+/* ... and of the decoder kernels of the last coded call, or of the pass loop (step kernels and
+ * decoders) of the last turbo call (0 after any other call). */
 double mimo_engine_last_decode_ms(const mimo_engine* e);
 /* ... and of the TDL generator kernels of the last call on a MIMO_CH_TDL engine (0 on any other);
  * an event pair of its own: mimo_engine_last_kernel_ms does not include it. */

@@ -179,6 +179,13 @@ SYMBOLS = {
     "mimo_engine_coded_points": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(MimoPoint), _u64p,
                                                   _u64p, _u64p, _i32p, ctypes.c_int32, ctypes.c_int32, _u64p, _u64p,
                                                   _u32p, ctypes.POINTER(LdpcCode), ctypes.c_double, _dp, _dp, _i8p]),
+    "mimo_turbo_width": (ctypes.c_int32, [ctypes.c_int32]),
+    "mimo_engine_turbo_points": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(MimoPoint), _u64p,
+                                                  _u64p, _u64p, _i32p, ctypes.c_int32, ctypes.c_int32, _u64p, _u64p,
+                                                  _u32p, ctypes.POINTER(LdpcCode), ctypes.c_double, ctypes.c_int32, _dp,
+                                                  _dp, _i8p, _dp]),
+    "mimo_engine_cnc_step": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(MimoPoint), _dp, _i32p, ctypes.c_int64,
+                                              _dp]),
     "mimo_engine_last_decode_ms": (ctypes.c_double, [ctypes.c_void_p]),
     "mimo_bank_capacity": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "mimo_engine_set_channel_bank": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, _dp]),
@@ -232,6 +239,7 @@ ENV_FIXED = 4    # include/mimo_engine.h MIMO_ENV_FIXED
 ENV_WIDTH = 2 * ENV_BINS + ENV_FIXED
 SOFT_BINS = 256  # include/mimo_engine.h MIMO_SOFT_BINS
 CODED_FIXED = 4  # include/mimo_engine.h MIMO_CODED_FIXED
+TURBO_MAX_PASSES = 16  # include/mimo_engine.h MIMO_TURBO_MAX_PASSES
 TDL_MAX_TAPS = 64  # include/mimo_engine.h MIMO_TDL_MAX_TAPS
 RAYS_MAX = 1024    # include/mimo_engine.h MIMO_RAYS_MAX
 
@@ -783,6 +791,69 @@ class CodedStats:
                 f"ber={np.array2string(self.ber(), precision=3)}, fer={np.array2string(self.fer(), precision=3)})")
 
 
+class TurboStats:
+    """Coded-link errors of a turbo call (mimo_engine_turbo_points): ``cells[n_passes][4]``, per pass of
+    the decoder-aided CNC receiver the four cells of ``CodedStats`` -- channel values below 0 at the
+    decoded positions, wrong bits after the decoder, wrong frames, frames that fail a parity check --
+    over ``n_frames`` codewords of ``n_code_bits`` bits each.  Pass 0 is the coded mode's CNC iteration
+    0.  ``a + b`` (``a.pool(b)``) pools two measurements of one system, code and number of passes."""
+
+    def __init__(self, cells, n_frames, n_code_bits):
+        self.cells = np.array(cells, np.float64).reshape(-1, CODED_FIXED)
+        self.n_frames, self.n_code_bits = int(n_frames), int(n_code_bits)
+        if self.n_frames < 0 or self.n_code_bits < 1:
+            raise ValueError("n_frames >= 0 and n_code_bits >= 1")
+        if not 1 <= self.cells.shape[0] <= TURBO_MAX_PASSES:
+            raise ValueError(f"n_passes must be in [1, {TURBO_MAX_PASSES}]")
+
+    @property
+    def n_passes(self):
+        return self.cells.shape[0]
+
+    @property
+    def n_bits(self):
+        """Decoded bits per pass."""
+        return self.n_frames * self.n_code_bits
+
+    def _share(self, col, n):
+        return self.cells[:, col] / n if n > 0 else np.zeros(self.n_passes)
+
+    def raw_ber(self):
+        """Uncoded BER at the decoded positions, per pass."""
+        return self._share(0, self.n_bits)
+
+    def ber(self):
+        """BER after the decoder, per pass."""
+        return self._share(1, self.n_bits)
+
+    def fer(self):
+        """Share of codewords with any wrong bit, per pass."""
+        return self._share(2, self.n_frames)
+
+    def syndrome_rate(self):
+        """Share of codewords whose hard decision is no codeword, per pass."""
+        return self._share(3, self.n_frames)
+
+    def undetected(self):
+        """Share of codewords that are wrong and pass every parity check, per pass."""
+        n = self.n_frames
+        return (self.cells[:, 2] - self.cells[:, 3]) / n if n > 0 else np.zeros(self.n_passes)
+
+    def pool(self, other):
+        if not isinstance(other, TurboStats):
+            return NotImplemented
+        if (other.n_code_bits, other.n_passes) != (self.n_code_bits, self.n_passes):
+            raise ValueError("turbo errors of different codes or numbers of passes cannot be pooled")
+        return TurboStats(self.cells + other.cells, self.n_frames + other.n_frames, self.n_code_bits)
+
+    __add__ = pool
+
+    def __repr__(self):
+        return (f"TurboStats(n_passes={self.n_passes}, n_frames={self.n_frames}, n_code_bits={self.n_code_bits}, "
+                f"raw_ber={np.array2string(self.raw_ber(), precision=3)}, "
+                f"ber={np.array2string(self.ber(), precision=3)}, fer={np.array2string(self.fer(), precision=3)})")
+
+
 class Engine:
     """One configured system (the deep-copied objects of a ``Link``) on one GPU."""
 
@@ -1022,6 +1093,62 @@ class Engine:
                                 incl_clean, per_trial, chan)
         return (out[0][0], out[1][0], out[2][0]) + tuple(out[3:])
 
+    def turbo_points(self, points, seeds, first_trials, n_trials, iters, code, rho_max, n_passes, incl_clean=False,
+                     per_trial=False, chan=False, z=False):
+        """run_points in turbo mode (mimo_engine_turbo_points; float64 CNC engines): the same trials and
+        counts, and per point and pass of the decoder-aided CNC receiver the four error counts of the
+        LDPC-coded link (``code``: an ``LdpcCode``; channel values quantised over ``+-rho_max``).
+        -> (err[P, n_idx], bits[P, n_idx], turbo[P, n_passes, 4], per-trial counts [sum n_trials, n_idx] or
+        None, per-trial rows [sum n_trials, n_passes, 4] or None), with ``chan=True`` also the channel
+        values [sum n_trials, n_passes, S log2 M] int8 and with ``z=True`` the received vectors
+        [sum n_trials, S] complex128;
+        TurboStats(turbo[i], n_trials[i] * coded_codewords(code), code.n_bits)."""
+        sb = self.n_sub_carr * int(round(np.log2(self.constel_size)))
+        n_passes = int(n_passes)
+        # (a number out of range is the library's to refuse: the arrays then hold one pass at least, so
+        # that the refusal names n_passes and no empty array's pointer)
+        shape_p = max(1, min(n_passes, TURBO_MAX_PASSES))
+        got = []
+
+        def tail(n, n_idx):
+            got.append(np.zeros((n, shape_p, sb), np.int8) if chan else None)
+            got.append(np.zeros((n, self.n_sub_carr), np.complex128) if z else None)
+            return (_ptr(got[0], ctypes.c_int8) if chan else None,
+                    _ptr(got[1].view(np.float64), ctypes.c_double) if z else None)
+
+        out = self._points_call("mimo_engine_turbo_points", points, seeds, first_trials, n_trials, iters, incl_clean,
+                                per_trial, lambda n_idx: ((shape_p, CODED_FIXED),
+                                                          (ctypes.byref(code) if code is not None else None,
+                                                           ctypes.c_double(float(rho_max)), ctypes.c_int32(n_passes))),
+                                tail)
+        return out + ((got[0],) if chan else ()) + ((got[1],) if z else ())
+
+    def turbo(self, seed, first_trial, n_trials, iters, code, rho_max, n_passes, incl_clean=False, per_trial=False,
+              point=None, chan=False, z=False):
+        """One point (the last set_point's, or ``point``: make_point keywords / MimoPoint).
+        -> (err[n_idx], bits[n_idx], turbo[n_passes, 4], per-trial counts or None, per-trial rows or None
+        [, channel values][, received vectors])."""
+        out = self.turbo_points([self._one_point(point)], [seed], [first_trial], [n_trials], iters, code, rho_max,
+                                n_passes, incl_clean, per_trial, chan, z)
+        return (out[0][0], out[1][0], out[2][0]) + tuple(out[3:])
+
+    def cnc_step(self, z, labels, point=None):
+        """The turbo mode's step kernel on caller-given vectors (mimo_engine_cnc_step): ``z`` [n, S]
+        complex and the decided ``labels`` [n, S] in [0, M) -> ``v = z - dist`` [n, S] complex128, dist the
+        clipping distortion the receiver's PA model (the point's ``cnc_*`` fields) gives the decided
+        symbols.  ``point``: make_point keywords / MimoPoint, or the last set_point's."""
+        pt = self._one_point(point)
+        pt = pt if isinstance(pt, MimoPoint) else self.make_point(**pt)
+        zz = np.ascontiguousarray(np.asarray(z, np.complex128).reshape(-1, self.n_sub_carr))
+        lab = _c(np.asarray(labels).reshape(-1, self.n_sub_carr), np.int32)
+        if lab.shape != zz.shape:
+            raise ValueError("z and labels must both be [n, n_sub_carr]")
+        out = np.zeros(zz.shape, np.complex128)
+        _check(self._L.mimo_engine_cnc_step(self._h, ctypes.byref(pt), _ptr(zz.view(np.float64), ctypes.c_double),
+                                            _ptr(lab, ctypes.c_int32), zz.shape[0],
+                                            _ptr(out.view(np.float64), ctypes.c_double)))
+        return out
+
     @property
     def chan_kernel_ms(self):
         """Device time of the TDL generator kernels of the last call [ms] (0 unless channel="tdl")."""
@@ -1061,7 +1188,8 @@ class Engine:
 
     @property
     def decode_kernel_ms(self):
-        """Device time of the decoder kernels of the last coded call (0 after any other call)."""
+        """Device time of the decoder kernels of the last coded call, or of the whole pass loop (step
+        kernels and decoders) of the last turbo call (0 after any other call)."""
         return self._L.mimo_engine_last_decode_ms(self._h)
 
     @property
@@ -1129,6 +1257,14 @@ def qam_softbits(constel_size, symbols):
 def coded_width(n_iters, incl_clean=False):
     """Doubles of a coded row (mimo_coded_width): 4 per counter index."""
     n = lib().mimo_coded_width(int(n_iters), int(bool(incl_clean)))
+    if n < 0:
+        _check(n)
+    return n
+
+
+def turbo_width(n_passes):
+    """Doubles of a turbo row (mimo_turbo_width): 4 per pass, ``n_passes`` in [1, 16]."""
+    n = lib().mimo_turbo_width(int(n_passes))
     if n < 0:
         _check(n)
     return n

@@ -26,6 +26,7 @@
 #endif
 #include "ldpc.h"
 #include "tdl.h"
+#include "turbo.h"
 
 namespace {
 
@@ -200,6 +201,11 @@ struct mimo_engine {
   Buf<int8_t> cchan;                      // [launch blocks][n_idx][S log2 M]
   Buf<int32_t> ctab;
   double last_decode_ms = 0.0;
+  // turbo calls: the turbo instances' received vectors of one launch and the decoder's decisions; the
+  // channel values (one pass's, or every pass's where the caller asks for them) are in cchan, the
+  // decoder's tables in ctab.  Together at most MIMO_TURBO_BUFFER_BYTES (launch_trials).
+  Buf<double2> tz;                        // [launch blocks][S]
+  Buf<int8_t> thard;                      // [launch blocks][S log2 M]
   // per-launch tables in one device blob, filled by one copy from a pinned host buffer:
   // TrialParams<R>[segments] | uint32 block offsets [segments + 1] |
   // uint32 reduction-slice starts [slices + 1] (<= kSlice trials, one point each) | int32 point of slice [slices]
@@ -267,6 +273,7 @@ mimo::ModeArgs<MODE> mode_args(const mimo_engine* e, double scale) {
   if constexpr (MODE == MIMO_MODE_PLAIN) return {};
   else if constexpr (MODE == MIMO_MODE_BEAM) return {e->bcell.p};
   else if constexpr (MODE == MIMO_MODE_CODED) return {e->cchan.p, scale};
+  else if constexpr (MODE == MIMO_MODE_TURBO) return {e->tz.p};
   else if constexpr (std::tuple_size_v<mimo::ModeArgs<MODE>> == 2) return {e->rows.p, scale};
   else return {e->rows.p};
 }
@@ -318,6 +325,7 @@ hipError_t launch(int mode, const mimo_engine* e, const mimo::InstanceKey& k, di
     MIMO_LAUNCH_MODE(MIMO_MODE_ENV)
     MIMO_LAUNCH_MODE(MIMO_MODE_SOFT)
     MIMO_LAUNCH_MODE(MIMO_MODE_CODED)
+    MIMO_LAUNCH_MODE(MIMO_MODE_TURBO)
 #undef MIMO_LAUNCH_MODE
     default: return launch_sized<R, MIMO_MODE_PLAIN>(e, k, grid, p, found, attr, scale);
   }
@@ -340,13 +348,28 @@ struct CodedCall {
   int8_t* per_trial_chan = nullptr;  // [trials of the call][n_idx][stream], or null
 };
 
+// A turbo call: the coded call's code and stream, and the pass loop's own arguments
+// (mimo_engine_turbo_points).
+struct TurboCall {
+  CodedCall cc;                    // cc.per_trial_chan: [trials of the call][n_passes][stream], or null
+  int n_passes = 1;
+  double* per_trial_z = nullptr;   // [trials of the call][S] complex128, or null
+  // bytes of one trial in the buffers of a launch: z, the streams, the decisions
+  uint64_t trial_bytes(int n_sub_carr) const {
+    return 16ull * (uint64_t)n_sub_carr + (uint64_t)cc.stream * (uint64_t)(cc.per_trial_chan ? n_passes : 1) +
+           (uint64_t)cc.stream;
+  }
+};
+
 // What a row mode adds to a plain run, filled by the extern "C" entry point of the mode.  The mode's
 // instances run and leave per-trial rows of row_width doubles, which are reduced per slice on the
 // device (reduce_spec; measure: reduce_meas) and per point, in slice order, on the host; a launch
 // holds no more trials than the mode's buffer fits (launch_trials).  Particular to a mode:
 //  envelope, soft, coded: the instances take a scale;
 //  beam, coded: the instances fill the launch's cells / channel values instead, and a second kernel
-//   (beam.hip, ldpc.hip) forms the rows from them, from the call's tables (launch_second).
+//   (beam.hip, ldpc.hip) forms the rows from them, from the call's tables (launch_second);
+//  turbo: the instances leave the received vectors, and launch_second runs the pass loop on them
+//   (turbo.hip's step kernel and the decoder, n_passes times), which forms the rows.
 struct RowMode {
   int mode = MIMO_MODE_PLAIN;
   double* out = nullptr;                // [points][width], added into
@@ -354,9 +377,10 @@ struct RowMode {
   double scale = 0.0;                   // envelope, soft, coded
   const BeamCall* beam = nullptr;       // beam only
   const CodedCall* coded = nullptr;     // coded only
+  const TurboCall* turbo = nullptr;     // turbo only
   int width = 0;                        // row_width, once run_points has checked the iteration list
   bool rows() const { return mode != MIMO_MODE_PLAIN; }
-  bool second() const { return beam || coded; }
+  bool second() const { return beam || coded || turbo; }
 };
 
 // Doubles of one trial's row in a mode, and of one point's in the mode's output: what the
@@ -398,6 +422,9 @@ uint64_t launch_trials(const mimo_config& c, const RowMode& rm, int n_idx) {
     case MIMO_MODE_ENV: n = MIMO_ENV_BUFFER_BYTES / row; break;
     case MIMO_MODE_SOFT: n = MIMO_SOFT_BUFFER_BYTES / row; break;
     case MIMO_MODE_CODED: n = MIMO_CODED_BUFFER_BYTES / (rm.coded->stream * (size_t)n_idx); break;
+    case MIMO_MODE_TURBO:
+      n = env_lowered("MIMO_TURBO_BUFFER_BYTES", MIMO_TURBO_BUFFER_BYTES) / rm.turbo->trial_bytes(c.n_sub_carr);
+      break;
     default: break;
   }
   if (c.channel_kind == MIMO_CH_TDL) {
@@ -753,7 +780,7 @@ int validate_points(const mimo_engine* e, int n_points, const mimo_point* pts, c
 // static LDS: check the sum against the CU's LDS before launching (F 8192 holds
 // ~157 KiB statically, so A = 512 (4 KiB) is the edge).  mode: the instance the call launches --
 // the envelope and soft instances hold their histogram on top of the plain instance's static LDS
-// (the measure, spectrum, beam and coded instances hold what the plain one holds).
+// (the measure, spectrum, beam, coded and turbo instances hold what the plain one holds).
 int check_csi_lds(const mimo_engine* e, const mimo::InstanceKey& key, int mode) {
   hipFuncAttributes fa{};
   bool found = false;
@@ -942,19 +969,59 @@ int prepare_second(mimo_engine* e, const RowMode& rm, const Plan& plan, int n_id
     MIMO_HIP_TRY(hipMemcpyAsync(e->bgeo.p, rm.beam->geo.data(), sizeof(double) * rm.beam->geo.size(),
                                 hipMemcpyHostToDevice, e->stream));
   } else {
-    const std::vector<int32_t>& tab = rm.coded->code.tables;
-    if (int rc = e->cchan.ensure(std::max<size_t>(1, plan.max_blocks * (size_t)n_idx * rm.coded->stream))) return rc;
+    const CodedCall& cc = rm.turbo ? rm.turbo->cc : *rm.coded;
+    const std::vector<int32_t>& tab = cc.code.tables;
+    // streams of one trial: one per counter index; turbo: one, or one per pass where they are copied back
+    const size_t per_trial = rm.turbo ? (cc.per_trial_chan ? (size_t)rm.turbo->n_passes : 1) : (size_t)n_idx;
+    if (int rc = e->cchan.ensure(std::max<size_t>(1, plan.max_blocks * per_trial * cc.stream))) return rc;
     if (int rc = e->ctab.ensure(tab.size())) return rc;
     MIMO_HIP_TRY(hipMemcpyAsync(e->ctab.p, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice, e->stream));
+    if (rm.turbo) {
+      if (int rc = e->tz.ensure(std::max<size_t>(1, plan.max_blocks * (size_t)c.n_sub_carr))) return rc;
+      if (int rc = e->thard.ensure(std::max<size_t>(1, plan.max_blocks * cc.stream))) return rc;
+    }
   }
   return MIMO_OK;
 }
 
+// The pass loop of a turbo launch, behind the trial kernel that left the nb received vectors in tz:
+// step<first>, decode, step, decode ... (turbo.h, ldpc.h), pass q's cells to columns 4 q ... 4 q + 3
+// of the trials' rows.  kp: the parameters of that trial launch (its point table is still in the blob).
+hipError_t launch_turbo_passes(mimo_engine* e, const mimo::InstanceKey& key, const TurboCall& tc, double scale,
+                               uint32_t nb, const mimo::TrialParams<double>& kp, bool* found) {
+  const CodedCall& cc = tc.cc;
+  const size_t pass_bytes = cc.per_trial_chan ? (size_t)nb * cc.stream : 0;  // between two passes' streams in cchan
+  for (int q = 0; q < tc.n_passes; ++q) {
+    mimo::StepArgs a{};
+    a.z = e->tz.p;
+    a.hard = e->thard.p;
+    a.chan_in = e->cchan.p + (size_t)std::max(0, q - 1) * pass_bytes;
+    a.n_dec = cc.n_cw * cc.code.n_bits();
+    a.chan_out = e->cchan.p + (size_t)q * pass_bytes;
+    a.scale = scale;
+    if (hipError_t se = mimo::launch_turbo_step(key, q == 0, nb, e->stream, kp, a, found); se != hipSuccess || !*found)
+      return se;
+    const bool last = q + 1 == tc.n_passes;
+    if (hipError_t de = mimo::launch_ldpc(e->stream, cc.code, e->ctab.p, a.chan_out, (int64_t)nb, (int64_t)cc.stream,
+                                          cc.n_cw, cc.n_cw, e->rows.p + (size_t)q * MIMO_CODED_FIXED, nullptr,
+                                          last ? nullptr : e->thard.p, (int64_t)tc.n_passes * MIMO_CODED_FIXED);
+        de != hipSuccess)
+      return de;
+  }
+  return hipSuccess;
+}
+
 // In a launch, behind the trial kernel: the rows of its nb trials from what the instances left, ev2
 // behind it (run_launch times ev1 to ev2), and a coded call's channel values copied back where asked.
-int launch_second(mimo_engine* e, const RowMode& rm, uint32_t nb, int n_idx, uint64_t trials_done) {
+int launch_second(mimo_engine* e, const RowMode& rm, uint32_t nb, int n_idx, uint64_t trials_done,
+                  const mimo::InstanceKey& key, const mimo::TrialParams<double>* kp) {
   hipError_t se = hipSuccess;
-  if (const CodedCall* cc = rm.coded) {
+  if (rm.turbo) {
+    bool found = false;
+    if (!kp) return fail(MIMO_ENOKERNEL, "the turbo pass loop is float64 only");
+    se = launch_turbo_passes(e, key, *rm.turbo, rm.scale, nb, *kp, &found);
+    if (se == hipSuccess && !found) return fail(MIMO_ENOKERNEL, "no step kernel instance for " + e->desc);
+  } else if (const CodedCall* cc = rm.coded) {
     se = mimo::launch_ldpc(e->stream, cc->code, e->ctab.p, e->cchan.p, (int64_t)nb * n_idx, (int64_t)cc->stream, cc->n_cw,
                            cc->n_cw, e->rows.p, nullptr);
   } else {
@@ -966,8 +1033,23 @@ int launch_second(mimo_engine* e, const RowMode& rm, uint32_t nb, int n_idx, uin
 #endif
   }
   if (se != hipSuccess)
-    return fail(MIMO_EHIP, std::string(rm.coded ? "decoder" : "beamforming") + " kernel launch: " + hipGetErrorString(se));
+    return fail(MIMO_EHIP, std::string(rm.turbo ? "turbo pass loop" : rm.coded ? "decoder" : "beamforming") +
+                               " kernel launch: " + hipGetErrorString(se));
   MIMO_HIP_TRY(hipEventRecord(e->ev2, e->stream));
+  if (rm.turbo) {
+    const CodedCall& cc = rm.turbo->cc;
+    const size_t np = (size_t)rm.turbo->n_passes;
+    if (cc.per_trial_chan)  // [trial][pass][stream] from the device's [pass][trial][stream]
+      for (size_t q = 0; q < np; ++q)
+        MIMO_HIP_TRY(hipMemcpy2DAsync(cc.per_trial_chan + (trials_done * np + q) * cc.stream, np * cc.stream,
+                                      e->cchan.p + q * (size_t)nb * cc.stream, cc.stream, cc.stream, nb,
+                                      hipMemcpyDeviceToHost, e->stream));
+    if (rm.turbo->per_trial_z) {
+      const size_t row = 2 * (size_t)e->cfg.n_sub_carr;  // doubles
+      MIMO_HIP_TRY(hipMemcpyAsync(rm.turbo->per_trial_z + trials_done * row, e->tz.p, (size_t)nb * row * sizeof(double),
+                                  hipMemcpyDeviceToHost, e->stream));
+    }
+  }
   if (rm.coded && rm.coded->per_trial_chan) {
     const size_t per_trial = (size_t)n_idx * rm.coded->stream;
     MIMO_HIP_TRY(hipMemcpyAsync(rm.coded->per_trial_chan + trials_done * per_trial, e->cchan.p, (size_t)nb * per_trial,
@@ -1022,8 +1104,11 @@ int run_launch(mimo_engine* e, const mimo::InstanceKey& key, const mimo::TrialPa
   if (!found) return fail(MIMO_ENOKERNEL, "no kernel instance for " + e->desc);
   if (le != hipSuccess) return fail(MIMO_EHIP, std::string("trial kernel launch: ") + hipGetErrorString(le));
   MIMO_HIP_TRY(hipEventRecord(e->ev1, e->stream));
-  if (rm.second())
-    if (int rc = launch_second(e, rm, nb, n_idx, pg->trials_done)) return rc;
+  if (rm.second()) {
+    const mimo::TrialParams<double>* kp64 = nullptr;
+    if constexpr (sizeof(R) == 8) kp64 = &kp;
+    if (int rc = launch_second(e, rm, nb, n_idx, pg->trials_done, key, kp64)) return rc;
+  }
   hipLaunchKernelGGL(reduce_counts, dim3((unsigned)nsl, n_idx), dim3(256), 0, e->stream, e->counts.p, d_slice_first,
                      reinterpret_cast<const int32_t*>(e->blob.p + o.point_of), n_idx, e->tot.p);
   MIMO_HIP_TRY(hipGetLastError());
@@ -1094,7 +1179,8 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
   if (!pts || !seeds || !first_trial || !n_trials) return fail(MIMO_EINVAL, "null point arrays");
   const int n_idx = n_iters + (incl_clean ? 1 : 0);
   const mimo_config& c = e->cfg;
-  rm.width = row_width(rm.mode, c.n_fft, n_idx, rm.beam ? rm.beam->n_probes : 0);
+  rm.width = rm.turbo ? MIMO_CODED_FIXED * rm.turbo->n_passes
+                      : row_width(rm.mode, c.n_fft, n_idx, rm.beam ? rm.beam->n_probes : 0);
   bool csi = false;
   if (int rc = validate_points(e, n_points, pts, first_trial, n_trials, &csi)) return rc;
   if (int rc = validate_distances(e)) return rc;
@@ -1119,7 +1205,9 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
   e->desc = describe(key);
 
   const uint64_t max_trials = launch_trials(c, rm, n_idx);
-  if (max_trials < 1) return fail(MIMO_EINVAL, "n_ant, n_sub_carr: one trial's channel does not fit the bank buffer");
+  if (max_trials < 1)
+    return fail(MIMO_EINVAL, rm.turbo ? "one trial's turbo buffers do not fit MIMO_TURBO_BUFFER_BYTES"
+                                      : "n_ant, n_sub_carr: one trial's channel does not fit the bank buffer");
   const Plan plan = plan_launches(n_points, first_trial, n_trials, max_trials);
   if (tdl) {
     const size_t cells = std::max<size_t>(1, plan.max_blocks * (size_t)c.n_ant * (size_t)c.n_sub_carr);
@@ -1164,7 +1252,7 @@ int run_points(mimo_engine* e, int n_points, const mimo_point* pts, const uint64
   }
   e->last_ms = pg.ms;
   e->last_beam_ms = rm.beam ? pg.second_ms : 0.0;
-  e->last_decode_ms = rm.coded ? pg.second_ms : 0.0;
+  e->last_decode_ms = rm.coded || rm.turbo ? pg.second_ms : 0.0;
   e->last_chan_ms = pg.chan_ms;
   return MIMO_OK;
 }
@@ -1370,6 +1458,88 @@ int32_t mimo_engine_coded_points(mimo_engine* e, int32_t n_points, const mimo_po
   cc.per_trial_chan = per_trial_chan;
   return run_points(e, n_points, points, seeds, first_trial, n_trials, iters, n_iters, incl_clean, err_out, bits_out,
                     per_trial, RowMode{MIMO_MODE_CODED, coded_out, per_trial_coded, scale, nullptr, &cc});
+}
+
+int32_t mimo_turbo_width(int32_t n_passes) {
+  if (n_passes < 1 || n_passes > MIMO_TURBO_MAX_PASSES)
+    return fail(MIMO_EINVAL, "n_passes must be in [1, " + std::to_string(MIMO_TURBO_MAX_PASSES) + "]");
+  return MIMO_CODED_FIXED * n_passes;
+}
+
+int32_t mimo_engine_turbo_points(mimo_engine* e, int32_t n_points, const mimo_point* points, const uint64_t* seeds,
+                                 const uint64_t* first_trial, const uint64_t* n_trials, const int32_t* iters,
+                                 int32_t n_iters, int32_t incl_clean, uint64_t* err_out, uint64_t* bits_out,
+                                 uint32_t* per_trial, const mimo_ldpc_code* code, double rho_max, int32_t n_passes,
+                                 double* turbo_out, double* per_trial_turbo, int8_t* per_trial_chan,
+                                 double* per_trial_z) {
+  if (int rc = row_call(e, "turbo", turbo_out, "turbo_out")) return rc;
+  if (e->cfg.receiver_kind != MIMO_RX_CNC)
+    return fail(MIMO_EINVAL, "receiver_kind: turbo needs a MIMO_RX_CNC engine (MCNC with decoder feedback is not built)");
+  if (mimo_turbo_width(n_passes) < 0) return MIMO_EINVAL;
+  const int n_cw = mimo_coded_codewords(e->cfg.n_sub_carr, e->cfg.constel_size, code);
+  if (n_cw < 0) return MIMO_EINVAL;
+  double scale;
+  if (int rc = scale_of("rho_max", rho_max, 32.0, "scale 32 / rho_max", &scale)) return rc;
+  TurboCall tc;
+  std::string err;
+  if (!mimo::ldpc_prepare(code, &tc.cc.code, &err)) return fail(MIMO_EINVAL, err);
+  tc.cc.n_cw = n_cw;
+  tc.cc.stream = (size_t)e->cfg.n_sub_carr * (size_t)std::lround(std::log2((double)e->cfg.constel_size));
+  tc.cc.per_trial_chan = per_trial_chan;
+  tc.n_passes = n_passes;
+  tc.per_trial_z = per_trial_z;
+  RowMode rm{MIMO_MODE_TURBO, turbo_out, per_trial_turbo, scale};
+  rm.turbo = &tc;
+  return run_points(e, n_points, points, seeds, first_trial, n_trials, iters, n_iters, incl_clean, err_out, bits_out,
+                    per_trial, rm);
+}
+
+int32_t mimo_engine_cnc_step(mimo_engine* e, const mimo_point* point, const double* z_iq, const int32_t* labels,
+                             int64_t n, double* v_out) {
+  if (!e) return fail(MIMO_EINVAL, "null engine");
+  if (e->cfg.precision != MIMO_PREC_F64)
+    return fail(MIMO_EINVAL, "cnc_step needs a float64 engine (no float32 step instances are built)");
+  if (e->cfg.receiver_kind != MIMO_RX_CNC) return fail(MIMO_EINVAL, "receiver_kind: cnc_step needs a MIMO_RX_CNC engine");
+  if (!point) return fail(MIMO_EINVAL, "null point");
+  if (int rc = validate_point(e, point)) return rc;
+  if (n < 0 || n > (1ll << 20)) return fail(MIMO_EINVAL, "n must be in [0, 1048576]");
+  if (n == 0) return MIMO_OK;
+  if (!z_iq || !labels || !v_out) return fail(MIMO_EINVAL, "null z_iq, labels or v_out");
+  const size_t S = (size_t)e->cfg.n_sub_carr, cells = (size_t)n * S;
+  for (size_t i = 0; i < cells; ++i)
+    if (labels[i] < 0 || labels[i] >= e->cfg.constel_size)
+      return fail(MIMO_EINVAL, "labels[" + std::to_string(i) + "] must be in [0, constel_size)");
+  const mimo::InstanceKey key = select_instance(e, false);
+  if (int rc = ensure_device(e)) return rc;
+  using TP = mimo::TrialParams<double>;
+  TP tp = base_params<double>(e, key, Iters{}, 0, 1);
+  fill_point(e, *point, 0, 0, tp);
+  // a one-point table behind the parameters, as a trial launch has it: TP | block offsets {0, n}
+  mimo::DBuf tab, dz, dl, dv;
+  const size_t off = (sizeof(TP) + 15) & ~size_t(15);
+  MIMO_HIP_TRY(tab.alloc(off + 2 * sizeof(uint32_t)));
+  MIMO_HIP_TRY(dz.alloc(cells * 16));
+  MIMO_HIP_TRY(dl.alloc(cells * sizeof(int32_t)));
+  MIMO_HIP_TRY(dv.alloc(cells * 16));
+  const uint32_t start[2] = {0u, (uint32_t)n};
+  MIMO_HIP_TRY(hipMemcpy(tab.p, &tp, sizeof(TP), hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(hipMemcpy(tab.as<char>() + off, start, sizeof start, hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(hipMemcpy(dz.p, z_iq, cells * 16, hipMemcpyHostToDevice));
+  MIMO_HIP_TRY(hipMemcpy(dl.p, labels, cells * sizeof(int32_t), hipMemcpyHostToDevice));
+  tp.points = tab.as<TP>();
+  tp.point_start = reinterpret_cast<const uint32_t*>(tab.as<char>() + off);
+  tp.n_points = 1;
+  mimo::StepArgs a{};
+  a.z = dz.as<double2>();
+  a.labels = dl.as<int32_t>();
+  a.v_out = dv.as<double2>();
+  bool found = false;
+  const hipError_t se = mimo::launch_turbo_step(key, false, (unsigned)n, e->stream, tp, a, &found);
+  if (!found) return fail(MIMO_ENOKERNEL, "no step kernel instance for " + describe(key));
+  if (se != hipSuccess) return fail(MIMO_EHIP, std::string("step kernel launch: ") + hipGetErrorString(se));
+  MIMO_HIP_TRY(hipStreamSynchronize(e->stream));
+  MIMO_HIP_TRY(hipMemcpy(v_out, dv.p, cells * 16, hipMemcpyDeviceToHost));
+  return MIMO_OK;
 }
 
 int64_t mimo_bank_capacity(int32_t n_ant, int32_t n_sub_carr, int32_t precision) {

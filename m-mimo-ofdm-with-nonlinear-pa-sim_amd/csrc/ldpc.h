@@ -38,7 +38,14 @@ bool ldpc_prepare(const mimo_ldpc_code* code, LdpcHost* out, std::string* err);
 //        has a non-zero syndrome.  Every cell written once, by plain stores; integer sums.
 //  app   null, or [n_blocks][n_cw][N] int16: the final L.
 //  tables the device copy of LdpcHost::tables.
+//  hard  null, or the decisions at chan's own addressing (the turbo mode): 1 where the final L < 0,
+//        else 0 (L = 0 counts as non-negative), one int8 per decoded bit; the stores coalesce like
+//        chan's loads.
+//  row_stride  doubles between the rows of two blocks (the turbo mode: a trial's passes side by side).
+//        With hard or a row_stride of its own a second kernel of the same decoder runs, which writes
+//        no app; without either, the kernel of the coded mode.
 hipError_t launch_ldpc(hipStream_t st, const LdpcHost& code, const int32_t* tables, const int8_t* chan,
-                       int64_t n_blocks, int64_t block_stride, int n_stride, int n_cw, double* rows, int16_t* app);
+                       int64_t n_blocks, int64_t block_stride, int n_stride, int n_cw, double* rows, int16_t* app,
+                       int8_t* hard = nullptr, int64_t row_stride = kCodedFixed);
 
 }  // namespace mimo

@@ -7,6 +7,8 @@
 #include "ldpc.h"
 
 #include <algorithm>
+#include <tuple>
+#include <type_traits>
 
 #include "host_util.h"
 
@@ -25,11 +27,19 @@ __device__ __forceinline__ int edge_msg(uint32_t mask, uint32_t mm, int e) {
   return neg ? -mag : mag;
 }
 
+// HARD (the turbo mode's instance alone) takes two more arguments, ta = (int8_t* hard, int64_t
+// row_stride): the sign of every final L (1 iff L < 0) also goes to hard, where given, at chan's own
+// addressing, the block's row is row_stride doubles from the one before, and app is not written.
+// Without it the kernel takes no further argument and is the one it was (as the trial kernel's modes:
+// an unused argument would move the implicit ones).
+template <bool HARD, typename... TA>
 __global__ __launch_bounds__(kMaxThreads) void k_ldpc_decode(int z, int n_rows, int n_cols, int n_dec_iters,
                                                             const int32_t* __restrict__ tables,
                                                             const int8_t* __restrict__ chan, int64_t block_stride,
                                                             int n_stride, int n_cw, double* __restrict__ rows,
-                                                            int16_t* __restrict__ app) {
+                                                            int16_t* __restrict__ app, TA... ta) {
+  static_assert(std::is_same_v<std::tuple<TA...>, std::conditional_t<HARD, std::tuple<int8_t*, int64_t>, std::tuple<>>>);
+  const std::tuple<TA...> turbo(ta...);
   extern __shared__ __attribute__((aligned(8))) unsigned char ldpc_lds[];
   __shared__ int red[kMaxThreads / 64][3];
   const int N = n_cols * z, n_chk = n_rows * z;
@@ -91,7 +101,10 @@ __global__ __launch_bounds__(kMaxThreads) void k_ldpc_decode(int z, int n_rows, 
     for (int n = t; n < N; n += T) {
       const int v = L[n];
       nbit += v < 0;
-      if (app) app[((int64_t)blockIdx.x * n_cw + w) * N + n] = (int16_t)v;
+      if constexpr (!HARD)
+        if (app) app[((int64_t)blockIdx.x * n_cw + w) * N + n] = (int16_t)v;
+      if constexpr (HARD)
+        if (int8_t* hard = std::get<0>(turbo)) hard[(int64_t)blockIdx.x * block_stride + (int64_t)n * n_stride + w] = (int8_t)(v < 0);
     }
     if (t < z)
       for (int r = 0; r < n_rows; ++r) {
@@ -133,7 +146,9 @@ __global__ __launch_bounds__(kMaxThreads) void k_ldpc_decode(int z, int n_rows, 
     __syncthreads();  // red and L are rewritten by the next codeword
   }
   if (t == 0 && rows) {
-    double* o = rows + (int64_t)blockIdx.x * kCodedFixed;
+    int64_t row_stride = kCodedFixed;
+    if constexpr (HARD) row_stride = std::get<1>(turbo);
+    double* o = rows + (int64_t)blockIdx.x * row_stride;
     o[0] = (double)cell_raw;
     o[1] = (double)cell_bit;
     o[2] = (double)cell_frame;
@@ -187,15 +202,20 @@ bool ldpc_prepare(const mimo_ldpc_code* code, LdpcHost* out, std::string* err) {
 }
 
 hipError_t launch_ldpc(hipStream_t st, const LdpcHost& code, const int32_t* tables, const int8_t* chan,
-                       int64_t n_blocks, int64_t block_stride, int n_stride, int n_cw, double* rows, int16_t* app) {
+                       int64_t n_blocks, int64_t block_stride, int n_stride, int n_cw, double* rows, int16_t* app,
+                       int8_t* hard, int64_t row_stride) {
   if (n_blocks <= 0 || n_cw <= 0) return hipSuccess;
-  const hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ldpc_decode),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)code.lds_bytes);
-  if (ae != hipSuccess) return ae;
   const int threads = std::min(kMaxThreads, (code.z + 63) & ~63);
-  hipLaunchKernelGGL(k_ldpc_decode, dim3((unsigned)n_blocks), dim3(threads), code.lds_bytes, st, code.z, code.n_rows,
-                     code.n_cols, code.n_dec_iters, tables, chan, block_stride, n_stride, n_cw, rows, app);
-  return hipGetLastError();
+  auto go = [&](auto* kern, auto... ta) {
+    const hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)code.lds_bytes);
+    if (ae != hipSuccess) return ae;
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_blocks), dim3(threads), code.lds_bytes, st, code.z, code.n_rows, code.n_cols,
+                       code.n_dec_iters, tables, chan, block_stride, n_stride, n_cw, rows, app, ta...);
+    return hipGetLastError();
+  };
+  if (hard || row_stride != kCodedFixed) return go(&k_ldpc_decode<true, int8_t*, int64_t>, hard, row_stride);
+  return go(&k_ldpc_decode<false>);
 }
 
 }  // namespace mimo

@@ -1,7 +1,7 @@
 // Defines launch_trial<F, R, MODE> (trial_launch.h), and with it instantiates the fused trial kernel,
 // for one FFT size, arithmetic type and run mode: compiled once per -DINST_F=<size> -DINST_F64=<0|1>,
 // and once more per size with -DINST_F64=1 -DINST_MODE=<1 measure | 2 spectrum | 3 beam | 4 envelope |
-// 5 soft | 6 coded> (trial_params.h MIMO_MODE_*; 0, plain, by default).
+// 5 soft | 6 coded | 7 turbo> (trial_params.h MIMO_MODE_*; 0, plain, by default).
 #include <type_traits>
 
 #ifndef INST_F
@@ -14,7 +14,7 @@
 #define INST_MODE 0
 #endif
 #if INST_MODE && !INST_F64
-#error "the measure, spectrum, beam, envelope, soft and coded instances are float64 only"
+#error "the measure, spectrum, beam, envelope, soft, coded and turbo instances are float64 only"
 #endif
 
 #include "trial_kernel.h"
@@ -53,11 +53,12 @@ constexpr Profile profile_for(int mode, int T, bool aligned, int ch) {
   // (the F 2048 soft instances: 2 waves/SIMD as well, tuning.h MIMO_SOFT_W64_2048: no spilled VGPR, -4 % at
   // config 2; the smaller soft instances keep the plain target -- at 2 the F 512 generic ones, which need up to
   // 326 VGPRs and run at one wave/SIMD, would be capped at 256 and spill, profiles/r18/soft/resources.txt)
-  // (the F 2048 coded instances: tuning.h MIMO_CODED_W64_2048, profiles/r19/coded/)
+  // (the F 2048 coded instances: tuning.h MIMO_CODED_W64_2048, profiles/r19/coded/; the turbo instances
+  // take the coded instances' target, inherited and not measured)
   if (kF64 && kF <= 2048)
     return Profile{mode == MIMO_MODE_ENV                   ? MIMO_ENV_W64_2048
                    : mode == MIMO_MODE_SOFT && kF == 2048  ? MIMO_SOFT_W64_2048
-                   : mode == MIMO_MODE_CODED && kF == 2048 ? MIMO_CODED_W64_2048
+                   : (mode == MIMO_MODE_CODED || mode == MIMO_MODE_TURBO) && kF == 2048 ? MIMO_CODED_W64_2048
                                                            : MIMO_W64_2048,
                    1, false};
   if (kF64 && kF == 4096) return Profile{2, 1, false};  // 16-point team, symbols from levels: 2 teams/CU

@@ -92,6 +92,7 @@ struct XAddrOf<FFT, true> {
 constexpr bool xaddr_inst_ok(int F, int mode, bool aligned, int ch) {
   constexpr unsigned out1024[7] = {0x91, 0x82, 0x81, 0x91, 0x00, 0xD8, 0xD1};
   constexpr unsigned out2048[7] = {0x80, 0x90, 0x00, 0x80, 0x20, 0x40, 0x80};
+  if (mode == MIMO_MODE_TURBO) mode = MIMO_MODE_CODED;  // the turbo instances: the coded instances' choices, inherited
   if (mode < 0 || mode > 6 || ch < 1 || ch > 4) return false;
   const unsigned bit = 1u << ((aligned ? 0 : 4) + ch - 1);
   return F == 1024 ? !(out1024[mode] & bit) : F == 2048 ? !(out2048[mode] & bit) : false;
@@ -132,6 +133,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
   constexpr bool ENV = MODE == MIMO_MODE_ENV && sizeof(R) == 8;
   constexpr bool SOFT = MODE == MIMO_MODE_SOFT && sizeof(R) == 8;
   constexpr bool CODED = MODE == MIMO_MODE_CODED && sizeof(R) == 8;
+  constexpr bool TURBO = MODE == MIMO_MODE_TURBO && sizeof(R) == 8;
   // ---- which point and trial this block runs (uniform binary search over point_start)
   uint32_t pi = 0;
   if (p0.n_points > 1) {
@@ -1092,6 +1094,12 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MINW))) void 
     const R ig = ((valid_mask >> s) & 1u) ? R(1) / g[s] : R(0);
     const R sn = sig / frel_of(s);
     z[s] = mkc((r[s].x + sn * zn[s].x) * ig, (r[s].y + sn * zn[s].y) * ig);
+    // turbo instances: z of every valid slot to the launch's buffer, sub-carrier order
+    if constexpr (TURBO) {
+      bool ok;
+      const int k = SL::k_of(s, opaque(tf), S, ok);
+      if (ok) std::get<kModeOut>(ma)[(size_t)blockIdx.x * (size_t)S + (size_t)k] = z[s];
+    }
   }
   if constexpr (MEAS) {
     // the noiseless AGC'd value z0 = r / g against the transmitted point: Es, Ez0, C = sum z0 conj(s), Ed0

@@ -51,7 +51,8 @@ hipError_t launch_trial(const InstanceKey& k, dim3 grid, hipStream_t st, const T
   MIMO_DECLARE_LAUNCH_AS(FV, double, MIMO_MODE_BEAM)      \
   MIMO_DECLARE_LAUNCH_AS(FV, double, MIMO_MODE_ENV)       \
   MIMO_DECLARE_LAUNCH_AS(FV, double, MIMO_MODE_SOFT)      \
-  MIMO_DECLARE_LAUNCH_AS(FV, double, MIMO_MODE_CODED)
+  MIMO_DECLARE_LAUNCH_AS(FV, double, MIMO_MODE_CODED)     \
+  MIMO_DECLARE_LAUNCH_AS(FV, double, MIMO_MODE_TURBO)
 MIMO_DECLARE_LAUNCH(128)
 MIMO_DECLARE_LAUNCH(256)
 MIMO_DECLARE_LAUNCH(512)

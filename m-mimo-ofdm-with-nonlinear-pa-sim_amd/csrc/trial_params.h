@@ -17,7 +17,7 @@ enum ChanKind : int { CH_RAYLEIGH = 1, CH_LOS = 2, CH_TWOPATH = 3, CH_TABLE = 4 
 enum RxKind : int { RX_CNC = 1, RX_MCNC = 2 };
 
 // The run mode of an instance: trial_kernel's first template argument (macros, since the Makefile
-// hands one to each trial_inst.hip object as -DINST_MODE=<mode>).  The six row modes are float64 only.
+// hands one to each trial_inst.hip object as -DINST_MODE=<mode>).  The seven row modes are float64 only.
 #define MIMO_MODE_PLAIN 0  // the counts alone
 #define MIMO_MODE_MEAS 1
 #define MIMO_MODE_SPEC 2
@@ -25,6 +25,7 @@ enum RxKind : int { RX_CNC = 1, RX_MCNC = 2 };
 #define MIMO_MODE_ENV 4
 #define MIMO_MODE_SOFT 5
 #define MIMO_MODE_CODED 6
+#define MIMO_MODE_TURBO 7
 
 // What a mode's kernel takes behind TrialParams, each argument with its true type: the buffer its
 // instances fill (kModeOut; the sections below have the layouts) and the mode's scale (kModeScale).
@@ -38,7 +39,8 @@ using ModeArgs = std::conditional_t<
     std::conditional_t<MODE == MIMO_MODE_CODED, std::tuple<int8_t*, double>,              // channel values, 32 / rho_max
                        std::conditional_t<MODE == MIMO_MODE_ENV || MODE == MIMO_MODE_SOFT,
                                           std::tuple<double*, double>,                    // rows, the bin scale
-                                          std::tuple<double*>>>>;                         // measure, spectrum: rows; beam: cells
+                                          std::conditional_t<MODE == MIMO_MODE_TURBO, std::tuple<double2*>,  // the received vectors
+                                                             std::tuple<double*>>>>>;     // measure, spectrum: rows; beam: cells
 constexpr int kModeOut = 0, kModeScale = 1;
 
 // Measure instances (MIMO_MODE_MEAS): the same trial, the same
@@ -109,6 +111,13 @@ constexpr int kEnvFixed = 4;    // MIMO_ENV_FIXED
 // written once, no LDS and no barrier on top of the plain instance's.  The LDPC decoder (ldpc.hip)
 // reads the buffer after the launch.  The buffer and the scale 32 / rho_max are extra arguments of
 // those instances alone.
+
+// Turbo instances (MIMO_MODE_TURBO): the same trial, the same counts, and per trial the AGC'd received
+// vector z -- what CNC iteration 0 slices -- of every valid slot as one complex128 at
+// zbuf[block S + k], sub-carrier order k.  Plain 16-byte stores from the receiver phase, where z is
+// formed; every cell written once, no LDS and no barrier on top of the plain instance's.  The step
+// kernel (turbo.hip; include/mimo_engine.h mimo_engine_turbo_points) reads the buffer after the
+// launch.  The buffer is an extra argument of those instances alone.
 
 constexpr int kMaxCsiAnt = 512;  // CSI-error runs: antennas (dynamic LDS per team, A doubles; engine.hip checks)
 constexpr uint32_t kFixedCsiTrial = 0xFFFFFFFFu;  // CSI stream counter of fixed-channel runs (oracle/sim.py draws)

@@ -761,6 +761,34 @@ class Link:
             lambda eng, *args: eng.coded_points(*args, uniq, code, rho_max, incl_clean_run), need_snr="coded")
         return [_engine.CodedStats(coded[i], int(n[i]) * n_cw, code.n_bits) for i in range(len(n))]
 
+    # ------------------------------------------------------------------ turbo mode
+    def turbo(self, reroll_chan: bool, seed_arr, n_trials: int, code, n_passes: int, rho_max: float = None):
+        """Decoder-in-the-loop CNC of the current grid point over trials [0, n_trials) of ``simulate``'s
+        trial sequence: an ``_engine.TurboStats`` -- per pass the uncoded BER at the decoded positions
+        and the BER and frame error rate after the decoder of ``code``, the distortion estimate of every
+        pass but the first re-synthesised from the decoder's decisions of the pass before.  The link's
+        receiver must be CNC.  ``rho_max=None``: ``32 / nominal_llr_scale()`` as for ``coded``.  A fixed
+        number of trials, no stopping rule."""
+        return self.turbo_points(reroll_chan, [seed_arr], [self.point_params()], n_trials, code, n_passes, rho_max)[0]
+
+    def turbo_points(self, reroll_chan: bool, seed_arrs, point_params, n_trials, code, n_passes: int,
+                     rho_max: float = None) -> list:
+        """``turbo`` for many grid points of this system in one engine call
+        (mimo_engine_turbo_points), all quantised over one ``rho_max`` (``None``:
+        ``32 / nominal_llr_scale`` of the point with the most noise); ``point_params`` as for
+        ``simulate_points``, ``n_trials`` one number or one per point.
+        -> a list of ``_engine.TurboStats``.  Single GPU."""
+        if any(pp["snr_db"] is None for pp in point_params):
+            raise ValueError("set_snr() must be called before turbo()")
+        if rho_max is None:
+            rho_max = max([32.0 / self.nominal_llr_scale(pp) for pp in point_params], default=1.0)
+        rho_max = float(rho_max)
+        n_cw = _engine.coded_codewords(self.my_mod.n_sub_carr, self.my_mod.constel_size, code)
+        (_, _, turbo, _, _), n = self._fixed_trials_call(
+            reroll_chan, seed_arrs, point_params, n_trials,
+            lambda eng, *args: eng.turbo_points(*args, [0], code, rho_max, n_passes), need_snr="turbo")
+        return [_engine.TurboStats(turbo[i], int(n[i]) * n_cw, code.n_bits) for i in range(len(n))]
+
     def update_distortion(self, ibo_val_db: float) -> None:
         """(mp_model.py:230-241)"""
         self.my_array.update_distortion(ibo_db=ibo_val_db, avg_sample_pow=self.my_mod.avg_sample_power)

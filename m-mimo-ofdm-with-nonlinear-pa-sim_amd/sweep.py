@@ -415,6 +415,36 @@ def coded_ber_vs_ebn0_rows(ebn0_arr, stats):
     return rows
 
 
+def turbo_ber_vs_ebn0(link, ibo_arr, ebn0_arr, n_passes, n_trials, code, seed=2137, reroll_chan=True, rho_max=None):
+    """Errors of the decoder-in-the-loop CNC receiver for every IBO of ``ibo_arr`` and every Eb/N0 of
+    ``ebn0_arr``: ``n_trials`` trials per point in ``n_passes`` passes with ``code`` (an
+    ``_engine.LdpcCode``), the IBOs of one Eb/N0 in one ``Link.turbo_points`` call; seeds, ``rho_max``
+    and the Eb/N0 convention as ``coded_ber_vs_ebn0`` has them, so pass 0 is that grid's iteration 0.
+    -> ``stats[i_ibo][i_ebn0]``, ``_engine.TurboStats``."""
+    m = link.my_mod
+    ibo_arr = np.asarray(ibo_arr, dtype=np.float64)
+    ebn0_arr = np.asarray(ebn0_arr, dtype=np.float64)
+    snr_arr = np.asarray(ebn0_to_snr(ebn0_arr, m.n_sub_carr, m.n_sub_carr, m.constel_size), dtype=np.float64)
+    out = [[None] * len(ebn0_arr) for _ in ibo_arr]
+    for j, snr in enumerate(snr_arr):
+        link.set_snr(float(snr))
+        params, seeds = [], []
+        for i, ibo in enumerate(ibo_arr):
+            link.update_distortion(ibo_val_db=float(ibo))
+            params.append(dict(link.point_params()))
+            seeds.append(point_seed(seed, i * len(ebn0_arr) + j))
+        for i, st in enumerate(link.turbo_points(reroll_chan, seeds, params, n_trials, code, n_passes, rho_max)):
+            out[i][j] = st
+    return out
+
+
+def turbo_ber_vs_ebn0_rows(ebn0_arr, stats):
+    """CSV rows of one IBO of the turbo sweep (``stats``: its TurboStats per Eb/N0): the Eb/N0 axis,
+    then per pass four rows -- the uncoded BER at the decoded positions, the BER after the decoder,
+    the frame error rate and the share of frames the parity checks flag."""
+    return coded_ber_vs_ebn0_rows(ebn0_arr, stats)
+
+
 def beam_vs_angle(link, angles_deg, ibo_arr, n_trials, seed=2137, reroll_chan=True, radius=None, z=None):
     """Beampattern of the array over ``angles_deg`` for every IBO of ``ibo_arr``: probes on the
     horizontal circle around the origin through the user (``radius``, ``z``: the link's nominal
@@ -515,7 +545,8 @@ def _build_link(args, device):
 def build_parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--grid", choices=["ber_vs_ebn0", "fixed_ber", "sdr_vs_ibo", "psd_vs_ibo", "beam_vs_angle",
-                                       "ccdf_vs_ibo", "gmi_vs_ebn0", "coded_ber_vs_ebn0"],
+                                       "ccdf_vs_ibo", "gmi_vs_ebn0", "coded_ber_vs_ebn0",
+                                       "turbo_ber_vs_ebn0"],
                     default="fixed_ber",
                     help="sdr_vs_ibo: measured in-band SDR and per-iteration signal-to-error ratio per IBO "
                          "(--n-trials trials per point at the first --ebn0 value; one GPU).  psd_vs_ibo: the "
@@ -531,9 +562,14 @@ def build_parser():
                          "other row grids without the clean index, which sweep.gmi_vs_ebn0(incl_clean=True) adds).  "
                          "coded_ber_vs_ebn0: per IBO and Eb/N0 the uncoded BER, the BER and frame error rate after a "
                          "layered min-sum LDPC decoder and the share of flagged frames, per recorded iteration, "
-                         "with the stand-in code of --ldpc (--n-trials trials per point; one GPU)")
+                         "with the stand-in code of --ldpc (--n-trials trials per point; one GPU).  "
+                         "turbo_ber_vs_ebn0: the same four figures per pass of the decoder-in-the-loop CNC receiver "
+                         "(--turbo-passes passes, the decoder's decisions fed back into the distortion estimate; "
+                         "--receiver cnc; --n-trials trials per point; one GPU)")
     ap.add_argument("--ldpc", type=str, default="128,4,8,10",
-                    help="coded_ber_vs_ebn0: z,n_rows,n_cols,n_dec_iters of utilities.qc_ldpc_code (seed 0)")
+                    help="coded_ber_vs_ebn0, turbo_ber_vs_ebn0: z,n_rows,n_cols,n_dec_iters of utilities.qc_ldpc_code "
+                         "(seed 0)")
+    ap.add_argument("--turbo-passes", type=int, default=2, help="turbo_ber_vs_ebn0: passes, 1 ... 16")
     ap.add_argument("--angles", type=str, default="0:180.1:1", help="beam_vs_angle: start:stop:step [deg]")
     ap.add_argument("--n-ant", type=int, default=64)
     ap.add_argument("--n-sc", type=int, default=2048)
@@ -675,6 +711,25 @@ def main():
                 "_".join(str(v) for v in iters))
             save_to_csv(coded_ber_vs_ebn0_rows(ebn0_arr, stats[i]), name, directory=args.out)
         print(f"coded sweep done: {len(ibo_arr)} IBO x {len(ebn0_arr)} Eb/N0 points x {args.n_trials} trials in "
+              f"{time.perf_counter() - t0:.1f} s -> {args.out}")
+        return
+    if args.grid == "turbo_ber_vs_ebn0":
+        if world > 1:
+            raise SystemExit("--grid turbo_ber_vs_ebn0 runs on one GPU")
+        if args.receiver != "cnc":
+            raise SystemExit("--grid turbo_ber_vs_ebn0 needs --receiver cnc")
+        from utilities import qc_ldpc_code
+        z, n_rows, n_cols, n_dec = (int(v) for v in args.ldpc.split(","))
+        code = qc_ldpc_code(z, n_rows, n_cols, n_dec)
+        t0 = time.perf_counter()
+        stats = turbo_ber_vs_ebn0(link, ibo_arr, ebn0_arr, args.turbo_passes, args.n_trials, code, args.seed)
+        for i, ibo in enumerate(ibo_arr):
+            name = "turbo_ber_vs_ebn0_%s_nant%d_ibo%1.2f_ebn0_min%d_max%d_step%1.2f_ntrials%d_z%d_%dx%d_dec%d_passes%d" % (
+                args.channel, args.n_ant, ibo, min(ebn0_arr), max(ebn0_arr),
+                ebn0_arr[1] - ebn0_arr[0] if len(ebn0_arr) > 1 else 0.0, args.n_trials, z, n_rows, n_cols, n_dec,
+                args.turbo_passes)
+            save_to_csv(turbo_ber_vs_ebn0_rows(ebn0_arr, stats[i]), name, directory=args.out)
+        print(f"turbo sweep done: {len(ibo_arr)} IBO x {len(ebn0_arr)} Eb/N0 points x {args.n_trials} trials in "
               f"{time.perf_counter() - t0:.1f} s -> {args.out}")
         return
     t0 = time.perf_counter()
